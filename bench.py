@@ -17,7 +17,12 @@ An unaided `bench.py --gpus N` (no WORLD_SIZE in the environment) starts torchru
 with N ranks itself as a child process; a WORLD_SIZE that differs from --gpus is
 an error.
 
-Extra fields: "roofline" (dominant kernel, HIP-event kernel times),
+A plain run (`--gpus 1 --steps K --warmup W`) does only what `value` needs: it
+sets up, warms up, times the K steps, writes the tables the last timed step left
+if --dump-outputs DIR is given (DIR/P.npy, Q.npy, accP.npy, accQ.npy, float32),
+and prints the result line.  Everything below runs only with --full.
+
+Extra fields (--full): "roofline" (dominant kernel, HIP-event kernel times),
 "cpu_baseline" (the reference's CPU hot loop restated in torch-CPU on every
 host thread, one ml-1m epoch, APR and BPR phases), "roofline_large_batch" /
 "roofline_large_batch_d64" (BASELINE configs[4]: batch 65,536 on 10M x 5M tables,
@@ -47,6 +52,13 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=3882, help="timed mini-batches (3882 = 2 ml-1m epochs)")
     p.add_argument("--warmup", type=int, default=1941)
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline line: the kernel-timing pass (roofline, "
+                        "step_bandwidth, batch_stats), the CPU baseline, the split-step, NeuMF, evaluation and "
+                        "synthetic-large lines (each with its --no-* switch)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the tables they left (P, Q and their Adagrad slots accP, "
+                        "accQ) as DIR/<name>.npy, float32")
     p.add_argument("--batch", type=int, default=512)
     p.add_argument("--dim", type=int, default=64)
     p.add_argument("--chunk", type=int, default=647,
@@ -72,7 +84,10 @@ def parse():
                    help="per-batch launches (two kernels per step) instead of the streamed step k_stream (A/B)")
     p.add_argument("--mapping", default="auto", choices=["auto", "wave", "group"],
                    help="slot mapping of the step kernels (auto: by batch size)")
-    return p.parse_args()
+    a = p.parse_args()
+    if not a.full:  # a plain run measures the headline line alone
+        a.no_cpu_baseline = a.no_sharded = a.no_neumf = a.no_eval = a.no_large = True
+    return a
 
 
 def log(*a):
@@ -165,6 +180,24 @@ def make_triplets(acf, ds, B, n_batches, dev, seed):
         e += 1
     n = n_batches * B
     return torch.cat(us)[:n].contiguous(), torch.cat(is_)[:n].contiguous(), torch.cat(js)[:n].contiguous()
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, tabs, rank=0):
+    """--dump-outputs: the tables as the last timed step left them (what a caller
+    of PlanPipeline.run holds afterwards), float32, as <path>/<name>.npy (rank r > 0
+    of a replica run: <name>_rank<r>.npy).  Tables beyond DUMP_LIMIT_BYTES in all
+    are written as a fixed, seeded sample of their rows (ascending row order)."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() * 4 for t in tabs)
+    for name, t in zip(("P", "Q", "accP", "accQ"), tabs):
+        x = t.detach().to(torch.float32).cpu().numpy()
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(x.shape[0] * DUMP_LIMIT_BYTES / total))
+            x = x[np.sort(np.random.default_rng(2019).choice(x.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + (f"_rank{rank}" if rank else "") + ".npy"), np.ascontiguousarray(x))
 
 
 def init_tables(U1, I1, d, dev, seed):
@@ -712,10 +745,14 @@ def main():
     ds = acf.ml1m_like(seed=2019 + rank)
     U1, I1 = ds.num_users + 1, ds.num_items + 1
     total = a.warmup + a.steps
-    u, i, j = make_triplets(acf, ds, B, max(total, a.time_batches, a.cpu_batches), dev, seed=rank)
-    tabs = init_tables(U1, I1, d, dev, seed=rank)
-    P0, Q0 = tabs[0].clone(), tabs[1].clone()
     chunk = min(a.chunk, a.steps)
+    # the batches the warm-up calls below read; --full's timing pass and CPU baseline
+    # read a prefix of the same stream (its first batches do not depend on its length)
+    need = max(total, 2 * chunk + a.steps % chunk)
+    u, i, j = make_triplets(acf, ds, B, max(need, a.time_batches, a.cpu_batches) if a.full else need, dev,
+                            seed=rank)
+    tabs = init_tables(U1, I1, d, dev, seed=rank)
+    P0, Q0 = (tabs[0].clone(), tabs[1].clone()) if a.full else (None, None)
     # chunk c+1 is planned on a side stream beside chunk c's streamed step
     pipe = ops.PlanPipeline(U1, I1, d, B, chunk, dev, overlap=False if a.no_plan_overlap else None)
     pipe.set_slot_mapping(a.mapping)
@@ -731,7 +768,9 @@ def main():
     # one-off host costs (≈25 us of enqueue on a 20-batch call), and the next few
     # are still ~5 us slower than the steady state of a training loop that issues
     # it over and over (tools/short_call.py --same: 133, 130, 128, ... 126 us)
-    for _ in range(3):
+    # (a call of more than 100,000 batches runs for the better part of a second:
+    # those costs vanish in it, and one issue is enough)
+    for _ in range(3 if a.steps <= 100_000 else 1):
         pipe.run(tabs, hp, u, i, j, a.warmup, a.steps, graph=graph)
         torch.cuda.synchronize(dev)
     torch.cuda.synchronize(dev)
@@ -752,12 +791,8 @@ def main():
     finite = bool(torch.isfinite(tabs[0]).all() and torch.isfinite(tabs[1]).all())
     step_errors = pipe.step_errors()
     recoveries = pipe.stream_recoveries()  # streamed calls replayed (a hand-off wait gave up)
-    # roofline of the dominant kernel (separate eager pass with per-launch events)
-    tctx = ops.APRContext(U1, I1, d, B, a.time_batches, dev)
-    tctx.set_slot_mapping(a.mapping)
-    tctx.set_stream(not a.no_stream)
-    st = batch_stats(u, i, j, B, a.time_batches, U1, I1)
-    roof = kernel_roofline(ops, tctx, tabs, hp, u, i, j, B, d, a.time_batches, st)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, tabs, rank)
 
     out = {
         "metric": "BPR triplets/sec (APR ml-1m d=64)",
@@ -777,19 +812,26 @@ def main():
                    "users": ds.num_users, "items": ds.num_items, "dim": d, "global_batch": B * world,
                    "per_gpu_batch": B, "parallelism": f"replicas x{world}",
                    "launch": "eager" if a.eager else "hipGraph"},
-        "roofline": roof,
-        "step_bandwidth": step_bandwidth(d, B, st, value / world),
-        "batch_stats": {k: round(v, 1) for k, v in st.items()},
         "tables_finite": finite,
         "step_errors": step_errors,
         "stream_recoveries": recoveries,
-        "step_stream": roof["kernel"].startswith("k_stream"),
         # the process group this line was measured in: ranks, backend, and how many
         # of them talk over RCCL (0 for the one-GPU gloo rehearsal)
         "world": {"ranks": world, "backend": None if dist is None else dist.get_backend(),
                   "rccl_ranks": world if dist is not None and dist.get_backend() == "nccl" else 0,
                   "gpus_flag": a.gpus, "rehearsal": bool(a.rehearse_one_gpu)},
     }
+    tctx = None
+    if a.full:
+        # roofline of the dominant kernel (separate eager pass with per-launch events)
+        tctx = ops.APRContext(U1, I1, d, B, a.time_batches, dev)
+        tctx.set_slot_mapping(a.mapping)
+        tctx.set_stream(not a.no_stream)
+        st = batch_stats(u, i, j, B, a.time_batches, U1, I1)
+        out["roofline"] = roof = kernel_roofline(ops, tctx, tabs, hp, u, i, j, B, d, a.time_batches, st)
+        out["step_bandwidth"] = step_bandwidth(d, B, st, value / world)
+        out["batch_stats"] = {k: round(v, 1) for k, v in st.items()}
+        out["step_stream"] = roof["kernel"].startswith("k_stream")
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cb = cpu_baseline(u, i, j, P0, Q0, B, a.cpu_batches)
         out["vs_cpu_baseline"] = round(value / cb["value"], 2)  # vs_baseline: the published 87k

@@ -43,6 +43,41 @@ def test_launch_command_passes_every_flag():
     assert cmd[k + 1:] == argv
 
 
+def test_plain_run_measures_the_headline_alone(monkeypatch):
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = b.parse()
+    assert not a.full and a.dump_outputs is None and a.steps == 20 and a.warmup == 5
+    assert a.no_cpu_baseline and a.no_sharded and a.no_neumf and a.no_eval and a.no_large
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-large", "--dump-outputs", "d"])
+    a = b.parse()
+    assert a.full and a.dump_outputs == "d" and a.no_large
+    assert not (a.no_cpu_baseline or a.no_sharded or a.no_neumf or a.no_eval)
+
+
+def test_dump_outputs_writes_float32_tables(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    b = _bench()
+    g = torch.Generator().manual_seed(0)
+    tabs = [torch.randn(n, 8, generator=g) for n in (37, 23, 37, 23)]
+    b.dump_outputs(str(tmp_path / "o"), tabs)
+    for name, t in zip(("P", "Q", "accP", "accQ"), tabs):
+        x = np.load(tmp_path / "o" / f"{name}.npy")
+        assert x.dtype == np.float32 and np.array_equal(x, t.numpy())
+    # beyond the size limit: the same seeded rows on every call, within the limit
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 2000)
+    b.dump_outputs(str(tmp_path / "s1"), tabs)
+    b.dump_outputs(str(tmp_path / "s2"), tabs, rank=1)
+    total = 0
+    for name, t in zip(("P", "Q", "accP", "accQ"), tabs):
+        x, y = np.load(tmp_path / "s1" / f"{name}.npy"), np.load(tmp_path / "s2" / f"{name}_rank1.npy")
+        assert np.array_equal(x, y) and 0 < x.shape[0] < t.shape[0]
+        assert all((t.numpy() == r).all(1).any() for r in x)
+        total += x.nbytes
+    assert total <= 2000
+
+
 def _run_bench(args, env_extra):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)

@@ -11,7 +11,7 @@ if [ -z "$NO_TESTS" ]; then
     ${TESTS:-tests} -m gpu > $OUT/pytest.log 2>&1 || { tail -40 $OUT/pytest.log; exit 1; }
   tail -2 $OUT/pytest.log
 fi
-ARGS="--no-sharded --no-neumf --no-large --no-cpu-baseline --no-eval"
+ARGS="--full --no-sharded --no-neumf --no-large --no-cpu-baseline --no-eval"
 for k in $(seq 1 ${REPS:-3}); do
   for v in ${AV:-head} base; do
     if [ "$v" = base ]; then L=""; else L=$PWD/tools/libacf_apr_$v.so; fi

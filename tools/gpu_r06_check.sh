@@ -9,7 +9,7 @@ timeout -k 10 ${TEST_TIMEOUT:-600} python3 -u -m pytest -x -v --timeout 200 --ti
   > $OUT/pytest.log 2>&1
 tail -3 $OUT/pytest.log
 if [ -z "$NO_REHEARSE" ]; then
-  timeout -k 10 400 python3 bench.py --gpus 2 --rehearse-one-gpu --no-large --no-neumf --no-eval --steps 20 --warmup 5 \
+  timeout -k 10 400 python3 bench.py --full --gpus 2 --rehearse-one-gpu --no-large --no-neumf --no-eval --steps 20 --warmup 5 \
     --sharded-steps 4 > $OUT/bench_gpus2_unaided.json 2> $OUT/bench_gpus2_unaided.err
   python3 -c "
 import json;d=json.loads(open('$OUT/bench_gpus2_unaided.json').read().strip().splitlines()[-1])
@@ -17,7 +17,7 @@ print('n_gpus', d['n_gpus'], 'world', d['world'], 'value', d['value'], 'step_err
 for k, v in d.get('sharded', {}).items(): print(k, v.get('n_gpus'), v.get('value'), v.get('config', {}).get('parallelism'))"
 fi
 if [ -z "$NO_BENCH" ]; then
-  timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench_steps20.err
+  timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench_steps20.err
   python3 -c "
 import json;d=json.loads(open('$OUT/bench_steps20.json').read().strip().splitlines()[-1])
 print('value', d['value'], 'frac', d['roofline']['frac'], 'cpu', d.get('cpu_baseline', {}).get('value'))

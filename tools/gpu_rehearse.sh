@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${OUT_TAG:-rehearse_n${NPROC:-2}}
 mkdir -p $OUT
 timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node ${NPROC:-2} --master-addr 127.0.0.1 \
-  --master-port 29533 bench.py --gpus ${NPROC:-2} --steps 20 --warmup 5 --rehearse-one-gpu \
+  --master-port 29533 bench.py --full --gpus ${NPROC:-2} --steps 20 --warmup 5 --rehearse-one-gpu \
   --no-large --no-neumf --sharded-steps 4 > $OUT/bench_n.json 2> $OUT/bench_n.err
 python3 -c "
 import json;d=json.loads(open('$OUT/bench_n.json').read().strip().splitlines()[-1])
