@@ -75,6 +75,9 @@ SIGNATURES = {
     "acf_eval_positions_all_kernel": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _I32, _I32, _P, _P, _P,
                                                      _I32, _P]),
     "acf_eval_positions_list": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _I32, _P, _P, _P, _P]),
+    "acf_recommend_topk_workspace": (ctypes.c_int, [_I32, _I32, _I32, _I32, ctypes.POINTER(ctypes.c_size_t)]),
+    "acf_recommend_topk": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _I32, _I32, _P, _P, _I32, _P, _P, _P,
+                                          ctypes.c_size_t, _I32, _P]),
     "acf_sample_epoch": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _U64, _I32, _I32, _P, _P,
                                         _P, _P]),
     "acf_gather_bpr_fwd_bwd": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _P, _I64, _F, _F, _P, _P, _P,

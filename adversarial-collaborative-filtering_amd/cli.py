@@ -60,7 +60,37 @@ def parse_args(argv=None, flavor="ori"):
     p.add_argument("--seed", type=int, default=0, help="Seed of init and device sampler.")
     p.add_argument("--sampler", choices=["device", "host"], default="device")
     p.add_argument("--no_graph", action="store_true", help="Launch eagerly instead of hipGraph replay.")
+    p.add_argument("--topk", type=int, default=0,
+                   help="After training, write each user's K best items (train items excluded) to "
+                        "<out>/<runName>.topk (0: off).")
     return p.parse_args(argv)
+
+
+def write_topk(path, name, items):
+    """One line per user 0..n-1 of an [n, K] item array: "user<TAB>item1,item2,...",
+    best first; the -1 padding of a user with fewer than K candidates is left out."""
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, name), "w") as f:
+        for u, row in enumerate(items):
+            f.write("%d\t%s\n" % (u, ",".join(str(int(i)) for i in row if i >= 0)))
+
+
+def read_topk(file, k=None):
+    """The int32 [n, K] array write_topk wrote (short lines padded with -1; K: the
+    longest line unless given)."""
+    import numpy as np
+    rows = []
+    with open(file) as f:
+        for n, line in enumerate(f):
+            user, _, items = line.rstrip("\n").partition("\t")
+            if int(user) != n:
+                raise ValueError(f"{file}: line {n} is for user {user}")
+            rows.append([int(i) for i in items.split(",") if i])
+    k = max([len(r) for r in rows], default=0) if k is None else k
+    out = np.full((len(rows), k), -1, dtype=np.int32)
+    for n, r in enumerate(rows):
+        out[n, :len(r)] = r[:k]
+    return out
 
 
 def init_logging(args, time_stamp):
@@ -107,4 +137,9 @@ def main(argv=None, flavor="ori"):
     else:
         print("model %r is not on the APR path of this build (bpr, apr)" % args.model, file=sys.stderr)
         return 2
+    if args.topk > 0:
+        from .evaluate import recommend
+        final = amf if args.model == "apr" else m
+        items, _ = recommend(final, dataset, k=args.topk)
+        write_topk(out, runName + ".topk", items)
     return 0

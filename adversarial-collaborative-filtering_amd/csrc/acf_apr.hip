@@ -3577,6 +3577,7 @@ __global__ void __launch_bounds__(256) k_forward(const float* __restrict__ P,
 }
 
 #include "acf_eval.h"  // all-items evaluation (k_eval_*): DESIGN.md §4
+#include "acf_topk.h"  // top-K recommendation lists (k_topk_*): DESIGN.md §4b
 
 // ---------------------------------------------------------------------------
 // sampler (shuffle / _get_train_batch, APR.py:39-81)
@@ -5624,6 +5625,88 @@ extern "C" int acf_eval_positions_all_kernel(const float* P, const float* Q, int
                                              int32_t* positions, int32_t kernel, void* stream_) {
   return eval_positions_all(P, Q, U1, I1, d, users, tests, n_users, num_cand, excl_off, excl, positions, kernel,
                             stream_);
+}
+
+// kernel: 0 auto, 1 the MFMA sweep k_topk_mfma, 2 the VALU sweep k_topk_valu;
+// identical outputs.  auto: the VALU sweep below ACF_TOPK_VALU_PAIRS user x candidate pairs.
+// Measured at K = 100, d = 64 the VALU sweep is 5-6x faster than the MFMA
+// sweep at ml-1m (22M pairs) and pinterest-20 (547M pairs) alike, so no measured size
+// crosses over: auto is the VALU sweep.
+#define ACF_TOPK_VALU_PAIRS INT64_MAX
+static int topk_kernel(int32_t n_users, int32_t num_cand, int32_t kernel) {
+  if (kernel == 0) return (int64_t)n_users * num_cand < ACF_TOPK_VALU_PAIRS ? 2 : 1;
+  return kernel;
+}
+
+static int topk_check(int32_t n_users, int32_t num_cand, int32_t k, int32_t kernel) {
+  ACF_CHECK(k >= 1 && k <= TOPK_MAX_K, ACF_E_INVALID, "k must be in [1, %d], got %d", TOPK_MAX_K, k);
+  ACF_CHECK(kernel >= 0 && kernel <= 2, ACF_E_INVALID, "kernel must be 0 (auto), 1 (MFMA) or 2 (VALU), got %d",
+            kernel);
+  ACF_CHECK(n_users >= 0 && num_cand >= 0, ACF_E_INVALID, "negative size");
+  return ACF_OK;
+}
+
+extern "C" int acf_recommend_topk_workspace(int32_t n_users, int32_t num_cand, int32_t k, int32_t kernel,
+                                            size_t* bytes) {
+  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
+  ACF_RET(topk_check(n_users, num_cand, k, kernel));
+  int wper = 0, S = 0;
+  topk_strips(n_users, num_cand, k, topk_kernel(n_users, num_cand, kernel), &wper, &S);
+  *bytes = (size_t)std::max(n_users, 1) * S * k * sizeof(uint64_t);
+  return ACF_OK;
+}
+
+// the sweeps' dynamic LDS (MFMA: up to 96 KB of keys; VALU: 32 KB of keys + 8 rows) is above the 64 KB default
+// (set per call: the attribute belongs to the current device's copy of the kernel)
+static int topk_lds_optin(int kernel) {
+  if (kernel == 1)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_topk_mfma),
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(EVM_U * TKM_CAP_MAX * sizeof(uint64_t))));
+  else
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_topk_valu),
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(TKV_UB * TKV_CAP * sizeof(uint64_t) + TKV_UB * 1024 * sizeof(float))));
+  return ACF_OK;
+}
+
+extern "C" int acf_recommend_topk(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
+                                  const int32_t* users, int32_t n_users, int32_t num_cand,
+                                  const int64_t* excl_off, const int32_t* excl, int32_t k, int32_t* out_items,
+                                  float* out_scores, void* workspace, size_t workspace_bytes, int32_t kernel,
+                                  void* stream_) {
+  ACF_RET(check_dim(d));
+  ACF_RET(topk_check(n_users, num_cand, k, kernel));
+  ACF_CHECK(P && Q && users && excl_off && excl && out_items && out_scores && workspace, ACF_E_INVALID,
+            "NULL argument");
+  ACF_CHECK(num_cand <= I1, ACF_E_INVALID, "num_candidates %d > item rows", num_cand);
+  ACF_CHECK(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, ACF_E_INVALID, "workspace must be 8-byte aligned");
+  kernel = topk_kernel(n_users, num_cand, kernel);
+  int wper = 0, S = 0;
+  topk_strips(n_users, num_cand, k, kernel, &wper, &S);
+  const size_t need = (size_t)std::max(n_users, 1) * S * k * sizeof(uint64_t);
+  ACF_CHECK(workspace_bytes >= need, ACF_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+  if (n_users == 0) return ACF_OK;
+  ACF_RET(topk_lds_optin(kernel));
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  uint64_t* ws = static_cast<uint64_t*>(workspace);
+  if (kernel == 2) {
+    const size_t lds = (size_t)TKV_UB * TKV_CAP * sizeof(uint64_t) + (size_t)TKV_UB * d * sizeof(float);
+    const dim3 grid((unsigned)((n_users + TKV_UB - 1) / TKV_UB), (unsigned)S);
+    k_topk_valu<<<grid, 256, lds, s>>>(P, Q, d, users, n_users, num_cand, excl_off, excl, k, wper, S, ws);
+  } else {
+    const float eb = 4.0f * (float)(d + 2) * 5.9604645e-8f;  // as k_eval_fused: 4 (d + 2) 2^-24
+    const float floor_e = (float)d * 1.1754944e-38f * 4.0f;   // denormal products flushed by MFMA
+    const int cap = topk_mfma_cap(k);
+    const dim3 grid((unsigned)((n_users + EVM_U - 1) / EVM_U), (unsigned)S);
+    k_topk_mfma<<<grid, 256, (size_t)EVM_U * cap * sizeof(uint64_t), s>>>(P, Q, d, users, n_users, num_cand,
+                                                                         excl_off, excl, eb, floor_e, k, cap, wper,
+                                                                         S, ws);
+  }
+  HIP_TRY(hipGetLastError());
+  k_topk_merge<<<(unsigned)n_users, 256, 0, s>>>(ws, S, k, out_items, out_scores);
+  HIP_TRY(hipGetLastError());
+  return ACF_OK;
 }
 
 extern "C" int acf_eval_positions_list(const float* P, const float* Q, int64_t U1, int64_t I1,

@@ -14,6 +14,7 @@
 //   acf::sparse_adagrad_apply  SparseApplyAdagrad (APR.py:193-195)
 //   acf::score_rank            _eval_by_user positions over candidate lists (utils.py:244-254)
 //   acf::score_rank_all        the same over all items minus exclusions (utils.py:211-254)
+//   acf::recommend_topk        the k best items per user and their scores (no reference counterpart)
 #include <torch/library.h>
 #include <ATen/ATen.h>
 // ROCm builds of PyTorch keep the "cuda" device type: the guard and stream
@@ -324,6 +325,39 @@ at::Tensor score_rank_all(const at::Tensor& P, const at::Tensor& Q, const at::Te
   return pos;
 }
 
+// the k best candidates per user and their scores (acf_recommend_topk, kernel auto).  An
+// exclusion list is a set and may hold entries outside [0, num_candidates), which
+// are ignored: unlike score_rank_all's, its entries are not range-checked.
+std::tuple<at::Tensor, at::Tensor> recommend_topk(const at::Tensor& P, const at::Tensor& Q, const at::Tensor& users_,
+                                                  int64_t k, int64_t num_candidates, const at::Tensor& excl_off,
+                                                  const at::Tensor& excl_items_) {
+  need_table(P, "embedding_P", P);
+  need_table(Q, "embedding_Q", P);
+  TORCH_CHECK(P.size(1) == Q.size(1), "embedding_P and embedding_Q dims differ");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(P.device());
+  at::Tensor users = idx32(users_, "users", P);
+  at::Tensor excl = idx32(excl_items_, "excl_items", P);
+  need(excl_off, "excl_off", at::kLong, 1);
+  TORCH_CHECK(excl_off.device() == P.device(), "excl_off must live on ", P.device());
+  TORCH_CHECK(excl_off.numel() == users.numel() + 1, "excl_off must have len(users) + 1 entries");
+  TORCH_CHECK(k >= 1 && k <= 128, "k must be in [1, 128], got ", k);
+  TORCH_CHECK(num_candidates >= 0 && num_candidates <= Q.size(0), "num_candidates exceeds item rows");
+  check_range(users, P.size(0), "users");
+  if (excl.numel() == 0) excl = at::zeros({1}, users.options());
+  const int32_t n = (int32_t)users.numel();
+  size_t ws = 0;
+  ok(acf_recommend_topk_workspace(n, (int32_t)num_candidates, (int32_t)k, 0, &ws), "acf_recommend_topk_workspace");
+  at::Tensor work = at::empty({(int64_t)((ws + 7) / 8)}, users.options().dtype(at::kLong));
+  at::Tensor items = at::empty({n, k}, users.options());
+  at::Tensor scores = at::empty({n, k}, P.options());
+  ok(acf_recommend_topk(P.data_ptr<float>(), Q.data_ptr<float>(), P.size(0), Q.size(0), (int32_t)P.size(1),
+                        users.data_ptr<int32_t>(), n, (int32_t)num_candidates, excl_off.data_ptr<int64_t>(),
+                        excl.data_ptr<int32_t>(), (int32_t)k, items.data_ptr<int32_t>(), scores.data_ptr<float>(),
+                        work.data_ptr(), ws, 0, stream_of(P)),
+     "acf_recommend_topk");
+  return {items, scores};
+}
+
 }  // namespace
 
 #ifndef ACF_BUILD_HASH
@@ -350,6 +384,8 @@ TORCH_LIBRARY(acf, m) {
   m.def("release_contexts() -> int", &release_contexts);
   m.def("score_rank_all(Tensor P, Tensor Q, Tensor users, Tensor test_items, int num_candidates, "
         "Tensor excl_off, Tensor excl_items) -> Tensor");
+  m.def("recommend_topk(Tensor P, Tensor Q, Tensor users, int k, int num_candidates, Tensor excl_off, "
+        "Tensor excl_items) -> (Tensor items, Tensor scores)");
 }
 
 TORCH_LIBRARY_IMPL(acf, CUDA, m) {
@@ -361,4 +397,5 @@ TORCH_LIBRARY_IMPL(acf, CUDA, m) {
   m.impl("sparse_adagrad_apply", &sparse_adagrad_apply);
   m.impl("score_rank", &score_rank);
   m.impl("score_rank_all", &score_rank_all);
+  m.impl("recommend_topk", &recommend_topk);
 }

@@ -104,6 +104,50 @@ def positions(P, Q, plan: EvalPlan, kernel: str = "auto"):
     return ops.eval_positions_list(P, Q, u, t, o, c)
 
 
+def train_exclusions(dataset, users):
+    """Exclusion CSR (offsets int64 [n + 1], items int32) for recommendation
+    lists: the sorted unique trainList[u] of every user in `users`, in that order
+    (repeats allowed).  Train items only: the held-out test item stays
+    recommendable.  A user without a train list gets an empty one.  Pure numpy."""
+    soff, sitems = dataset.sorted_lists()
+    users = np.asarray(users, dtype=np.int64).reshape(-1)
+    soff = np.append(np.asarray(soff, dtype=np.int64), soff[-1])  # one empty list past the end
+    known = (users >= 0) & (users < len(soff) - 2)
+    safe = np.where(known, users, len(soff) - 2)  # users without a trainList: the empty one
+    lens = soff[safe + 1] - soff[safe]
+    off = np.zeros(len(users) + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    within = np.arange(off[-1], dtype=np.int64) - np.repeat(off[:-1], lens)
+    items = np.asarray(sitems)[np.repeat(soff[safe], lens) + within].astype(np.int32)
+    return off, items
+
+
+def recommend(model_or_tables, dataset=None, users=None, k: int = 10, exclude_train: bool = True,
+              kernel: str = "auto"):
+    """The k best items per user from the model's tables, on the GPU
+    (ops.recommend_topk): (items int32 [n, k], scores float32 [n, k]) as numpy
+    arrays, -1 / -inf past a user's candidates.  model_or_tables: an MF (or
+    anything with embedding_P / embedding_Q) or a (P, Q) pair of device tensors.
+    users: default every user of the dataset.  Candidates are the dataset's items
+    [0, num_items) (no dataset: every row of Q), minus the user's train items when
+    exclude_train."""
+    if hasattr(model_or_tables, "embedding_P"):
+        P, Q = model_or_tables.embedding_P, model_or_tables.embedding_Q
+    else:
+        P, Q = model_or_tables[0], model_or_tables[1]
+    if users is None:
+        if dataset is None:
+            raise ValueError("users=None needs a dataset")
+        users = np.arange(dataset.num_users, dtype=np.int64)
+    users = np.asarray(users, dtype=np.int64).reshape(-1)
+    num_candidates = min(int(dataset.num_items), Q.shape[0]) if dataset is not None else Q.shape[0]
+    off = ex = None
+    if exclude_train and dataset is not None:
+        off, ex = train_exclusions(dataset, users)
+    items, scores = ops.recommend_topk(P, Q, users.astype(np.int32), int(k), num_candidates, off, ex, kernel=kernel)
+    return items.cpu().numpy(), scores.cpu().numpy()
+
+
 def metrics_from_positions(pos, n_neg, K):
     """utils.py:256-261 for k = 1..K -> raw [U, 3, K] array of (hr, ndcg, auc)."""
     pos = np.asarray(pos, dtype=np.int64)

@@ -193,6 +193,14 @@ class MF:
         _, _, op, _ = ops.bpr_forward(self.embedding_P, self.embedding_Q, u, i, i, n, want_scores=True)
         return op.cpu().numpy().reshape(-1, 1)
 
+    def recommend(self, users, k, dataset=None):
+        """The k best items of each user: (items [n, k] int32, scores [n, k]
+        float32) numpy arrays, best first, -1 / -inf past a user's candidates.
+        With a dataset the candidates are its items minus the user's train items
+        (evaluate.recommend); without one, every item row."""
+        from .evaluate import recommend
+        return recommend(self, dataset, users=users, k=k)
+
 
 class Session:
     """Minimal ``tf.Session`` stand-in for the fetches the APR path uses."""

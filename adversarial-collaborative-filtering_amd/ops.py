@@ -675,6 +675,73 @@ def eval_positions_all(P, Q, users, test_items, num_candidates: int, excl_off, e
     return pos
 
 
+TOPK_MAX_K = 128
+
+
+def recommend_topk_workspace(n_users: int, num_candidates: int, k: int, kernel: str = "auto") -> int:
+    """Bytes of device workspace acf_recommend_topk needs (a host-only query)."""
+    if kernel not in EVAL_KERNELS:
+        raise ValueError(f"kernel must be one of {sorted(EVAL_KERNELS)}, got {kernel!r}")
+    if not 1 <= int(k) <= TOPK_MAX_K:
+        raise ValueError(f"k must be in [1, {TOPK_MAX_K}], got {k}")
+    size = ctypes.c_size_t()
+    call("acf_recommend_topk_workspace", int(n_users), int(num_candidates), int(k), EVAL_KERNELS[kernel],
+         ctypes.byref(size))
+    return int(size.value)
+
+
+def recommend_topk(P, Q, users, k: int, num_candidates: int | None = None, excl_off=None, excl_items=None,
+                   kernel: str = "auto"):
+    """The k best items per user: (items int32 [n, k], scores float32 [n, k]).
+    Candidates of users[j] are [0, num_candidates) (default: every row of Q) minus
+    the set of excl_items[excl_off[j]:excl_off[j+1]] (unsorted, repeated and
+    out-of-range entries are fine; no exclusion arguments: nothing is excluded).
+    Scores are the evaluation's sequential dot product bit for bit, ordered by
+    score descending, ties to the lower item id; a user with fewer than k
+    candidates gets -1 / -inf in the tail.  kernel: 'auto' | 'mfma' | 'valu'
+    (identical outputs).  No [n, num_candidates] score array is formed."""
+    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f"k must be an int in [1, {TOPK_MAX_K}], got {k!r}")
+    if kernel not in EVAL_KERNELS:
+        raise ValueError(f"kernel must be one of {sorted(EVAL_KERNELS)}, got {kernel!r}")
+    _require(P, "embedding_P", torch.float32, None, 2)
+    dev = P.device
+    _require(Q, "embedding_Q", torch.float32, dev, 2)
+    if P.shape[1] != Q.shape[1]:
+        raise ValueError("embedding_P and embedding_Q dims differ")
+    settle_tables()
+    u = _idx(users, "users", dev)
+    n = u.numel()
+    if num_candidates is None:
+        num_candidates = Q.shape[0]
+    num_candidates = int(num_candidates)
+    if not 0 <= num_candidates <= Q.shape[0]:
+        raise ValueError("num_candidates must lie in [0, item rows]")
+    if (excl_off is None) != (excl_items is None):
+        raise ValueError("excl_off and excl_items go together")
+    if excl_off is None:
+        off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        ex = torch.zeros(1, dtype=torch.int32, device=dev)
+    else:
+        off = torch.as_tensor(excl_off).to(device=dev, dtype=torch.int64).contiguous()
+        ex = (_idx(excl_items, "excl_items", dev) if len(excl_items)
+              else torch.zeros(1, dtype=torch.int32, device=dev))
+        if off.numel() != n + 1:
+            raise ValueError("excl_off must have len(users) + 1 entries")
+    _check_range(u, P.shape[0], "user")
+    items = torch.empty((n, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+    if n == 0:
+        return items, scores
+    nbytes = recommend_topk_workspace(n, num_candidates, k, kernel)
+    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    with _on(dev):
+        call("acf_recommend_topk", P.data_ptr(), Q.data_ptr(), P.shape[0], Q.shape[0], P.shape[1], u.data_ptr(),
+             n, num_candidates, off.data_ptr(), ex.data_ptr(), k, items.data_ptr(), scores.data_ptr(),
+             work.data_ptr(), nbytes, EVAL_KERNELS[kernel], _stream_ptr(dev))
+    return items, scores
+
+
 def eval_positions_list(P, Q, users, test_items, cand_off, cand_items):
     """_eval_by_user positions over explicit candidate lists ("sample" mode)."""
     settle_tables()

@@ -126,3 +126,24 @@ class APR(Recommender):
     def rank(self, users, items):
         self._ensure()
         return self.model.scores(np.asarray(users).reshape(-1), np.asarray(items).reshape(-1))
+
+    def recommend(self, users, k, train=None):
+        """The k best items of each user among [0, iNum): (items [n, k] int32,
+        scores [n, k] float32) numpy arrays, best first, -1 / -inf past a user's
+        candidates.  train: the dok/CSR matrix of get_train_instances; its pairs
+        are never recommended."""
+        self._ensure()
+        m = self.model
+        users = np.asarray(users, dtype=np.int64).reshape(-1)
+        off = ex = None
+        if train is not None:
+            csr = train.tocsr()
+            lens = np.where(users < csr.shape[0], np.diff(csr.indptr)[np.minimum(users, csr.shape[0] - 1)], 0)
+            off = np.zeros(len(users) + 1, dtype=np.int64)
+            np.cumsum(lens, out=off[1:])
+            start = np.repeat(csr.indptr[np.minimum(users, csr.shape[0] - 1)].astype(np.int64), lens)
+            within = np.arange(off[-1], dtype=np.int64) - np.repeat(off[:-1], lens)
+            ex = csr.indices[start + within].astype(np.int32)
+        items, scores = ops.recommend_topk(m.embedding_P, m.embedding_Q, users.astype(np.int32), int(k), self.iNum,
+                                           off, ex)
+        return items.cpu().numpy(), scores.cpu().numpy()

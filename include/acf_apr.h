@@ -349,6 +349,32 @@ int acf_eval_positions_all_kernel(const float* P, const float* Q, int64_t num_us
                                   const int32_t* excl_items, int32_t* positions, int32_t kernel,
                                   void* stream);
 
+/* ---- recommendation lists: the K best items per user ----------------------
+ * (no reference counterpart: the reference only ranks a held-out item.)
+ * For user k (row users[k] of P; any order, repeats allowed) the candidates are
+ * [0, num_candidates) minus the SET of excl_items[excl_off[k] .. excl_off[k+1]):
+ * a list may be unsorted, repeat items and hold entries outside the range (-1
+ * included), which are ignored.  score(u,c) is the sequential round-then-add
+ * dot product the evaluation uses, bit for bit; the order is score descending by
+ * float comparison, ties to the ascending item id.  out_items / out_scores
+ * [n_users, k] receive the first k candidates in that order and their scores;
+ * a user with fewer than k candidates gets -1 / -inf in the tail.  Exact and
+ * deterministic: identical bits run to run and for every kernel (0 = auto,
+ * 1 = the MFMA sweep filtering for an exact rescoring, 2 = the VALU sweep).
+ * 1 <= k <= 128.  No [n_users, num_candidates] array is formed: the caller
+ * provides `workspace` (device memory, 8-byte aligned) of at least the size
+ * acf_recommend_topk_workspace reports for the same (n_users, num_candidates,
+ * k, kernel) -- a host-only query; a smaller one is ACF_E_INVALID.  User
+ * indices must lie in [0, num_user_rows) (not checked here).  Tables are
+ * assumed finite: with a NaN score the order is unspecified. */
+int acf_recommend_topk_workspace(int32_t n_users, int32_t num_candidates, int32_t k, int32_t kernel,
+                                 size_t* bytes);
+int acf_recommend_topk(const float* P, const float* Q, int64_t num_user_rows, int64_t num_item_rows,
+                       int32_t dim, const int32_t* users, int32_t n_users, int32_t num_candidates,
+                       const int64_t* excl_off, const int32_t* excl_items, int32_t k,
+                       int32_t* out_items, float* out_scores, void* workspace, size_t workspace_bytes,
+                       int32_t kernel, void* stream);
+
 /* ---- sampler: shuffle/_get_train_batch (APR.py:39-81) --------------------
  * Shuffles the n_pos positive pairs with a counter-based permutation of
  * `seed`, keeps floor(n_pos / batch_size) * batch_size of them (drop-last,
