@@ -16,14 +16,14 @@ import sys as _sys
 from . import _native  # noqa: F401
 from .data import (DeviceDataset, OriginalDataset, SyntheticDataset, get_dataset, ml1m_like, pinterest_like,
                    synthetic_dataset, synthetic_large, yelp_like)
-from .evaluate import evaluate, init_eval_model
+from .evaluate import evaluate, init_eval_model, robustness
 from .evaluation import evaluate_apr_mode, evaluate_model
 from .model import MF, Session
 from .neumf import AdversarialNeuMF, NeuMF
 from .fast_adversarial_mf import FastAdversarialMF
 from .recommender import APR, Recommender
 from .sampler import DeviceSampler, EpochTriplets, sampling, shuffle
-from .train import (output_evaluate, prediction2file, training, training_batch, training_loss_acc,
+from .train import (adv_update, output_evaluate, prediction2file, training, training_batch, training_loss_acc,
                     write2file)
 
 _sys.modules.setdefault("acf_amd", _sys.modules[__name__])
@@ -32,5 +32,5 @@ __all__ = [
     "APR", "AdversarialNeuMF", "DeviceDataset", "FastAdversarialMF", "DeviceSampler", "EpochTriplets", "MF", "NeuMF", "OriginalDataset", "Recommender", "Session",
     "SyntheticDataset", "evaluate", "evaluate_apr_mode", "evaluate_model", "get_dataset", "init_eval_model", "ml1m_like", "output_evaluate",
     "pinterest_like", "prediction2file", "sampling", "shuffle", "synthetic_dataset", "synthetic_large", "training",
-    "training_batch", "training_loss_acc", "write2file", "yelp_like",
+    "training_batch", "training_loss_acc", "write2file", "yelp_like", "adv_update", "robustness",
 ]

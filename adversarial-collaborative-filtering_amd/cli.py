@@ -63,7 +63,49 @@ def parse_args(argv=None, flavor="ori"):
     p.add_argument("--topk", type=int, default=0,
                    help="After training, write each user's K best items (train items excluded) to "
                         "<out>/<runName>.topk (0: off).")
+    p.add_argument("--robust_eps", type=parse_eps_list, default=[],
+                   help="After training, evaluate under perturbed tables at these eps (comma separated, e.g. "
+                        "\"0.5,1,2\"), gradient and random directions over the last epoch's triplets, and write "
+                        "<out>/<runName>.robust (empty: off).")
     return p.parse_args(argv)
+
+
+def parse_eps_list(text):
+    """"0.5,1,2" -> [0.5, 1.0, 2.0]; empty -> [] (off); a negative or non-numeric value is an error."""
+    out = []
+    for tok in str(text).split(","):
+        tok = tok.strip()
+        if not tok:
+            continue
+        try:
+            v = float(tok)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"not a number: {tok!r}")
+        if not v >= 0 or v == float("inf"):
+            raise argparse.ArgumentTypeError(f"eps must be finite and >= 0, got {tok!r}")
+        out.append(v)
+    return out
+
+
+def write_robust(path, name, rows):
+    """One line "mode<TAB>eps<TAB>hr<TAB>ndcg<TAB>auc" per row of evaluate.robustness
+    (floats by repr: the reader gets the same values back)."""
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, name), "w") as f:
+        for mode, eps, hr, ndcg, auc in rows:
+            f.write("%s\t%r\t%r\t%r\t%r\n" % (mode, float(eps), float(hr), float(ndcg), float(auc)))
+
+
+def read_robust(file):
+    """The rows [(mode, eps, hr, ndcg, auc)] write_robust wrote."""
+    rows = []
+    with open(file) as f:
+        for n, line in enumerate(f):
+            parts = line.rstrip("\n").split("\t")
+            if len(parts) != 5:
+                raise ValueError(f"{file}: line {n} has {len(parts)} fields, expected 5")
+            rows.append((parts[0], *[float(x) for x in parts[1:]]))
+    return rows
 
 
 def write_topk(path, name, items):
@@ -142,4 +184,14 @@ def main(argv=None, flavor="ori"):
         final = amf if args.model == "apr" else m
         items, _ = recommend(final, dataset, k=args.topk)
         write_topk(out, runName + ".topk", items)
+    if args.robust_eps:
+        from .evaluate import init_eval_model, robustness
+        final = amf if args.model == "apr" else m
+        trip = getattr(final, "last_train_batches", None)
+        if trip is None:
+            print("--robust_eps: no epoch was trained, nothing to evaluate on", file=sys.stderr)
+        else:
+            rows = robustness(final, dataset, init_eval_model(dataset, args), trip, args.robust_eps,
+                              seed=args.seed)
+            write_robust(out, runName + ".robust", rows)
     return 0

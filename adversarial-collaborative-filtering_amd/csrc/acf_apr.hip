@@ -3578,6 +3578,7 @@ __global__ void __launch_bounds__(256) k_forward(const float* __restrict__ P,
 
 #include "acf_eval.h"  // all-items evaluation (k_eval_*): DESIGN.md §4
 #include "acf_topk.h"  // top-K recommendation lists (k_topk_*): DESIGN.md §4b
+#include "acf_adv.h"   // whole-stream adversarial direction (k_adv_*): DESIGN.md §4c
 
 // ---------------------------------------------------------------------------
 // sampler (shuffle / _get_train_batch, APR.py:39-81)
@@ -5705,6 +5706,112 @@ extern "C" int acf_recommend_topk(const float* P, const float* Q, int64_t U1, in
   }
   HIP_TRY(hipGetLastError());
   k_topk_merge<<<(unsigned)n_users, 256, 0, s>>>(ws, S, k, out_items, out_scores);
+  HIP_TRY(hipGetLastError());
+  return ACF_OK;
+}
+
+// ---- whole-stream adversarial direction (acf_adv.h) -------------------------
+static int adv_check(int64_t n, int64_t U1, int64_t I1, int32_t d) {
+  ACF_RET(check_dim(d));
+  ACF_CHECK(U1 > 0 && I1 > 0, ACF_E_INVALID, "empty table");
+  ACF_CHECK(U1 + I1 < ((int64_t)1 << 31), ACF_E_INVALID, "more than 2^31 - 1 table rows");
+  ACF_CHECK(n >= 0 && n < ((int64_t)1 << 29), ACF_E_INVALID, "n must lie in [0, 2^29), got %lld", (long long)n);
+  return ACF_OK;
+}
+
+extern "C" int acf_adv_direction_workspace(int64_t n, int64_t U1, int64_t I1, int32_t d, size_t* bytes) {
+  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
+  ACF_RET(adv_check(n, U1, I1, d));
+  *bytes = adv_layout(n, U1, I1, d).total;
+  return ACF_OK;
+}
+
+template <int LPR, int NV>
+static void launch_adv_random(uint64_t seed, uint32_t call, int32_t t, int d, int64_t U1, int64_t R, float* nP,
+                              float* nQ, hipStream_t s) {
+  k_adv_random<LPR, NV><<<grid_for(R * LPR), 256, 0, s>>>(seed, call, t, d, U1, R, nP, nQ);
+}
+
+template <int LPR, int NV>
+static void launch_adv_sum(const float* P, const float* Q, int d, int64_t U1, int64_t R, const int32_t* off,
+                           const int2* rec, float* part, float* nP, float* nQ, int64_t units, hipStream_t s) {
+  k_adv_chunks<LPR, NV><<<grid_for(units * LPR), 256, 0, s>>>(P, Q, d, U1, R, off, rec, part, nP, nQ, units);
+  k_adv_combine<LPR, NV><<<grid_for(R * LPR), 256, 0, s>>>(d, U1, R, off, part, nP, nQ);
+}
+
+extern "C" int acf_adv_direction(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
+                                 const int32_t* user, const int32_t* ipos, const int32_t* ineg, int64_t n,
+                                 float clip_lo, float clip_hi, int32_t adv_mode, uint64_t seed, uint32_t call,
+                                 int32_t t, float* nP, float* nQ, void* workspace, size_t workspace_bytes,
+                                 int32_t check, void* stream_) {
+  ACF_RET(adv_check(n, U1, I1, d));
+  ACF_CHECK(adv_mode == 0 || adv_mode == 1, ACF_E_INVALID, "adv_mode must be 0 (grad) or 1 (random), got %d",
+            adv_mode);
+  ACF_CHECK(P && Q && nP && nQ, ACF_E_INVALID, "NULL argument");
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  const int64_t R = U1 + I1;
+  if (adv_mode == 1) {  // the triplets are not read
+    ACF_RET(DISPATCH_GEOM(d, launch_adv_random, seed, call, t, d, U1, R, nP, nQ, s));
+    HIP_TRY(hipGetLastError());
+    return ACF_OK;
+  }
+  if (n == 0) {
+    HIP_TRY(hipMemsetAsync(nP, 0, (size_t)U1 * d * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(nQ, 0, (size_t)I1 * d * sizeof(float), s));
+    return ACF_OK;
+  }
+  ACF_CHECK(user && ipos && ineg && workspace, ACF_E_INVALID, "NULL argument");
+  ACF_CHECK(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, ACF_E_INVALID, "workspace must be 16-byte aligned");
+  const AdvLayout L = adv_layout(n, U1, I1, d);
+  ACF_CHECK(workspace_bytes >= L.total, ACF_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes,
+            L.total);
+  char* ws = static_cast<char*>(workspace);
+  float* coef = reinterpret_cast<float*>(ws + L.coef);
+  uint32_t* kb[2] = {reinterpret_cast<uint32_t*>(ws + L.k0), reinterpret_cast<uint32_t*>(ws + L.k1)};
+  uint32_t* vb[2] = {reinterpret_cast<uint32_t*>(ws + L.v0), reinterpret_cast<uint32_t*>(ws + L.v1)};
+  uint32_t* counts = reinterpret_cast<uint32_t*>(ws + L.counts);
+  uint32_t* tsum = reinterpret_cast<uint32_t*>(ws + L.tsum);
+  int32_t* off = reinterpret_cast<int32_t*>(ws + L.off);
+  float* part = reinterpret_cast<float*>(ws + L.part);
+  int32_t* err = reinterpret_cast<int32_t*>(ws + L.err);
+  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+  k_adv_stage<<<grid_for(n), 256, 0, s>>>(P, Q, d, user, ipos, ineg, n, U1, I1, clip_lo, clip_hi, coef, kb[0], vb[0],
+                                           err);
+  HIP_TRY(hipGetLastError());
+  if (check) {  // before anything is built on the indices
+    int32_t herr = 0;
+    HIP_TRY(hipMemcpyAsync(&herr, err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    ACF_CHECK(herr == 0, ACF_E_RANGE, "triplet index out of range (%s%s)",
+              (herr & 1) ? "user >= num_user_rows " : "", (herr & 2) ? "item >= num_item_rows" : "");
+  }
+  int cur = 0;
+  for (int p = 0; p < L.passes; ++p, cur ^= 1) {
+    k_adv_hist<<<(unsigned)L.ntiles, ADV_SORT_BS, 0, s>>>(kb[cur], L.N, 8 * p, L.ntiles, counts);
+    k_adv_scan1<<<(unsigned)L.T, 256, 0, s>>>(counts, L.M, tsum);
+    k_adv_scan2<<<1, 1024, 0, s>>>(tsum, L.T);
+    k_adv_scan3<<<(unsigned)L.T, 256, 0, s>>>(counts, L.M, tsum);
+    k_adv_reorder<<<(unsigned)L.ntiles, ADV_SORT_BS, 0, s>>>(kb[cur], vb[cur], kb[cur ^ 1], vb[cur ^ 1], L.N, 8 * p,
+                                                            L.ntiles, counts);
+    HIP_TRY(hipGetLastError());
+  }
+  int2* rec = reinterpret_cast<int2*>(kb[cur ^ 1]);  // the free (keys, values) pair: N * 8 bytes
+  k_adv_offsets<<<grid_for(R + 1), 256, 0, s>>>(kb[cur], L.N, R, off);
+  k_adv_records<<<grid_for(L.N), 256, 0, s>>>(vb[cur], L.N, n, user, ipos, ineg, U1, I1, coef, rec);
+  HIP_TRY(hipGetLastError());
+  const int64_t units = L.N / ADV_CHUNK + R + 1;
+  ACF_RET(DISPATCH_GEOM(d, launch_adv_sum, P, Q, d, U1, R, off, rec, part, nP, nQ, units, s));
+  HIP_TRY(hipGetLastError());
+  return ACF_OK;
+}
+
+extern "C" int acf_adv_apply(const float* W, const float* N, int64_t rows, int32_t d, float eps, float* delta_out,
+                             float* sum_out, void* stream_) {
+  ACF_CHECK(rows >= 0 && d > 0, ACF_E_INVALID, "negative size");
+  ACF_CHECK(N && (W || !sum_out), ACF_E_INVALID, "NULL argument");
+  const int64_t count = rows * (int64_t)d;
+  if (count == 0 || (!delta_out && !sum_out)) return ACF_OK;
+  k_adv_apply<<<grid_for(count), 256, 0, static_cast<hipStream_t>(stream_)>>>(W, N, count, eps, delta_out, sum_out);
   HIP_TRY(hipGetLastError());
   return ACF_OK;
 }

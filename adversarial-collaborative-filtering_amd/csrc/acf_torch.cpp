@@ -15,6 +15,8 @@
 //   acf::score_rank            _eval_by_user positions over candidate lists (utils.py:244-254)
 //   acf::score_rank_all        the same over all items minus exclusions (utils.py:211-254)
 //   acf::recommend_topk        the k best items per user and their scores (no reference counterpart)
+//   acf::adv_direction         adv_update's direction over a whole triplet stream (utils.py:145-154)
+//   acf::adv_apply             delta = N * eps and W + delta (APR.py:130-141,190)
 #include <torch/library.h>
 #include <ATen/ATen.h>
 // ROCm builds of PyTorch keep the "cuda" device type: the guard and stream
@@ -358,6 +360,49 @@ std::tuple<at::Tensor, at::Tensor> recommend_topk(const at::Tensor& P, const at:
   return {items, scores};
 }
 
+// unit-direction tables (nP, nQ) over all the triplets as one batch (acf_adv_direction,
+// indices range-checked by the call); adv: "grad" or "random"
+std::tuple<at::Tensor, at::Tensor> adv_direction(const at::Tensor& P, const at::Tensor& Q, const at::Tensor& user_,
+                                                 const at::Tensor& item_pos_, const at::Tensor& item_neg_,
+                                                 c10::string_view adv, int64_t seed, int64_t call, int64_t t,
+                                                 double clip_lo, double clip_hi) {
+  need_table(P, "embedding_P", P);
+  need_table(Q, "embedding_Q", P);
+  TORCH_CHECK(P.size(1) == Q.size(1), "embedding_P and embedding_Q dims differ");
+  TORCH_CHECK(adv == "grad" || adv == "random", "adv must be 'grad' or 'random'");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(P.device());
+  at::Tensor u = idx32(user_, "user", P), i = idx32(item_pos_, "item_pos", P), j = idx32(item_neg_, "item_neg", P);
+  const int64_t n = u.numel();
+  TORCH_CHECK(i.numel() == n && j.numel() == n, "user, item_pos and item_neg must have equal lengths");
+  const int32_t mode = adv == "grad" ? 0 : 1;
+  size_t ws = 0;
+  if (mode == 0 && n > 0)
+    ok(acf_adv_direction_workspace(n, P.size(0), Q.size(0), (int32_t)P.size(1), &ws), "acf_adv_direction_workspace");
+  at::Tensor work = at::empty({(int64_t)((ws + 7) / 8)}, u.options().dtype(at::kLong));
+  at::Tensor nP = at::empty_like(P), nQ = at::empty_like(Q);
+  ok(acf_adv_direction(P.data_ptr<float>(), Q.data_ptr<float>(), P.size(0), Q.size(0), (int32_t)P.size(1),
+                       n ? u.data_ptr<int32_t>() : nullptr, n ? i.data_ptr<int32_t>() : nullptr,
+                       n ? j.data_ptr<int32_t>() : nullptr, n, (float)clip_lo, (float)clip_hi, mode, (uint64_t)seed,
+                       (uint32_t)call, (int32_t)t, nP.data_ptr<float>(), nQ.data_ptr<float>(),
+                       ws ? work.data_ptr() : nullptr, ws, 1, stream_of(P)),
+     "acf_adv_direction");
+  return {nP, nQ};
+}
+
+// (W + N * eps, N * eps): two separately rounded fp32 operations (acf_adv_apply)
+std::tuple<at::Tensor, at::Tensor> adv_apply(const at::Tensor& W, const at::Tensor& N, double eps) {
+  need(W, "W", at::kFloat, 2);
+  need(N, "N", at::kFloat, 2);
+  TORCH_CHECK(N.device() == W.device(), "N is on ", N.device(), ", expected ", W.device());
+  TORCH_CHECK(W.sizes() == N.sizes(), "W and N differ in shape");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(W.device());
+  at::Tensor sum = at::empty_like(W), delta = at::empty_like(W);
+  ok(acf_adv_apply(W.data_ptr<float>(), N.data_ptr<float>(), W.size(0), (int32_t)W.size(1), (float)eps,
+                   delta.data_ptr<float>(), sum.data_ptr<float>(), stream_of(W)),
+     "acf_adv_apply");
+  return {sum, delta};
+}
+
 }  // namespace
 
 #ifndef ACF_BUILD_HASH
@@ -386,6 +431,9 @@ TORCH_LIBRARY(acf, m) {
         "Tensor excl_off, Tensor excl_items) -> Tensor");
   m.def("recommend_topk(Tensor P, Tensor Q, Tensor users, int k, int num_candidates, Tensor excl_off, "
         "Tensor excl_items) -> (Tensor items, Tensor scores)");
+  m.def("adv_direction(Tensor P, Tensor Q, Tensor user, Tensor item_pos, Tensor item_neg, str adv=\"grad\", "
+        "int seed=0, int call=1, int t=0, float clip_lo=-80.0, float clip_hi=1e8) -> (Tensor nP, Tensor nQ)");
+  m.def("adv_apply(Tensor W, Tensor N, float eps) -> (Tensor sum, Tensor delta)");
 }
 
 TORCH_LIBRARY_IMPL(acf, CUDA, m) {
@@ -398,4 +446,6 @@ TORCH_LIBRARY_IMPL(acf, CUDA, m) {
   m.impl("score_rank", &score_rank);
   m.impl("score_rank_all", &score_rank_all);
   m.impl("recommend_topk", &recommend_topk);
+  m.impl("adv_direction", &adv_direction);
+  m.impl("adv_apply", &adv_apply);
 }

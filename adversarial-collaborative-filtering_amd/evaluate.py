@@ -160,11 +160,63 @@ def metrics_from_positions(pos, n_neg, K):
 
 
 def evaluate(model, sess, dataset, feed_dicts: EvalPlan, output_adv=0, args=None):
-    """utils.py:221-241: returns ((hr, ndcg, auc) as per-K lists, raw [U,3,K])."""
+    """utils.py:221-241: returns ((hr, ndcg, auc) as per-K lists, raw [U,3,K]).
+    output_adv=1 ranks with model.output_adv, (P + delta_P)[u] . (Q + delta_Q)[i]
+    (APR.py:130-141): delta_P / delta_Q are what the last train.adv_update put
+    there (zeros before any), not the last mini-batch's delta as in TF, because
+    training here never materialises delta."""
+    P, Q = model.embedding_P, model.embedding_Q
     if output_adv:
-        raise NotImplementedError("evaluation of model.output_adv is not on the APR path "
-                                  "(APR.training always passes output_adv=0)")
-    pos = positions(model.embedding_P, model.embedding_Q, feed_dicts).cpu().numpy()
+        P, Q = perturbed_tables(model)
+    pos = positions(P, Q, feed_dicts).cpu().numpy()
     raw = metrics_from_positions(pos, feed_dicts.n_neg, feed_dicts.K)
     hr, ndcg, auc = raw.mean(axis=0).tolist()
     return (hr, ndcg, auc), raw
+
+
+def perturbed_tables(model):
+    """(P + delta_P, Q + delta_Q) of a model, each one rounded fp32 add
+    (ops.adv_apply); the model's own tables are not written."""
+    return (ops.adv_apply(model.embedding_P, model.delta_P, 1.0),
+            ops.adv_apply(model.embedding_Q, model.delta_Q, 1.0))
+
+
+def triplet_arrays(triplets):
+    """(user, item_pos, item_neg) of what training_batch returns: an EpochTriplets
+    (device tensors, passed through) or the lists (user_input, item_input_pos,
+    [user_dns,] item_neg) of per-batch arrays, concatenated to int32 numpy."""
+    if hasattr(triplets, "item_neg"):
+        return triplets.user, triplets.item_pos, triplets.item_neg
+    if len(triplets) not in (3, 4):
+        raise ValueError("triplets must be an EpochTriplets or the lists training_batch returns")
+    u, i, j = triplets[0], triplets[1], triplets[-1]
+    cat = lambda xs: (np.concatenate([np.asarray(x).reshape(-1) for x in xs]).astype(np.int32)  # noqa: E731
+                      if len(xs) else np.zeros(0, np.int32))
+    return cat(u), cat(i), cat(j)
+
+
+def robustness(model, dataset, plan: EvalPlan, triplets, eps_list, modes=("grad", "random"), seed=0):
+    """HR@K, NDCG@K and AUC (K = plan.K) under a perturbation of both tables, per
+    mode and eps: rows (mode, eps, hr, ndcg, auc).  One direction per mode over
+    ALL the triplets as one batch (ops.adv_direction; "random": the draw of
+    (seed, call 1, t 0)), then per eps one ops.adv_apply per table and one
+    positions() on the perturbed tables.  eps = 0 reproduces
+    evaluate(output_adv=0).  The model's tables and delta_P / delta_Q are left
+    as they are."""
+    for mode in modes:
+        if mode not in ops.ADV_MODES:
+            raise ValueError(f"mode must be one of {sorted(ops.ADV_MODES)}, got {mode!r}")
+    eps_list = [float(e) for e in eps_list]
+    if any(e < 0 for e in eps_list):
+        raise ValueError("eps must be >= 0")
+    u, i, j = triplet_arrays(triplets)
+    P, Q = model.embedding_P, model.embedding_Q
+    rows = []
+    for mode in modes:
+        nP, nQ = ops.adv_direction(P, Q, u, i, j, adv=mode, seed=int(seed or 0), call=1, t=0)
+        for eps in eps_list:
+            pos = positions(ops.adv_apply(P, nP, eps), ops.adv_apply(Q, nQ, eps), plan).cpu().numpy()
+            raw = metrics_from_positions(pos, plan.n_neg, plan.K)
+            hr, ndcg, auc = raw.mean(axis=0)[:, -1].tolist() if len(pos) else (0.0, 0.0, 0.0)
+            rows.append((mode, eps, hr, ndcg, auc))
+    return rows

@@ -100,6 +100,10 @@ class MF:
         self._create_placeholders()
         self._create_variables(device, generator)
         self._create_fetches()
+        # delta_P / delta_Q (APR.py:111-116): zeros until train.adv_update assigns them
+        self.delta_P = torch.zeros_like(self.embedding_P)
+        self.delta_Q = torch.zeros_like(self.embedding_Q)
+        self._adv_calls = 0
         self._ctx = None
         self._pipe = None
         self._delta_feed = None
@@ -200,6 +204,17 @@ class MF:
         (evaluate.recommend); without one, every item row."""
         from .evaluate import recommend
         return recommend(self, dataset, users=users, k=k)
+
+    def adv_update(self, train_batches, adv=None):
+        """train.adv_update: delta_P / delta_Q over all the triplets as one batch."""
+        from .train import adv_update
+        return adv_update(self, None, train_batches, adv=adv)
+
+    def robustness(self, dataset, plan, triplets, eps_list, modes=("grad", "random"), seed=0):
+        """evaluate.robustness: rows (mode, eps, hr@K, ndcg@K, auc) under a
+        perturbation of both tables."""
+        from .evaluate import robustness
+        return robustness(self, dataset, plan, triplets, eps_list, modes=modes, seed=seed)
 
 
 class Session:

@@ -742,6 +742,80 @@ def recommend_topk(P, Q, users, k: int, num_candidates: int | None = None, excl_
     return items, scores
 
 
+ADV_MODES = {"grad": 0, "random": 1}
+ADV_MAX_TRIPLETS = (1 << 29) - 1
+
+
+def adv_direction_workspace(n: int, num_user_rows: int, num_item_rows: int, dim: int) -> int:
+    """Bytes of device workspace acf_adv_direction needs for n triplets (a host-only query)."""
+    if not 0 <= int(n) <= ADV_MAX_TRIPLETS:
+        raise ValueError(f"n must lie in [0, {ADV_MAX_TRIPLETS}], got {n}")
+    size = ctypes.c_size_t()
+    call("acf_adv_direction_workspace", int(n), int(num_user_rows), int(num_item_rows), int(dim),
+         ctypes.byref(size))
+    return int(size.value)
+
+
+def adv_direction(P, Q, user, item_pos, item_neg, adv: str = "grad", seed: int = 0, call: int = 1, t: int = 0,
+                  clip_lo=CLIP_LO, clip_hi=CLIP_HI, check: bool = True):
+    """The adversarial direction of the WHOLE triplet stream as one batch
+    (utils.py:145-154): dense unit-direction tables (nP [rows of P, d], nQ [rows of
+    Q, d]); delta = direction * eps is adv_apply's job, so one direction serves
+    every eps.  adv="grad" (APR.py:180-191): the l2-normalised gradient of the
+    clean loss of all triplets; rows no triplet touches are exact zeros; the
+    order in which a row's terms are added is a fixed function of the input
+    order, so equal inputs give equal bits.  adv="random" (APR.py:170-177): every
+    row is the step's l2-normalised truncated-normal draw for (seed, call, t,
+    table, row); the triplets are not read.  P and Q are never written.
+    check: an index outside its table raises NativeIndexError."""
+    if adv not in ADV_MODES:
+        raise ValueError(f"adv must be one of {sorted(ADV_MODES)}, got {adv!r}")
+    n = len(user)
+    if len(item_pos) != n or len(item_neg) != n:
+        raise ValueError("user, item_pos and item_neg must have equal lengths")
+    if n > ADV_MAX_TRIPLETS:
+        raise ValueError(f"at most {ADV_MAX_TRIPLETS} triplets, got {n}")
+    _require(P, "embedding_P", torch.float32, None, 2)
+    dev = P.device
+    _require(Q, "embedding_Q", torch.float32, dev, 2)
+    if P.shape[1] != Q.shape[1]:
+        raise ValueError("embedding_P and embedding_Q dims differ")
+    u, i, j = (_idx(x, nm, dev) for x, nm in ((user, "user"), (item_pos, "item_pos"), (item_neg, "item_neg")))
+    if not (u.numel() == i.numel() == j.numel() == n):
+        raise ValueError("user, item_pos and item_neg must have equal lengths")
+    settle_tables()
+    U1, I1, d = P.shape[0], Q.shape[0], P.shape[1]
+    nP = torch.empty((U1, d), dtype=torch.float32, device=dev)
+    nQ = torch.empty((I1, d), dtype=torch.float32, device=dev)
+    grad = adv == "grad"
+    nbytes = adv_direction_workspace(n, U1, I1, d) if grad and n else 0
+    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev) if nbytes else None
+    with _on(dev):
+        _native.call("acf_adv_direction", P.data_ptr(), Q.data_ptr(), U1, I1, d, u.data_ptr() if n else None,
+                     i.data_ptr() if n else None, j.data_ptr() if n else None, n, clip_lo, clip_hi, ADV_MODES[adv],
+                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF, int(t),
+                     nP.data_ptr(), nQ.data_ptr(), work.data_ptr() if work is not None else None, nbytes,
+                     int(bool(check)), _stream_ptr(dev))
+    return nP, nQ
+
+
+def adv_apply(W, N, eps: float, want_delta: bool = False):
+    """sum = W + delta with delta = N * eps, two separately rounded fp32 operations
+    (TF: l2_normalize(...) * eps, then embedding + delta): the perturbed table, or
+    (sum, delta) with want_delta."""
+    _require(W, "W", torch.float32, None, 2)
+    _require(N, "N", torch.float32, W.device, 2)
+    if W.shape != N.shape:
+        raise ValueError(f"W {tuple(W.shape)} and N {tuple(N.shape)} differ in shape")
+    dev = W.device
+    out = torch.empty_like(W)
+    delta = torch.empty_like(W) if want_delta else None
+    with _on(dev):
+        _native.call("acf_adv_apply", W.data_ptr(), N.data_ptr(), W.shape[0], W.shape[1], float(eps),
+                     delta.data_ptr() if want_delta else None, out.data_ptr(), _stream_ptr(dev))
+    return (out, delta) if want_delta else out
+
+
 def eval_positions_list(P, Q, users, test_items, cand_off, cand_items):
     """_eval_by_user positions over explicit candidate lists ("sample" mode)."""
     settle_tables()

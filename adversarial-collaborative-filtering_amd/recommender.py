@@ -147,3 +147,16 @@ class APR(Recommender):
         items, scores = ops.recommend_topk(m.embedding_P, m.embedding_Q, users.astype(np.int32), int(k), self.iNum,
                                            off, ex)
         return items.cpu().numpy(), scores.cpu().numpy()
+
+    def adv_update(self, x_train, adv=None):
+        """train.adv_update on the triplets of get_train_instances: the model's
+        delta_P / delta_Q over all of them as one batch."""
+        self._ensure()
+        return self.model.adv_update((([x_train[0]], [x_train[1]], [x_train[2]])), adv=adv)
+
+    def robustness(self, dataset, plan, x_train, eps_list, modes=("grad", "random"), seed=0):
+        """evaluate.robustness on the triplets of get_train_instances: rows
+        (mode, eps, hr@K, ndcg@K, auc)."""
+        self._ensure()
+        return self.model.robustness(dataset, plan, ([x_train[0]], [x_train[1]], [x_train[2]]), eps_list,
+                                     modes=modes, seed=seed)

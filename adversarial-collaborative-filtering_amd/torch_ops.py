@@ -15,6 +15,9 @@ SURVEY.md §8(b) proposes:
 - evaluation: ``score_rank`` / ``score_rank_all`` (_eval_by_user, utils.py:211-254);
 - ``recommend_topk(P, Q, users, k, num_candidates, excl_off, excl_items) -> (items, scores)``:
   the k best items per user (exact; ``ops.recommend_topk``);
+- ``adv_direction(P, Q, user, item_pos, item_neg, adv, seed, call, t, clip_lo, clip_hi) -> (nP, nQ)``
+  and ``adv_apply(W, N, eps) -> (sum, delta)``: the whole-stream adversarial direction and
+  the perturbed table (``ops.adv_direction`` / ``ops.adv_apply``);
 - ``release_contexts() -> int``: frees the cached step contexts (plan workspace and
   the streamed step's version buffers) that ``apr_train`` / ``bpr_apr_step`` keep per
   (device, table shape, batch shape).
@@ -32,7 +35,7 @@ from . import build_native
 
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libacf_torch.so")
 OPS = ("bpr_apr_step", "apr_train", "gather_bpr_fwd_bwd", "row_segment_sum", "l2norm_perturb",
-       "sparse_adagrad_apply", "score_rank", "score_rank_all", "recommend_topk",
+       "sparse_adagrad_apply", "score_rank", "score_rank_all", "recommend_topk", "adv_direction", "adv_apply",
        "release_contexts")
 _lock = threading.Lock()
 _loaded = False

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .evaluate import evaluate, init_eval_model
+from .evaluate import evaluate, init_eval_model, perturbed_tables, triplet_arrays
 from .sampler import DeviceSampler, EpochTriplets, sampling, shuffle
 
 
@@ -104,9 +104,10 @@ def plan_chunk(batch_size: int) -> int:
 
 
 def training_loss_acc(model, sess, train_batches, output_adv=0):
-    """utils.py:159-175: mean per-batch summed clean loss and mean pairwise accuracy."""
-    if output_adv:
-        raise NotImplementedError("output_adv=1 is not used by the APR driver (APR.py:258,266)")
+    """utils.py:159-175: mean per-batch summed clean loss and mean pairwise accuracy.
+    output_adv=1: loss_adv, output_adv and output_neg_adv (utils.py:169-170), the
+    same forward on (P + delta_P, Q + delta_Q), where delta_P / delta_Q are what
+    the last adv_update put there (zeros before any; see adv_update)."""
     if isinstance(train_batches, EpochTriplets):
         u, i, j, B = train_batches.user, train_batches.item_pos, train_batches.item_neg, train_batches.batch_size
     else:
@@ -115,10 +116,31 @@ def training_loss_acc(model, sess, train_batches, output_adv=0):
     nb = u.numel() // B
     if nb == 0:
         return 0.0, 0.0
-    bl, bc, _, _ = ops.bpr_forward(model.embedding_P, model.embedding_Q, u, i, j, B)
+    P, Q = perturbed_tables(model) if output_adv else (model.embedding_P, model.embedding_Q)
+    bl, bc, _, _ = ops.bpr_forward(P, Q, u, i, j, B)
     bl = bl.double().cpu().numpy()
     bc = bc.cpu().numpy().astype(np.float64)
     return float(bl.sum() / nb), float((bc / B).sum() / nb)
+
+
+def adv_update(model, sess, train_batches, adv=None):
+    """utils.py:145-154: one sess.run([update_P, update_Q]) over the whole epoch's
+    triplets as ONE batch.  train_batches: what training_batch returns (an
+    EpochTriplets or its three lists).  Sets model.delta_P / model.delta_Q (dense
+    device tables, zeros from build_graph on) to direction * model.eps and
+    returns them; adv defaults to model.adv ("random": a fresh draw per call).
+    The tables and accumulators are not written.
+    One deviation from the reference: training here never materialises delta, so
+    after training delta_P / delta_Q hold what the last adv_update put there, not
+    the last mini-batch's delta as in TF."""
+    u, i, j = triplet_arrays(train_batches)
+    mode = model.adv if adv is None else adv
+    model._adv_calls = getattr(model, "_adv_calls", 0) + 1
+    nP, nQ = ops.adv_direction(model.embedding_P, model.embedding_Q, u, i, j, adv=mode,
+                               seed=int(model.seed or 0), call=model._adv_calls, t=0)
+    model.delta_P = ops.adv_apply(model.embedding_P, nP, model.eps, want_delta=True)[1]
+    model.delta_Q = ops.adv_apply(model.embedding_Q, nQ, model.eps, want_delta=True)[1]
+    return model.delta_P, model.delta_Q
 
 
 def output_evaluate(model, sess, dataset, train_batches, eval_feed_dicts, epoch_count, batch_time,
@@ -227,6 +249,7 @@ def training(model, dataset, args, runName, epoch_start, epoch_end, time_stamp, 
         train_batches = training_batch(model, sess, batches, args.adver, graph=graph)
         torch.cuda.synchronize(model.device)
         train_time = time() - train_begin
+        model.last_train_batches = train_batches  # the CLI's --robust_eps evaluates on them
         if epoch_count % args.verbose == 0:
             _, ndcg, cur_res, raw_result = output_evaluate(
                 model, sess, dataset, train_batches, eval_feed_dicts, epoch_count, batch_time,

@@ -375,6 +375,43 @@ int acf_recommend_topk(const float* P, const float* Q, int64_t num_user_rows, in
                        int32_t* out_items, float* out_scores, void* workspace, size_t workspace_bytes,
                        int32_t kernel, void* stream);
 
+/* ---- robustness evaluation: a whole-stream adversarial direction ------------
+ * utils.py:145-154 (adv_update): ONE delta over all n triplets as one batch, as
+ * dense tables.  acf_adv_direction fills EVERY row of the unit-direction tables
+ * nP [num_user_rows, dim] and nQ [num_item_rows, dim]; acf_adv_apply turns a
+ * direction into delta = N * eps and W + delta, so one direction serves every
+ * eps.  No context; P, Q and the accumulators are never written; everything runs
+ * on `stream`; the only scratch is `workspace` (device memory, 16-byte aligned,
+ * at least acf_adv_direction_workspace(n, ...) bytes -- a host-only query; a
+ * smaller one is ACF_E_INVALID).  0 <= n < 2^29, no multiple-of-anything rule.
+ *  adv_mode 0 ("grad", APR.py:180-191): g = d/d(P,Q) sum_t softplus(-clip(x+_t -
+ *    x-_t)), the clean loss only; scores are the evaluation's sequential dot
+ *    product, the clip mask and softplus those of the step.  A row is
+ *    g_row * rsqrt(max(|g_row|^2, 1e-12)); a row no triplet touches is +0.0; n = 0
+ *    gives all-zero tables.  A row's terms are added in a fixed order: the pos
+ *    branch's terms in triplet order, then the neg branch's (the reference's
+ *    IndexedSlices concat order); rows of more than 256 terms as partial sums of
+ *    256 consecutive terms added in order.  Two calls on the same inputs give the
+ *    same bits; no float atomics.
+ *  adv_mode 1 ("random", APR.py:170-177): every row of both tables is the
+ *    l2-normalised truncated-normal draw the step's random mode makes for
+ *    (seed, call, t, table, row); the triplets are not read (may be NULL).
+ * check != 0: the call synchronises after its first kernel and returns
+ * ACF_E_RANGE when an index is outside its table, before anything is built on
+ * it (check == 0: such an index is read as row 0, no error).
+ * acf_adv_apply: delta_out = N * eps, sum_out = W + delta_out, two separately
+ * rounded fp32 operations (TF: l2_normalize(...) * eps, then embedding + delta);
+ * either output may be NULL (W may be NULL when sum_out is). */
+int acf_adv_direction_workspace(int64_t n, int64_t num_user_rows, int64_t num_item_rows, int32_t dim,
+                                size_t* bytes);
+int acf_adv_direction(const float* P, const float* Q, int64_t num_user_rows, int64_t num_item_rows,
+                      int32_t dim, const int32_t* user, const int32_t* item_pos, const int32_t* item_neg,
+                      int64_t n, float clip_lo, float clip_hi, int32_t adv_mode, uint64_t seed, uint32_t call,
+                      int32_t t, float* nP, float* nQ, void* workspace, size_t workspace_bytes, int32_t check,
+                      void* stream);
+int acf_adv_apply(const float* W, const float* N, int64_t rows, int32_t dim, float eps, float* delta_out,
+                  float* sum_out, void* stream);
+
 /* ---- sampler: shuffle/_get_train_batch (APR.py:39-81) --------------------
  * Shuffles the n_pos positive pairs with a counter-based permutation of
  * `seed`, keeps floor(n_pos / batch_size) * batch_size of them (drop-last,
