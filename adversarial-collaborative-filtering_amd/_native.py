@@ -82,6 +82,8 @@ SIGNATURES = {
     "acf_adv_direction": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _P, _I64, _F, _F, _I32, _U64,
                                          ctypes.c_uint32, _I32, _P, _P, _P, ctypes.c_size_t, _I32, _P]),
     "acf_adv_apply": (ctypes.c_int, [_P, _P, _I64, _I32, _F, _P, _P, _P]),
+    "acf_fold_in_users": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _P, _I64, _I32, _I32,
+                                         ctypes.POINTER(HParams), _P, _P, _P, _P, _P, _I32, _P]),
     "acf_sample_epoch": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _U64, _I32, _I32, _P, _P,
                                         _P, _P]),
     "acf_gather_bpr_fwd_bwd": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _P, _I64, _F, _F, _P, _P, _P,

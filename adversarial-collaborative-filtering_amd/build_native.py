@@ -31,7 +31,8 @@ LIBS = {
     "apr": {"lib": f"{PKG}/lib/libacf_apr.so",
             "srcs": [f"{PKG}/csrc/acf_apr.hip", f"{PKG}/csrc/acf_ops.hip"],
             "headers": ["include/acf_apr.h", f"{PKG}/csrc/acf_rows.h", f"{PKG}/csrc/acf_hplan.h",
-                        f"{PKG}/csrc/acf_eval.h", f"{PKG}/csrc/acf_topk.h", f"{PKG}/csrc/acf_adv.h"]},
+                        f"{PKG}/csrc/acf_eval.h", f"{PKG}/csrc/acf_topk.h", f"{PKG}/csrc/acf_adv.h",
+                        f"{PKG}/csrc/acf_fold.h"]},
     "neumf": {"lib": f"{PKG}/lib/libacf_neumf.so",
               "srcs": [f"{PKG}/csrc/acf_neumf.hip"],
               "headers": ["include/acf_apr.h", "include/acf_neumf.h"]},

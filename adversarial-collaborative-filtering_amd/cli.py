@@ -67,7 +67,15 @@ def parse_args(argv=None, flavor="ori"):
                    help="After training, evaluate under perturbed tables at these eps (comma separated, e.g. "
                         "\"0.5,1,2\"), gradient and random directions over the last epoch's triplets, and write "
                         "<out>/<runName>.robust (empty: off).")
-    return p.parse_args(argv)
+    p.add_argument("--fold_in", type=str, default=None, metavar="FILE",
+                   help="After training, fold in the new users of FILE (rating TSV: uid<TAB>item<TAB>...; its "
+                        "uids are keys of new users, not rows of the user table) and write their --topk best "
+                        "items to <out>/<runName>.foldin.topk (rows in ascending uid order) and the uids to "
+                        "<out>/<runName>.foldin.users.  Needs --topk.")
+    args = p.parse_args(argv)
+    if args.fold_in is not None and args.topk <= 0:
+        p.error("--fold_in needs --topk K (K > 0)")
+    return args
 
 
 def parse_eps_list(text):
@@ -106,6 +114,37 @@ def read_robust(file):
                 raise ValueError(f"{file}: line {n} has {len(parts)} fields, expected 5")
             rows.append((parts[0], *[float(x) for x in parts[1:]]))
     return rows
+
+
+def read_fold_file(file):
+    """{uid: [items]} of a rating file in the reference's TSV format
+    ("uid<TAB>item[<TAB>rating[<TAB>time]]", ids possibly written as floats);
+    items in file order, repeats kept (fold_lists de-duplicates)."""
+    lists = {}
+    with open(file) as f:
+        for n, line in enumerate(f):
+            line = line.strip()
+            if not line:
+                continue
+            parts = line.split("\t")
+            if len(parts) < 2:
+                raise ValueError(f"{file}: line {n} has {len(parts)} field(s), expected uid<TAB>item")
+            try:
+                uid, item = float(parts[0]), float(parts[1])
+            except ValueError:
+                raise ValueError(f"{file}: line {n}: uid and item must be numbers") from None
+            if uid != int(uid) or item != int(item) or uid < 0 or item < 0:
+                raise ValueError(f"{file}: line {n}: uid and item must be integers >= 0")
+            lists.setdefault(int(uid), []).append(int(item))
+    return lists
+
+
+def write_fold_users(path, name, keys):
+    """One uid per line, in the row order of the .foldin.topk file."""
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, name), "w") as f:
+        for k in keys:
+            f.write("%d\n" % int(k))
 
 
 def write_topk(path, name, items):
@@ -184,6 +223,13 @@ def main(argv=None, flavor="ori"):
         final = amf if args.model == "apr" else m
         items, _ = recommend(final, dataset, k=args.topk)
         write_topk(out, runName + ".topk", items)
+    if args.fold_in is not None:
+        from .evaluate import recommend_new
+        final = amf if args.model == "apr" else m
+        lists = read_fold_file(args.fold_in)
+        items, _ = recommend_new(final, lists, args.topk, seed=args.seed, batch=min(args.batch_size, 512))
+        write_topk(out, runName + ".foldin.topk", items)
+        write_fold_users(out, runName + ".foldin.users", sorted(lists))
     if args.robust_eps:
         from .evaluate import init_eval_model, robustness
         final = amf if args.model == "apr" else m

@@ -279,3 +279,5 @@ extern "C" int acf_sparse_adagrad_apply(float* W, float* acc, int64_t rows, int3
   OPS_TRY(hipGetLastError());
   return ACF_OK;
 }
+
+#include "acf_fold.h"

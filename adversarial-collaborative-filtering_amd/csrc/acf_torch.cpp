@@ -17,6 +17,7 @@
 //   acf::recommend_topk        the k best items per user and their scores (no reference counterpart)
 //   acf::adv_direction         adv_update's direction over a whole triplet stream (utils.py:145-154)
 //   acf::adv_apply             delta = N * eps and W + delta (APR.py:130-141,190)
+//   acf::fold_in_users         rows for new users against a frozen Q (no reference counterpart)
 #include <torch/library.h>
 #include <ATen/ATen.h>
 // ROCm builds of PyTorch keep the "cuda" device type: the guard and stream
@@ -403,6 +404,53 @@ std::tuple<at::Tensor, at::Tensor> adv_apply(const at::Tensor& W, const at::Tens
   return {sum, delta};
 }
 
+// rows, accumulators and per-epoch losses of n new users fitted against a frozen Q
+// (acf_fold_in_users, items range-checked by the call); init / acc_init: [n, d] or None
+std::tuple<at::Tensor, at::Tensor, at::Tensor> fold_in_users(
+    const at::Tensor& Q, const at::Tensor& user_off, const at::Tensor& item_pos_, const at::Tensor& item_neg_,
+    int64_t epochs, int64_t batch, const c10::optional<at::Tensor>& init, const c10::optional<at::Tensor>& acc_init,
+    double lr, double eps, double reg, double reg_adv, bool adver, double clip_lo, double clip_hi) {
+  need_table(Q, "embedding_Q", Q);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
+  need(user_off, "user_off", at::kLong, 1);
+  TORCH_CHECK(user_off.device() == Q.device(), "user_off must live on ", Q.device());
+  TORCH_CHECK(user_off.numel() >= 1, "user_off must have n + 1 entries");
+  TORCH_CHECK(epochs >= 0 && epochs < (1ll << 31), "epochs must be >= 0");
+  TORCH_CHECK(batch >= 1 && batch <= ACF_FOLD_MAX_BATCH, "batch must lie in [1, ", ACF_FOLD_MAX_BATCH, "], got ", batch);
+  at::Tensor ip = idx32(item_pos_, "item_pos", Q);
+  const int64_t n = user_off.numel() - 1, T = ip.numel(), d = Q.size(1);
+  TORCH_CHECK(item_neg_.dim() == 2 && item_neg_.size(0) == epochs && item_neg_.size(1) == T,
+              "item_neg must have shape (epochs, len(item_pos))");
+  at::Tensor in = idx32(item_neg_, "item_neg", Q);
+  const at::Tensor off = user_off.cpu();
+  const int64_t* o = off.data_ptr<int64_t>();
+  TORCH_CHECK(o[0] == 0 && o[n] == T, "user_off must start at 0 and end at len(item_pos)");
+  for (int64_t r = 0; r < n; ++r) TORCH_CHECK(o[r] <= o[r + 1], "user_off must be non-decreasing");
+  const float *ini = nullptr, *aci = nullptr;
+  if (init.has_value()) {
+    need(*init, "init", at::kFloat, 2);
+    TORCH_CHECK(init->device() == Q.device() && init->size(0) == n && init->size(1) == d, "init must be [n, dim] on ",
+                Q.device());
+    ini = init->data_ptr<float>();
+  }
+  if (acc_init.has_value()) {
+    need(*acc_init, "acc_init", at::kFloat, 2);
+    TORCH_CHECK(acc_init->device() == Q.device() && acc_init->size(0) == n && acc_init->size(1) == d,
+                "acc_init must be [n, dim] on ", Q.device());
+    aci = acc_init->data_ptr<float>();
+  }
+  const acf_apr_hparams hp = hparams(lr, eps, reg, reg_adv, adver, clip_lo, clip_hi);
+  at::Tensor P_new = at::empty({n, d}, Q.options()), acc_new = at::empty({n, d}, Q.options());
+  at::Tensor loss = at::empty({epochs, n}, Q.options());
+  ok(acf_fold_in_users(Q.data_ptr<float>(), Q.size(0), (int32_t)d, user_off.data_ptr<int64_t>(), n,
+                       T ? ip.data_ptr<int32_t>() : nullptr, T && epochs ? in.data_ptr<int32_t>() : nullptr, T,
+                       (int32_t)epochs, (int32_t)batch, &hp, ini, aci, n ? P_new.data_ptr<float>() : nullptr,
+                       n ? acc_new.data_ptr<float>() : nullptr, n && epochs ? loss.data_ptr<float>() : nullptr, 1,
+                       stream_of(Q)),
+     "acf_fold_in_users");
+  return {P_new, acc_new, loss};
+}
+
 }  // namespace
 
 #ifndef ACF_BUILD_HASH
@@ -434,6 +482,9 @@ TORCH_LIBRARY(acf, m) {
   m.def("adv_direction(Tensor P, Tensor Q, Tensor user, Tensor item_pos, Tensor item_neg, str adv=\"grad\", "
         "int seed=0, int call=1, int t=0, float clip_lo=-80.0, float clip_hi=1e8) -> (Tensor nP, Tensor nQ)");
   m.def("adv_apply(Tensor W, Tensor N, float eps) -> (Tensor sum, Tensor delta)");
+  m.def("fold_in_users(Tensor Q, Tensor user_off, Tensor item_pos, Tensor item_neg, int epochs, int batch=512, "
+        "Tensor? init=None, Tensor? acc_init=None, float lr=0.05, float eps=0.5, float reg=0., float reg_adv=1., "
+        "bool adver=True, float clip_lo=-80., float clip_hi=100000000.) -> (Tensor P_new, Tensor acc_new, Tensor loss)");
 }
 
 TORCH_LIBRARY_IMPL(acf, CUDA, m) {
@@ -448,4 +499,5 @@ TORCH_LIBRARY_IMPL(acf, CUDA, m) {
   m.impl("recommend_topk", &recommend_topk);
   m.impl("adv_direction", &adv_direction);
   m.impl("adv_apply", &adv_apply);
+  m.impl("fold_in_users", &fold_in_users);
 }

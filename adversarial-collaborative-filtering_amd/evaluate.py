@@ -220,3 +220,133 @@ def robustness(model, dataset, plan: EvalPlan, triplets, eps_list, modes=("grad"
             hr, ndcg, auc = raw.mean(axis=0)[:, -1].tolist() if len(pos) else (0.0, 0.0, 0.0)
             rows.append((mode, eps, hr, ndcg, auc))
     return rows
+
+
+# ---- fold-in: rows for users who were not in the training set -----------------
+class FoldIn:
+    """What fold_in returns: keys (the dict's keys ascending, or 0..n-1 for a
+    list of lists), the CSR (user_off int64 [n + 1], item_pos int32 [T], numpy)
+    of the sorted unique lists, and the device tensors P [n, d], acc [n, d] (the
+    fitted rows and their Adagrad accumulators) and loss [epochs, n]."""
+
+    def __init__(self, keys, user_off, item_pos, P, acc, loss):
+        self.keys, self.user_off, self.item_pos = keys, user_off, item_pos
+        self.P, self.acc, self.loss = P, acc, loss
+
+    def __len__(self):
+        return len(self.keys)
+
+
+def fold_lists(lists):
+    """(keys, user_off int64 [n + 1], item_pos int32 [T]) of `lists`: a sequence
+    of item lists (keys 0..n-1, in order) or a dict key -> items (keys
+    ascending).  Each list is sorted and de-duplicated; an empty list stays an
+    empty row.  Items must be integers >= 0.  Pure numpy."""
+    if isinstance(lists, dict):
+        keys = sorted(lists)
+        rows = [lists[k] for k in keys]
+    else:
+        rows = list(lists)
+        keys = list(range(len(rows)))
+    out = []
+    for k, row in zip(keys, rows):
+        a = np.asarray(list(row) if not isinstance(row, np.ndarray) else row)
+        if a.size == 0:
+            out.append(np.zeros(0, np.int32))
+            continue
+        if a.ndim != 1 or a.dtype.kind not in "iu":
+            raise ValueError(f"list of {k!r}: items must be a flat sequence of integers")
+        if a.min() < 0 or a.max() >= 2 ** 31:
+            raise ValueError(f"list of {k!r}: item outside [0, 2^31)")
+        out.append(np.unique(a).astype(np.int32))
+    off = np.zeros(len(out) + 1, dtype=np.int64)
+    np.cumsum([len(r) for r in out], out=off[1:])
+    items = np.concatenate(out) if out else np.zeros(0, np.int32)
+    return keys, off, items.astype(np.int32)
+
+
+def fold_negatives(user_off, item_pos, num_items: int, epochs: int, seed: int = 0):
+    """item_neg int32 [epochs, T]: per positive and epoch one item uniform on
+    [0, num_items), redrawn while it is in that user's own list (APR.py:76-77).
+    Reproducible from `seed` (numpy RandomState).  A user whose list holds every
+    item has no admissible negative: ValueError."""
+    off = np.asarray(user_off, dtype=np.int64)
+    items = np.asarray(item_pos, dtype=np.int64)
+    num_items, epochs, T = int(num_items), int(epochs), len(items)
+    if num_items <= 0:
+        raise ValueError("num_items must be positive")
+    if T and (items.min() < 0 or items.max() >= num_items):
+        raise ValueError(f"a list holds an item outside [0, {num_items})")
+    lens = np.diff(off)
+    if (lens >= num_items).any():
+        raise ValueError("a list holds every item: no admissible negative")
+    owner = np.repeat(np.arange(len(lens), dtype=np.int64), lens)
+    keys = owner * num_items + items  # ascending: owners ascend, lists are sorted
+    rng = np.random.RandomState(int(seed) & 0xFFFFFFFF)
+    own = np.tile(owner, epochs)
+    neg = rng.randint(num_items, size=epochs * T).astype(np.int64)
+    todo = np.arange(epochs * T)
+    while len(todo):
+        k = own[todo] * num_items + neg[todo]
+        at = np.minimum(np.searchsorted(keys, k), T - 1)
+        todo = todo[keys[at] == k]
+        neg[todo] = rng.randint(num_items, size=len(todo))
+    return neg.astype(np.int32).reshape(epochs, T)
+
+
+def _fold_target(model_or_tables):
+    """(Q, num_items, default hparams) of an MF-like model, a (P, Q) pair or Q.
+    A model's default takes its lr, eps, reg, reg_adv and adver as they are: a
+    plain BPR model (adver=0) folds in WITHOUT the adversarial term.  The rest is
+    not carried over: the delta is always the gradient one (a model trained with
+    adv="random" folds in with adv="grad", the only delta fold-in takes) and the
+    clip bounds are the graph's constants (-80, 1e8)."""
+    m = model_or_tables
+    if hasattr(m, "embedding_Q"):
+        hp = m.hparams()
+        hp = ops.StepHParams(lr=hp.lr, eps=hp.eps, reg=hp.reg, reg_adv=hp.reg_adv, adver=hp.adver)
+        return m.embedding_Q, min(int(m.num_items), m.embedding_Q.shape[0]), hp
+    Q = m[1] if isinstance(m, (tuple, list)) else m
+    return Q, Q.shape[0], ops.StepHParams(adver=1)
+
+
+def fold_in(model_or_tables, lists, epochs: int = 20, batch: int = 512, seed: int = 0, hp=None, init=None,
+            num_items=None) -> FoldIn:
+    """Fit a row to every NEW user's item list while the item table stays fixed
+    (ops.fold_in_users): APR's own step, adversarial term included, so a
+    folded-in user is regularised like a trained one.  model_or_tables: an MF (or
+    anything with embedding_Q / num_items / hparams()), a (P, Q) pair or Q.
+    lists: a sequence of item lists or a dict key -> items (see fold_lists).
+    Negatives: fold_negatives(seed) over [0, num_items) (default: the model's
+    num_items, or every row of Q).  hp: default the model's own lr, eps, reg,
+    reg_adv and adver with the gradient delta -- so a BPR model (adver=0) folds
+    in without the adversarial term; pass hp=StepHParams(adver=1, ...) to force
+    it (tables: StepHParams(adver=1)).  init: None, a
+    FoldIn, or (P [n, d], acc [n, d]) device tensors of an earlier fit of the
+    same users, to continue when lists have grown."""
+    Q, n_items, hp0 = _fold_target(model_or_tables)
+    hp = hp0 if hp is None else hp
+    n_items = int(n_items if num_items is None else num_items)
+    if n_items > Q.shape[0]:
+        raise ValueError("num_items exceeds item rows")
+    keys, off, items = fold_lists(lists)
+    neg = fold_negatives(off, items, n_items, epochs, seed)
+    P0 = A0 = None
+    if init is not None:
+        P0, A0 = (init.P, init.acc) if isinstance(init, FoldIn) else init
+    P, acc, loss = ops.fold_in_users(Q, off, items, neg, hp, int(epochs), int(batch), init=P0, acc_init=A0)
+    return FoldIn(keys, off, items, P, acc, loss)
+
+
+def recommend_new(model_or_tables, lists, k: int, **fold_args):
+    """The k best items for every NEW user: fold_in(lists, **fold_args), then
+    ops.recommend_topk on the folded rows with the user's own list excluded.
+    (items int32 [n, k], scores float32 [n, k]) numpy arrays, rows in fold_lists'
+    key order (a dict's keys ascending)."""
+    import torch
+    Q, n_items, _ = _fold_target(model_or_tables)
+    n_items = int(fold_args.get("num_items") or n_items)
+    f = fold_in(model_or_tables, lists, **fold_args)
+    users = torch.arange(len(f), dtype=torch.int32, device=Q.device)
+    items, scores = ops.recommend_topk(f.P, Q, users, int(k), n_items, excl_off=f.user_off, excl_items=f.item_pos)
+    return items.cpu().numpy(), scores.cpu().numpy()

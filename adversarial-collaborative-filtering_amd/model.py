@@ -205,6 +205,18 @@ class MF:
         from .evaluate import recommend
         return recommend(self, dataset, users=users, k=k)
 
+    def fold_in(self, lists, **fold_args):
+        """evaluate.fold_in: rows for new users fitted against this model's frozen
+        item table (a FoldIn)."""
+        from .evaluate import fold_in
+        return fold_in(self, lists, **fold_args)
+
+    def recommend_new(self, lists, k, **fold_args):
+        """evaluate.recommend_new: the k best items of new users, their own lists
+        excluded: (items [n, k], scores [n, k]) numpy arrays."""
+        from .evaluate import recommend_new
+        return recommend_new(self, lists, k, **fold_args)
+
     def adv_update(self, train_batches, adv=None):
         """train.adv_update: delta_P / delta_Q over all the triplets as one batch."""
         from .train import adv_update

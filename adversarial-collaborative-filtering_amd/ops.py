@@ -816,6 +816,108 @@ def adv_apply(W, N, eps: float, want_delta: bool = False):
     return (out, delta) if want_delta else out
 
 
+FOLD_MAX_BATCH = 512  # ACF_FOLD_MAX_BATCH
+
+
+def _fold_csr(user_off, n_items: int):
+    """user_off as a host int64 array after the CSR checks (ValueError)."""
+    import numpy as np
+    off = user_off.detach().cpu().numpy() if isinstance(user_off, torch.Tensor) else np.asarray(user_off)
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError(f"user_off must be 1-D with n + 1 entries, got shape {off.shape}")
+    if off.dtype.kind not in "iu":
+        raise ValueError(f"user_off must be an integer array, got {off.dtype}")
+    off = off.astype(np.int64)
+    if off[0] != 0:
+        raise ValueError(f"user_off[0] must be 0, got {off[0]}")
+    if (np.diff(off) < 0).any():
+        raise ValueError("user_off must be non-decreasing")
+    if off[-1] != n_items:
+        raise ValueError(f"user_off[-1] must be len(item_pos) = {n_items}, got {off[-1]}")
+    return off
+
+
+def _fold_items(t, name: str, device, shape) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(t)
+    if t.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name} must be int32 or int64, got {t.dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _fold_table(t, name: str, device, shape=None) -> int:
+    try:
+        ptr = _require(t, name, torch.float32, device, 2)
+    except TypeError as e:
+        raise ValueError(str(e)) from None
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    return ptr
+
+
+def fold_in_users(Q, user_off, item_pos, item_neg, hp: StepHParams, epochs: int, batch: int = FOLD_MAX_BATCH,
+                  init=None, acc_init=None, check: bool = True):
+    """Rows for n NEW users fitted against the frozen item table Q, on the GPU
+    (acf_fold_in_users): (P_new [n, d], acc_new [n, d], loss [epochs, n]).
+    User r owns item_pos[user_off[r]:user_off[r+1]] (CSR; user_off int64 [n + 1],
+    item_pos int32 [T]); item_neg [epochs, T] holds one negative per positive per
+    epoch.  For every epoch, every consecutive slice of at most `batch` positions
+    of a user's list is one training_batch iteration (APR.py:143-195) on the
+    one-row user table [p_r] and Q: with hp.adver the step's own gradient delta
+    (of p_r and of every item row of the slice), reg as in the step; only p_r and
+    its Adagrad accumulator are kept, Q is never written.  init / acc_init [n, d]
+    (default zeros / 0.1): pass a previous (P_new, acc_new) to continue a fit.
+    loss[e, r]: the user's clean loss of epoch e, each slice before its update.
+    A user's outputs depend on that user's inputs only, bit for bit, and equal
+    inputs give equal bits.  Bad arguments raise ValueError before any native
+    call; with check, an item outside Q raises NativeIndexError."""
+    if not isinstance(hp, StepHParams):
+        raise ValueError(f"hp must be a StepHParams, got {type(hp).__name__}")
+    if hp.adv != "grad" or hp.zero_delta:
+        raise ValueError("fold-in takes only the gradient delta: adv='grad' and zero_delta=0 "
+                         f"(got adv={hp.adv!r}, zero_delta={hp.zero_delta})")
+    if isinstance(batch, bool) or not isinstance(batch, int) or not 1 <= batch <= FOLD_MAX_BATCH:
+        raise ValueError(f"batch must be an int in [1, {FOLD_MAX_BATCH}], got {batch!r}")
+    if isinstance(epochs, bool) or not isinstance(epochs, int) or epochs < 0:
+        raise ValueError(f"epochs must be an int >= 0, got {epochs!r}")
+    T = len(item_pos)
+    off = _fold_csr(user_off, T)
+    n = off.size - 1
+    if tuple(getattr(item_neg, "shape", ())) != (epochs, T):
+        raise ValueError(f"item_neg must have shape (epochs, len(item_pos)) = {(epochs, T)}, "
+                         f"got {tuple(getattr(item_neg, 'shape', ()))}")
+    _fold_table(Q, "embedding_Q", None)
+    dev = Q.device
+    I1, d = Q.shape
+    if d < 4 or d > 1024 or d % 4:
+        raise ValueError(f"dim must be a multiple of 4 in [4, 1024], got {d}")
+    ip = _fold_items(item_pos, "item_pos", dev, (T,))
+    ineg = _fold_items(item_neg, "item_neg", dev, (epochs, T))
+    if init is not None:
+        _fold_table(init, "init", dev, (n, d))
+    if acc_init is not None:
+        _fold_table(acc_init, "acc_init", dev, (n, d))
+    offd = (user_off if isinstance(user_off, torch.Tensor) and user_off.dtype == torch.int64
+            and user_off.device == dev and user_off.is_contiguous()
+            else torch.as_tensor(off).to(dev))
+    settle_tables()
+    P_new = torch.empty((n, d), dtype=torch.float32, device=dev)
+    acc_new = torch.empty((n, d), dtype=torch.float32, device=dev)
+    loss = torch.empty((epochs, n), dtype=torch.float32, device=dev)
+    if n == 0:
+        return P_new, acc_new, loss
+    c = hp.to_c()
+    with _on(dev):
+        call("acf_fold_in_users", Q.data_ptr(), I1, d, offd.data_ptr(), n, ip.data_ptr() if T else None,
+             ineg.data_ptr() if T and epochs else None, T, epochs, batch, ctypes.byref(c),
+             init.data_ptr() if init is not None else None, acc_init.data_ptr() if acc_init is not None else None,
+             P_new.data_ptr(), acc_new.data_ptr(), loss.data_ptr() if epochs else None, int(bool(check)),
+             _stream_ptr(dev))
+    return P_new, acc_new, loss
+
+
 def eval_positions_list(P, Q, users, test_items, cand_off, cand_items):
     """_eval_by_user positions over explicit candidate lists ("sample" mode)."""
     settle_tables()

@@ -148,6 +148,29 @@ class APR(Recommender):
                                            off, ex)
         return items.cpu().numpy(), scores.cpu().numpy()
 
+    @staticmethod
+    def _new_lists(train):
+        """Item lists of new users: a dok/CSR matrix (row r = new user r), or
+        lists / a dict as evaluate.fold_lists takes them."""
+        if hasattr(train, "tocsr"):
+            csr = train.tocsr()
+            return [csr.indices[csr.indptr[r]:csr.indptr[r + 1]] for r in range(csr.shape[0])]
+        return train
+
+    def fold_in(self, train, **fold_args):
+        """evaluate.fold_in for the new users of `train` (a matrix like
+        get_train_instances takes, one row per new user, or item lists)."""
+        self._ensure()
+        fold_args.setdefault("num_items", self.iNum)
+        return self.model.fold_in(self._new_lists(train), **fold_args)
+
+    def recommend_new(self, train, k, **fold_args):
+        """evaluate.recommend_new for the new users of `train`: (items [n, k],
+        scores [n, k]) numpy arrays among [0, iNum), their own items excluded."""
+        self._ensure()
+        fold_args.setdefault("num_items", self.iNum)
+        return self.model.recommend_new(self._new_lists(train), k, **fold_args)
+
     def adv_update(self, x_train, adv=None):
         """train.adv_update on the triplets of get_train_instances: the model's
         delta_P / delta_Q over all of them as one batch."""

@@ -18,6 +18,13 @@ SURVEY.md §8(b) proposes:
 - ``adv_direction(P, Q, user, item_pos, item_neg, adv, seed, call, t, clip_lo, clip_hi) -> (nP, nQ)``
   and ``adv_apply(W, N, eps) -> (sum, delta)``: the whole-stream adversarial direction and
   the perturbed table (``ops.adv_direction`` / ``ops.adv_apply``);
+- ``fold_in_users(Q, user_off, item_pos, item_neg, epochs, batch, init, acc_init, lr, eps, reg, reg_adv,
+  adver, clip_lo, clip_hi) -> (P_new, acc_new, loss)``: rows for new users against a frozen
+  item table (``ops.fold_in_users``, the same bits).  The op always synchronises with the host:
+  it copies ``user_off`` back to validate the CSR, and it always runs the native range check
+  of the items (``check=1``: a small stream-ordered allocation, one kernel and a stream
+  synchronise before the fold-in launch).  Use ``ops.fold_in_users(..., check=False)`` with a
+  host ``user_off`` for a call that stays asynchronous;
 - ``release_contexts() -> int``: frees the cached step contexts (plan workspace and
   the streamed step's version buffers) that ``apr_train`` / ``bpr_apr_step`` keep per
   (device, table shape, batch shape).
@@ -36,7 +43,7 @@ from . import build_native
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libacf_torch.so")
 OPS = ("bpr_apr_step", "apr_train", "gather_bpr_fwd_bwd", "row_segment_sum", "l2norm_perturb",
        "sparse_adagrad_apply", "score_rank", "score_rank_all", "recommend_topk", "adv_direction", "adv_apply",
-       "release_contexts")
+       "fold_in_users", "release_contexts")
 _lock = threading.Lock()
 _loaded = False
 

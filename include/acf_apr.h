@@ -412,6 +412,40 @@ int acf_adv_direction(const float* P, const float* Q, int64_t num_user_rows, int
 int acf_adv_apply(const float* W, const float* N, int64_t rows, int32_t dim, float eps, float* delta_out,
                   float* sum_out, void* stream);
 
+/* ---- fold-in: new users against a frozen item table --------------------------
+ * (no reference counterpart: the reference can only retrain.)  User r of the CSR
+ * user_off int64 [n + 1] / item_pos [T] gets a row fitted to its list while Q
+ * stays fixed.  For epoch e = 0..epochs-1 and every consecutive slice of at most
+ * `batch` positions of [user_off[r], user_off[r+1]) (the last one may be short;
+ * the same order every epoch) the user takes ONE training_batch iteration
+ * (APR.py:143-195) on the one-row user table [p_r] and Q with the batch
+ * {(0, item_pos[k], item_neg[e*T + k])}; only p_r and its Adagrad accumulator are
+ * kept.  With hp->adver the delta is the step's own: delta_p from the slice's
+ * summed clean gradient of p_r, delta_q per item row of the slice from its clean
+ * gradient summed over all the row's occurrences in the slice (pos branch, then
+ * neg branch, triplet order), both l2-normalised with the 1e-12 floor; reg acts
+ * on p_r as in the step (2*reg/(B_slice*dim), twice when adversarial).
+ * hp->adv_mode != 0 or hp->zero_delta != 0 is ACF_E_INVALID.
+ *   init, acc_init [n, dim]: starting rows / accumulators (NULL: zeros / 0.1);
+ *   P_new, acc_new [n, dim]: the fitted rows and accumulators (pass them back as
+ *     init / acc_init to continue when a list grows);
+ *   loss [epochs, n] (may be NULL): the clean loss summed over the user's slices
+ *     of that epoch, each slice before its own update.
+ * A user with an empty list keeps its inits and has loss 0; epochs = 0 copies the
+ * inits.  A user's outputs depend on that user's inputs only and are the same
+ * bits in every call (no float atomics, fixed summation orders).  Q is never
+ * written; no workspace.  1 <= batch <= ACF_FOLD_MAX_BATCH.  user_off must be
+ * non-decreasing within [0, T] (offsets outside are clamped).
+ * check != 0: the call first synchronises and returns ACF_E_RANGE when an item is
+ * outside [0, num_item_rows), before anything is written (check == 0: such an
+ * item is read as row 0). */
+#define ACF_FOLD_MAX_BATCH 512
+int acf_fold_in_users(const float* Q, int64_t num_item_rows, int32_t dim, const int64_t* user_off,
+                      int64_t n_users, const int32_t* item_pos, const int32_t* item_neg, int64_t T,
+                      int32_t epochs, int32_t batch, const acf_apr_hparams* hp, const float* init,
+                      const float* acc_init, float* P_new, float* acc_new, float* loss, int32_t check,
+                      void* stream);
+
 /* ---- sampler: shuffle/_get_train_batch (APR.py:39-81) --------------------
  * Shuffles the n_pos positive pairs with a counter-based permutation of
  * `seed`, keeps floor(n_pos / batch_size) * batch_size of them (drop-last,
