@@ -210,6 +210,9 @@ NEUMF_SIGNATURES = {
     "acf_neumf_predict": (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _P]),
     "acf_neumf_train": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I64,
                                        ctypes.POINTER(NeuMFHParams), _P, _P]),
+    "acf_neumf_rank_all_workspace": (ctypes.c_int, [_I32, _I32, _I32, ctypes.POINTER(ctypes.c_size_t)]),
+    "acf_neumf_rank_all": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P, _P, _I32, _P, _P, _P,
+                                          ctypes.c_size_t, _P]),
     "acf_kbpr_create": (ctypes.c_int, [ctypes.POINTER(_P), _I64, _I64, _I32, _I32]),
     "acf_kbpr_destroy": (ctypes.c_int, [_P]),
     "acf_kbpr_train": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I64,

@@ -11,6 +11,8 @@ per user; the ranking rules are the reference's:
   item appended), i.e. a stable sort, so a tie goes to the item listed first and
   a duplicated item keeps its first position and last score.  HR = gt in top K,
   NDCG = log 2 / log(rank + 2).
+- ``evaluate_model_all``: the same protocol for the ``--eval all`` lists of a
+  ranker that ranks whole users on the GPU (``positions_all``), without the lists.
 - ``evaluate_apr_mode`` (evaluation.py:94-140): every rating ``[u, gt]``, the first
   100 negatives; position = #(negatives scoring >= gt); HR@k / NDCG@k for
   k = 1..100.
@@ -79,6 +81,22 @@ def evaluate_model(model, testRatings, testNegatives, K, num_thread=1):
         rank = int((vals > vals[g]).sum() + (vals[:g] == vals[g]).sum())
         hits.append(1 if rank < K else 0)
         ndcgs.append(math.log(2) / math.log(rank + 2) if rank < K else 0)
+    return hits, ndcgs
+
+
+def evaluate_model_all(model, testRatings, train, K):
+    """``evaluate_model`` for the ``--eval all`` negatives (every item the user did
+    not train on except 0 and the test item) of a ranker with ``positions_all``:
+    -> (hits, ndcgs), entry for entry what evaluate_model returns for those lists,
+    from one position per user (rank = #(negatives scoring >= gt)); no negative
+    list and no pair array is built."""
+    users = np.arange(1, len(testRatings), dtype=np.int64)
+    if not len(users):
+        return [], []
+    tests = np.asarray([testRatings[u] for u in users.tolist()], dtype=np.int64)
+    rank = np.asarray(model.positions_all(users, tests, train)).reshape(-1)
+    hits = [1 if r < K else 0 for r in rank.tolist()]
+    ndcgs = [math.log(2) / math.log(r + 2) if r < K else 0 for r in rank.tolist()]
     return hits, ndcgs
 
 

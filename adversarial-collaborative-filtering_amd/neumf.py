@@ -27,6 +27,32 @@ from . import _native
 from .ops import _idx, _require, _stream_ptr
 
 NAMES = ("MF_U", "MF_I", "MLP_U", "MLP_I", "W1", "b1", "W2", "b2", "Wo", "bo")
+RANK_MAX_K = 128  # TOPK_MAX_K of acf_topk_select.h
+
+
+def rank_all_workspace(n_users: int, num_candidates: int, k: int) -> int:
+    """Bytes of device workspace acf_neumf_rank_all needs (a host-only query)."""
+    size = ctypes.c_size_t()
+    _native.call_neumf("acf_neumf_rank_all_workspace", int(n_users), int(num_candidates), int(k),
+                       ctypes.byref(size))
+    return int(size.value)
+
+
+def _int_vec(x, name: str):
+    """A 1-D integer index argument (tensor or array-like; [N] or [N, 1]), checked on
+    the host: TypeError for a non-integer dtype."""
+    if isinstance(x, torch.Tensor):
+        if x.dtype.is_floating_point or x.dtype.is_complex or x.dtype == torch.bool:
+            raise TypeError(f"{name} must hold integers, got {x.dtype}")
+        if x.dim() > 2 or (x.dim() == 2 and x.shape[1] != 1):
+            raise ValueError(f"{name} must be [N] or [N, 1], got shape {tuple(x.shape)}")
+        return x.reshape(-1)
+    a = np.asarray(x)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"{name} must hold integers, got {a.dtype}")
+    if a.ndim > 2 or (a.ndim == 2 and a.shape[1] != 1):
+        raise ValueError(f"{name} must be [N] or [N, 1], got shape {a.shape}")
+    return torch.as_tensor(a.reshape(-1).astype(np.int64, copy=False))
 
 
 def _shapes(U1, I1, d):
@@ -183,6 +209,104 @@ class NeuMFContext:
                                    i.data_ptr(), u.numel(), out.data_ptr(), _stream_ptr(s.device))
         return out
 
+    def rank_all(self, users, k: int = 0, num_candidates: int | None = None, excl_off=None, excl_items=None,
+                 test_items=None):
+        """All-items ranking without a pair list or a score array (acf_neumf_rank_all):
+        -> (positions int32 [n] | None, items int32 [n, k] | None, scores float32
+        [n, k] | None) on the device.  Candidates of users[j]: [0, num_candidates)
+        (default: every item row) minus the set excl_items[excl_off[j]:excl_off[j+1]]
+        (unsorted, repeated and out-of-range entries are fine).  Scores are
+        ``predict``'s bit for bit; lists are ordered by score descending, ties to
+        the lower id, -1 / -inf past a user's candidates.  With test_items,
+        positions[j] = #(candidates scoring >= the test item); put the test item
+        into the exclusion list.  Everything is validated before any launch."""
+        s = self.state
+        if not isinstance(k, (int, np.integer)) or isinstance(k, bool) or not 0 <= k <= RANK_MAX_K:
+            raise ValueError(f"k must be an int in [0, {RANK_MAX_K}], got {k!r}")
+        k = int(k)
+        u = _int_vec(users, "users")
+        n = u.numel()
+        nc = s.I1 if num_candidates is None else int(num_candidates)
+        if not 1 <= nc <= s.I1:
+            raise ValueError(f"num_candidates must lie in [1, {s.I1}] (item rows), got {nc}")
+        if (excl_off is None) != (excl_items is None):
+            raise ValueError("excl_off and excl_items go together")
+        off = ex = None
+        if excl_off is not None:
+            off, ex = _int_vec(excl_off, "excl_off"), _int_vec(excl_items, "excl_items")
+            if off.numel() != n + 1:
+                raise ValueError(f"excl_off must have len(users) + 1 = {n + 1} entries, got {off.numel()}")
+            o = off.cpu()
+            if int(o[0]) < 0 or int(o[-1]) > ex.numel() or bool((o[1:] < o[:-1]).any()):
+                raise ValueError("excl_off must be non-decreasing within [0, len(excl_items)]")
+        t = None
+        if test_items is not None:
+            t = _int_vec(test_items, "test_items")
+            if t.numel() != n:
+                raise ValueError(f"test_items must have len(users) = {n} entries, got {t.numel()}")
+        if k == 0 and t is None:
+            raise ValueError("nothing to compute: k == 0 and no test_items")
+        dev = s.device
+        u = _idx(u, "users", dev)
+        if off is not None:
+            off = off.to(device=dev, dtype=torch.int64).contiguous()
+            ex = _idx(ex, "excl_items", dev) if ex.numel() else torch.zeros(1, dtype=torch.int32, device=dev)
+        pos = items = scores = None
+        if t is not None:
+            t = _idx(t, "test_items", dev)
+            pos = torch.empty(n, dtype=torch.int32, device=dev)
+        if k:
+            items = torch.empty((n, k), dtype=torch.int32, device=dev)
+            scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+        if n == 0:
+            return pos, items, scores
+        nbytes = rank_all_workspace(n, nc, k)
+        work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            _native.call_neumf("acf_neumf_rank_all", self._ptr, s.params.data_ptr(), u.data_ptr(), n, nc,
+                               0 if off is None else off.data_ptr(), 0 if ex is None else ex.data_ptr(),
+                               0 if t is None else t.data_ptr(), 0 if pos is None else pos.data_ptr(), k,
+                               0 if items is None else items.data_ptr(),
+                               0 if scores is None else scores.data_ptr(), work.data_ptr(), nbytes,
+                               _stream_ptr(dev))
+        return pos, items, scores
+
+
+def _train_pairs(train):
+    """(users, items) int64 of the train matrix (dok: key order; else coo order)."""
+    if hasattr(train, "keys"):
+        pairs = np.array(list(train.keys()), dtype=np.int64).reshape(-1, 2)
+        return pairs[:, 0], pairs[:, 1]
+    coo = train.tocoo()
+    return np.asarray(coo.row, np.int64), np.asarray(coo.col, np.int64)
+
+
+class _TrainLists:
+    """The train matrix as what evaluate.train_exclusions reads: sorted_lists() ->
+    (offsets [rows + 1], items), each user's unique train items ascending."""
+
+    def __init__(self, train, num_rows: int, num_items: int):
+        u, i = _train_pairs(train)
+        keys = np.unique(u * int(num_items) + i)
+        self.off = np.zeros(int(num_rows) + 1, dtype=np.int64)
+        np.cumsum(np.bincount(keys // int(num_items), minlength=int(num_rows))[:int(num_rows)], out=self.off[1:])
+        self.items = (keys % int(num_items)).astype(np.int32)
+
+    def sorted_lists(self):
+        return self.off, self.items
+
+
+def _append_columns(off, items, extra):
+    """The exclusion CSR with extra[j] (int [n, m]) appended to list j."""
+    n, m = extra.shape
+    lens = np.diff(off)
+    noff = off + m * np.arange(n + 1, dtype=np.int64)
+    out = np.empty(int(noff[-1]), dtype=np.int32)
+    out[np.arange(off[-1], dtype=np.int64) + m * np.repeat(np.arange(n, dtype=np.int64), lens)] = items
+    for j in range(m):
+        out[noff[1:] - m + j] = extra[:, j]
+    return noff, out
+
 
 def mf_train_instances(train, iNum, rng):
     """MF.py:42-56: per training pair (u, i), in the train matrix's key order, a
@@ -190,12 +314,7 @@ def mf_train_instances(train, iNum, rng):
     training pair (label 0).  The reference redraws until the negative is valid;
     a user whose pairs cover all of [1, iNum) has none, and is refused here
     (the reference would loop forever)."""
-    if hasattr(train, "keys"):
-        pairs = np.array(list(train.keys()), dtype=np.int64).reshape(-1, 2)
-        u, i = pairs[:, 0], pairs[:, 1]
-    else:
-        coo = train.tocoo()
-        u, i = np.asarray(coo.row, np.int64), np.asarray(coo.col, np.int64)
+    u, i = _train_pairs(train)
     keys = np.unique(u * iNum + i)
     per_user = np.bincount((keys // iNum)[(keys % iNum) >= 1], minlength=int(u.max(initial=0)) + 1)
     if len(u) and (per_user[u] >= iNum - 1).any():
@@ -275,6 +394,48 @@ class NeuMF:
         ctx = self._context(1)
         out = ctx.predict(np.asarray(users).reshape(-1), np.asarray(items).reshape(-1))
         return out.cpu().numpy().reshape(-1, 1)
+
+    def _exclusions(self, users, train, test_items=None):
+        """Exclusion CSR of `users`: item 0 (run.py's masking id), the test item if
+        given, and with `train` the user's train items (evaluate.train_exclusions)."""
+        from .evaluate import train_exclusions
+        users = np.asarray(users, dtype=np.int64).reshape(-1)
+        if train is None:
+            off, items = np.zeros(len(users) + 1, np.int64), np.zeros(0, np.int32)
+        else:
+            if getattr(self, "_lists_of", None) is not train:  # one CSR per train matrix, not per epoch
+                self._lists, self._lists_of = _TrainLists(train, self.uNum, self.iNum), train
+            off, items = train_exclusions(self._lists, users)
+        extra = [np.zeros(len(users), np.int32)]
+        if test_items is not None:
+            extra.append(np.asarray(test_items, dtype=np.int32).reshape(-1))
+        return _append_columns(off, items, np.stack(extra, 1))
+
+    def recommend(self, users, k, train=None):
+        """The k best items of every user in `users` under ``rank``'s scores, on the
+        GPU with no pair list (NeuMFContext.rank_all): numpy (items int32 [n, k],
+        scores float32 [n, k]), -1 / -inf past a user's candidates.  With `train`
+        (what get_train_instances takes) each user's train items and item 0 (the
+        masking id) are excluded; without it nothing is.  Candidates are the ids
+        below the constructor's iNum (the table has one more row, NeuMF.py:12-13)."""
+        users = np.asarray(users, dtype=np.int64).reshape(-1)
+        off = ex = None
+        if train is not None:
+            off, ex = self._exclusions(users, train)
+        _, items, scores = self._context(1).rank_all(users, int(k), self.iNum - 1, off, ex)
+        return items.cpu().numpy(), scores.cpu().numpy()
+
+    def positions_all(self, users, test_items, train):
+        """Per user the number of candidates scoring >= the user's test item, the
+        candidates being every item except 0, the user's train items and the test
+        item: the rank run.py's --eval all protocol gives it.  int32 numpy [n]."""
+        users = np.asarray(users, dtype=np.int64).reshape(-1)
+        tests = np.asarray(test_items, dtype=np.int64).reshape(-1)
+        if len(tests) != len(users):
+            raise ValueError("users and test_items lengths differ")
+        off, ex = self._exclusions(users, train, tests)
+        pos, _, _ = self._context(1).rank_all(users, 0, self.iNum - 1, off, ex, tests)
+        return pos.cpu().numpy()
 
     def save(self, path):
         np.savez(path if path.endswith(".npz") else path + ".npz", **self.state.numpy())

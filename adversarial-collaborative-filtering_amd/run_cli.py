@@ -60,7 +60,39 @@ def parse_args(argv=None):
     p.add_argument("--ckpt", type=int, default=1, help="Save the model per X epochs.")
     p.add_argument("--save_model", type=int, default=1, help="Save model")
     p.add_argument("--seed", type=int, default=0, help="(MI355X build) seed of init and sampling")
-    return p.parse_args(argv)
+    p.add_argument("--topk", type=int, default=0,
+                   help="(MI355X build) after training write <out>/<runName>.topk: the K best items of every user, "
+                        "train items and item 0 excluded (neumf / aneumf; K <= 128; 0 = off)")
+    args = p.parse_args(argv)
+    if not 0 <= args.topk <= 128:
+        p.error("--topk must lie in [0, 128], got %d" % args.topk)
+    return args
+
+
+class AllNegatives:
+    """testNegatives of ``--eval all``, built on demand: ``[x]`` is the ascending list
+    of every item user x never trained on except 0 and the test item ([] for x = 0);
+    ``len`` is the number of user rows.  Nothing per user is kept."""
+
+    def __init__(self, seq, testRatings, num_users, num_items):
+        self._seq, self._tests, self._n, self._items = seq, testRatings, int(num_users), int(num_items)
+
+    def __len__(self):
+        return self._n
+
+    def __getitem__(self, x):
+        x = int(x)
+        if x < 0:
+            x += self._n
+        if not 0 <= x < self._n:
+            raise IndexError("user %d outside [0, %d)" % (x, self._n))
+        if x == 0:
+            return []
+        keep = np.ones(self._items, bool)
+        keep[0] = False
+        keep[np.asarray(self._seq.get(x, []), np.int64)] = False
+        keep[self._tests[x]] = False
+        return np.flatnonzero(keep).tolist()
 
 
 class RunDataset:
@@ -83,16 +115,10 @@ class RunDataset:
         self.trainSeq = seq
         tests = {int(k) + 1: int(t) + 1 for k, t in base.testRatings}
         self.testRatings = [None] + [tests.get(x, 0) for x in range(1, self.num_users)]
-        self.testNegatives = [[]] * self.num_users
         if eval_mode == "all":
-            every = np.arange(1, self.num_items)
-            for x in range(1, self.num_users):
-                keep = np.ones(self.num_items, bool)
-                keep[0] = False
-                keep[np.asarray(seq.get(x, []), np.int64)] = False
-                keep[self.testRatings[x]] = False
-                self.testNegatives[x] = every[keep[1:]].tolist()
+            self.testNegatives = AllNegatives(seq, self.testRatings, self.num_users, self.num_items)
         else:
+            self.testNegatives = [[]] * self.num_users
             random.seed(2019)
             cand = i.tolist()
             for x in range(1, self.num_users):
@@ -135,9 +161,12 @@ def make_ranker(name, uNum, iNum, dim, args, device=None):
 
 
 def main(argv=None, device=None):
-    from .evaluation import evaluate_model
+    from .evaluation import evaluate_model, evaluate_model_all
     from .train import prediction2file, write2file
     args = parse_args(argv)
+    if args.topk and args.model not in ("neumf", "aneumf"):
+        raise SystemExit(f"--topk: --model {args.model} has no recommend() on this driver "
+                         "(neumf, aneumf; the APR drivers run_adv.py / run_adv_ori.py have their own --topk)")
     path, opath, data, modelName, dim = args.path, args.opath, args.data, args.model, args.d
     batch_size, epochs, adv_epochs = args.bs, args.epochs, args.adv_epochs
     pre, evalMode, verbose_eval = args.pre, args.eval, args.verbose_eval
@@ -166,7 +195,15 @@ def main(argv=None, device=None):
     write2file(out, runName + ".out", runName)
     if pre != "":
         write2file(out, runName + ".out", pre)
-    hits, ndcgs = evaluate_model(ranker, testRatings, testNegatives, topK, 1)
+
+    def evaluate(model):
+        # --eval all on a ranker that ranks whole users on the GPU: one position per
+        # user, no negative lists and no pair array (the same hits / ndcgs)
+        if evalMode == "all" and hasattr(model, "positions_all"):
+            return evaluate_model_all(model, testRatings, train, topK)
+        return evaluate_model(model, testRatings, testNegatives, topK, 1)
+
+    hits, ndcgs = evaluate(ranker)
     hr, ndcg = np.array(hits).mean(), np.array(ndcgs).mean()
     write2file(out, runName + ".out", "Init: HR = %f, NDCG = %f" % (hr, ndcg))
     best_hr, best_ndcg, best_iter = hr, ndcg, -1
@@ -182,7 +219,7 @@ def main(argv=None, device=None):
         loss = ranker.train(x_train, y_train, batch_size)
         t2 = time()
         if epoch % verbose_eval == 0:
-            hits, ndcgs = evaluate_model(ranker, testRatings, testNegatives, topK, 1)
+            hits, ndcgs = evaluate(ranker)
             hr, ndcg = np.array(hits).mean(), np.array(ndcgs).mean()
         write2file(out, runName + ".out", "Iteration %d [%.1f s]: HR = %f, NDCG = %f, loss = %.4f [%.1f s]" % (
             epoch, t2 - t1, hr, ndcg, loss, time() - t2))
@@ -198,4 +235,10 @@ def main(argv=None, device=None):
             ranker.save(path + "h5/" + saveName + ".last.h5")
     write2file(out, runName + ".out", "End. Best Iteration %d:  HR = %.4f, NDCG = %.4f, Total time = %.2f" % (
         best_iter, best_hr, best_ndcg, (time() - start) / 3600))
-    return {"best_iter": best_iter, "best_hr": float(best_hr), "best_ndcg": float(best_ndcg), "runName": runName}
+    result = {"best_iter": best_iter, "best_hr": float(best_hr), "best_ndcg": float(best_ndcg), "runName": runName}
+    if args.topk:
+        from .cli import write_topk
+        items, _ = ranker.recommend(np.arange(1, uNum), args.topk, train)
+        write_topk(out, runName + ".topk", items)  # line n: user n + 1 (user 0 is the masking id)
+        result["topk"] = os.path.join(out, runName + ".topk")
+    return result

@@ -19,6 +19,7 @@
 #ifndef ACF_NEUMF_H
 #define ACF_NEUMF_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -102,6 +103,45 @@ int acf_neumf_train(acf_neumf_ctx* ctx, float* params, float* grad, float* m, fl
 /* ranker.rank(users, items) (MF.py:38-40): sigmoid scores of n (user, item) pairs. */
 int acf_neumf_predict(acf_neumf_ctx* ctx, const float* params, const int32_t* user,
                       const int32_t* item, int64_t n, float* scores, void* stream);
+
+/* All-items ranking: for each of n_users entries (row users[r]; any order, repeats
+ * allowed) the position of a test item among the user's candidates and / or the
+ * user's k best candidates, with no (user, item) pair list and no
+ * [n_users, num_candidates] score array.  No reference counterpart: the reference
+ * ranks explicit pair lists (evaluation.py:54-80).
+ * Candidates of entry r: [0, num_candidates) minus the SET of
+ * excl_items[excl_off[r] .. excl_off[r + 1]) -- a list may be unsorted, repeat
+ * items and hold entries outside the range (-1 included; they are ignored).
+ * 1 <= num_candidates <= num_item_rows.  excl_off == NULL: no exclusions.
+ * score(u, c) is the fp32 value acf_neumf_predict returns for the pair (u, c), bit
+ * for bit (the same MFMA k-order, c0 + c1 split, 16-lane head reduction and
+ * sigmoid), so positions and lists equal what the pair-list path gives.
+ *   positions[r] = #{candidates c : score(u, c) >= score(u, test_items[r])}
+ *     (int32 [n_users]; the caller puts the test item into the exclusion list, as
+ *     for acf_eval_positions_all; test_items[r] in [0, num_item_rows)).
+ *     test_items and positions are both NULL or both set.
+ *   out_items / out_scores ([n_users, k]): the first k candidates in the order
+ *     (score descending by float comparison, ties to the ascending item id); a user
+ *     with fewer than k candidates gets -1 / -inf in the tail.  0 <= k <= 128;
+ *     k == 0 (out_items and out_scores NULL) with positions is a pure evaluation
+ *     call; k == 0 without positions is ACF_E_INVALID.
+ * Exact and deterministic (identical bits run to run; no float atomics); entry
+ * r's outputs depend only on (users[r], its exclusion list, test_items[r], params),
+ * not on which other entries are in the call.  params is never written.
+ * workspace: acf_neumf_rank_all_workspace bytes (a host-only query; a smaller
+ * buffer is ACF_E_INVALID): k keys of 8 bytes per user and strip of the candidate
+ * range (strips of 4,096 to 32,768 candidates: one strip at 25,816 candidates once
+ * there are 1,024 users) plus 8 bytes per user -- 20.6 MB for 25,677 users x 25,816
+ * candidates at k = 100, where the score array would be 2.65 GB.
+ * A user or test item outside its table is ACF_E_RANGE, read from the context's
+ * error word at the end of the call (which therefore synchronises), as predict
+ * reports it.  Every dim a context accepts is served. */
+int acf_neumf_rank_all_workspace(int32_t n_users, int32_t num_candidates, int32_t k, size_t* bytes);
+int acf_neumf_rank_all(acf_neumf_ctx* ctx, const float* params, const int32_t* users, int32_t n_users,
+                       int32_t num_candidates, const int64_t* excl_off, const int32_t* excl_items,
+                       const int32_t* test_items, int32_t* positions, /* both NULL, or both set */
+                       int32_t k, int32_t* out_items, float* out_scores, /* k == 0: both NULL */
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Keras BPR (BPR.py:23-99): run.py --model bpr, BASELINE configs[0] ----
  * Parameters in one flat fp32 buffer [uEmb (num_user_rows x dim) | iEmb
