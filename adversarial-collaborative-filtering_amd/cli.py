@@ -72,6 +72,13 @@ def parse_args(argv=None, flavor="ori"):
                         "uids are keys of new users, not rows of the user table) and write their --topk best "
                         "items to <out>/<runName>.foldin.topk (rows in ascending uid order) and the uids to "
                         "<out>/<runName>.foldin.users.  Needs --topk.")
+    p.add_argument("--test_multi", type=str, default=None, metavar="FILE",
+                   help="After training, evaluate against SEVERAL held-out items per user: the rows of FILE "
+                        "(rating TSV: uid<TAB>item<TAB>...) are the users' test lists; writes "
+                        "<out>/<runName>.multi, one line name<TAB>value per metric (hit, recall, precision, "
+                        "ndcg, map at every --cutoffs K, then mrr, auc, n_users).")
+    p.add_argument("--cutoffs", type=parse_cutoffs, default=[10, 50, 100],
+                   help="The K of --test_multi's metrics: up to 8 integers in [1, 1024], comma separated.")
     args = p.parse_args(argv)
     if args.fold_in is not None and args.topk <= 0:
         p.error("--fold_in needs --topk K (K > 0)")
@@ -92,6 +99,48 @@ def parse_eps_list(text):
         if not v >= 0 or v == float("inf"):
             raise argparse.ArgumentTypeError(f"eps must be finite and >= 0, got {tok!r}")
         out.append(v)
+    return out
+
+
+def parse_cutoffs(text):
+    """"10,50,100" -> [10, 50, 100]: 1 to 8 integers in [1, 1024]."""
+    out = []
+    for tok in str(text).split(","):
+        tok = tok.strip()
+        if not tok:
+            continue
+        try:
+            v = int(tok)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"not an integer: {tok!r}")
+        if not 1 <= v <= 1024:
+            raise argparse.ArgumentTypeError(f"a cutoff must lie in [1, 1024], got {tok!r}")
+        out.append(v)
+    if not 1 <= len(out) <= 8:
+        raise argparse.ArgumentTypeError(f"1 to 8 cutoffs, got {len(out)}")
+    return out
+
+
+def write_multi(path, name, metrics, cutoffs):
+    """One line "name<TAB>value" per metric of evaluate.evaluate_multi, in
+    evaluate.metric_names order (floats by repr: the reader gets the same values back)."""
+    from .evaluate import metric_names
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, name), "w") as f:
+        for key in metric_names(cutoffs):
+            v = metrics[key]
+            f.write("%s\t%s\n" % (key, "%d" % v if key == "n_users" else repr(float(v))))
+
+
+def read_multi(file):
+    """The dict write_multi wrote (insertion order = file order; n_users an int)."""
+    out = {}
+    with open(file) as f:
+        for n, line in enumerate(f):
+            parts = line.rstrip("\n").split("\t")
+            if len(parts) != 2:
+                raise ValueError(f"{file}: line {n} has {len(parts)} fields, expected 2")
+            out[parts[0]] = int(parts[1]) if parts[0] == "n_users" else float(parts[1])
     return out
 
 
@@ -230,6 +279,12 @@ def main(argv=None, flavor="ori"):
         items, _ = recommend_new(final, lists, args.topk, seed=args.seed, batch=min(args.batch_size, 512))
         write_topk(out, runName + ".foldin.topk", items)
         write_fold_users(out, runName + ".foldin.users", sorted(lists))
+    if args.test_multi is not None:
+        from .data import load_test_lists
+        from .evaluate import evaluate_multi, init_eval_multi
+        final = amf if args.model == "apr" else m
+        plan = init_eval_multi(dataset, load_test_lists(args.test_multi))
+        write_multi(out, runName + ".multi", evaluate_multi(final, plan, args.cutoffs), args.cutoffs)
     if args.robust_eps:
         from .evaluate import init_eval_model, robustness
         final = amf if args.model == "apr" else m

@@ -38,6 +38,7 @@
 #include <rocprim/block/block_scan.hpp>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 
 #include <cstdarg>
@@ -3579,6 +3580,7 @@ __global__ void __launch_bounds__(256) k_forward(const float* __restrict__ P,
 #include "acf_eval.h"  // all-items evaluation (k_eval_*): DESIGN.md §4
 #include "acf_topk.h"  // top-K recommendation lists (k_topk_*): DESIGN.md §4b
 #include "acf_adv.h"   // whole-stream adversarial direction (k_adv_*): DESIGN.md §4c
+#include "acf_eval_multi.h"  // multi-item evaluation and rank metrics (k_evx_*): DESIGN.md §4f
 
 // ---------------------------------------------------------------------------
 // sampler (shuffle / _get_train_batch, APR.py:39-81)
@@ -5706,6 +5708,92 @@ extern "C" int acf_recommend_topk(const float* P, const float* Q, int64_t U1, in
   }
   HIP_TRY(hipGetLastError());
   k_topk_merge<<<(unsigned)n_users, 256, 0, s>>>(ws, S, k, out_items, out_scores);
+  HIP_TRY(hipGetLastError());
+  return ACF_OK;
+}
+
+// ---- multi-item evaluation (acf_eval_multi.h) ---------------------------------
+static int evx_check(int32_t n_users, int64_t n_tests, int32_t num_cand) {
+  ACF_CHECK(n_users >= 0 && n_tests >= 0, ACF_E_INVALID, "negative count");
+  ACF_CHECK(n_tests < ((int64_t)1 << 31), ACF_E_INVALID, "more than 2^31 - 1 test items");
+  ACF_CHECK(num_cand >= 1, ACF_E_INVALID, "num_candidates must be >= 1, got %d", num_cand);
+  return ACF_OK;
+}
+
+extern "C" int acf_eval_positions_multi_workspace(int32_t n_users, int64_t n_tests, int32_t num_cand,
+                                                  size_t* bytes) {
+  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
+  ACF_RET(evx_check(n_users, n_tests, num_cand));
+  *bytes = evx_workspace(n_users, n_tests, num_cand);
+  return ACF_OK;
+}
+
+extern "C" int acf_eval_positions_multi(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
+                                        const int32_t* users, const int64_t* test_off, const int32_t* test_items,
+                                        int32_t n_users, int64_t n_tests, int32_t num_cand, const int64_t* excl_off,
+                                        const int32_t* excl, int32_t* positions, void* workspace,
+                                        size_t workspace_bytes, int32_t check, void* stream_) {
+  ACF_RET(check_dim(d));
+  ACF_RET(evx_check(n_users, n_tests, num_cand));
+  ACF_CHECK(U1 > 0 && I1 > 0, ACF_E_INVALID, "empty table");
+  ACF_CHECK(num_cand <= I1, ACF_E_INVALID, "num_candidates %d > item rows", num_cand);
+  ACF_CHECK(P && Q && users && test_off && test_items && positions && workspace, ACF_E_INVALID, "NULL argument");
+  ACF_CHECK((excl_off == nullptr) == (excl == nullptr), ACF_E_INVALID, "excl_off and excl_items go together");
+  ACF_CHECK(reinterpret_cast<uintptr_t>(workspace) % 4 == 0, ACF_E_INVALID, "workspace must be 4-byte aligned");
+  const size_t need = evx_workspace(n_users, n_tests, num_cand);
+  ACF_CHECK(workspace_bytes >= need, ACF_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+  if (n_users == 0 || n_tests == 0) return ACF_OK;
+  int wper = 0, S = 0;
+  evx_strips(n_users, n_tests, num_cand, &wper, &S);
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  int32_t* err = static_cast<int32_t*>(workspace);
+  int32_t* part = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + EVX_WS_HEAD);
+  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+  const dim3 grid((unsigned)((n_users + EVX_UB - 1) / EVX_UB), (unsigned)S);
+  k_evx_sweep<<<grid, 256, (size_t)EVX_UB * d * sizeof(float), s>>>(P, Q, d, U1, I1, users, test_off, test_items,
+                                                                     n_users, n_tests, num_cand, excl_off, excl, wper,
+                                                                     S > 1 ? part : positions, err);
+  HIP_TRY(hipGetLastError());
+  if (S > 1) {
+    k_evx_sum<<<grid_for(n_tests), 256, 0, s>>>(part, S, n_tests, positions);
+    HIP_TRY(hipGetLastError());
+  }
+  if (check) {
+    int32_t herr = 0;
+    HIP_TRY(hipMemcpyAsync(&herr, err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    ACF_CHECK(herr == 0, ACF_E_RANGE, "index out of range (%s%s)", (herr & 1) ? "user >= num_user_rows " : "",
+              (herr & 2) ? "test item >= num_item_rows" : "");
+  }
+  return ACF_OK;
+}
+
+extern "C" int acf_eval_rank_metrics(const int32_t* positions, const int64_t* test_off, int32_t n_users,
+                                     const int32_t* n_neg, const int32_t* cutoffs, int32_t n_cutoffs,
+                                     double* per_user, double* per_user_free, double* mean_cut, double* mean_free,
+                                     int64_t* n_scored, void* stream_) {
+  ACF_CHECK(n_users >= 0, ACF_E_INVALID, "negative count");
+  ACF_CHECK(n_cutoffs >= 0 && n_cutoffs <= EVX_MAX_CUT, ACF_E_INVALID, "n_cutoffs %d outside [0, %d]", n_cutoffs,
+            EVX_MAX_CUT);
+  ACF_CHECK(cutoffs || n_cutoffs == 0, ACF_E_INVALID, "NULL argument");
+  EvxCuts cuts{};
+  cuts.n = n_cutoffs;
+  for (int c = 0; c < n_cutoffs; ++c) {
+    ACF_CHECK(cutoffs[c] >= 1 && cutoffs[c] <= EVX_MAX_K, ACF_E_INVALID, "cutoff %d outside [1, %d]", cutoffs[c],
+              EVX_MAX_K);
+    cuts.k[c] = cutoffs[c];
+  }
+  ACF_CHECK(test_off && mean_free && n_scored && (mean_cut || n_cutoffs == 0), ACF_E_INVALID, "NULL argument");
+  ACF_CHECK(n_users == 0 || (positions && n_neg && per_user_free && (per_user || n_cutoffs == 0)), ACF_E_INVALID,
+            "NULL argument");
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  if (n_users > 0) {
+    k_evx_metrics<<<(unsigned)n_users, 256, 0, s>>>(positions, test_off, n_neg, cuts, per_user, per_user_free);
+    HIP_TRY(hipGetLastError());
+  }
+  const int ncol = n_cutoffs * EVX_NM;
+  k_evx_means<<<(unsigned)(ncol + 2), 256, 0, s>>>(per_user, per_user_free, test_off, n_users, ncol, mean_cut,
+                                                   mean_free, n_scored);
   HIP_TRY(hipGetLastError());
   return ACF_OK;
 }

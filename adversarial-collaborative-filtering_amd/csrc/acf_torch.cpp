@@ -18,6 +18,8 @@
 //   acf::adv_direction         adv_update's direction over a whole triplet stream (utils.py:145-154)
 //   acf::adv_apply             delta = N * eps and W + delta (APR.py:130-141,190)
 //   acf::fold_in_users         rows for new users against a frozen Q (no reference counterpart)
+//   acf::eval_positions_multi  positions of several held-out items per user, one sweep per user
+//   acf::rank_metrics          hit / recall / precision / ndcg / map @K, mrr, auc of such positions (fp64)
 #include <torch/library.h>
 #include <ATen/ATen.h>
 // ROCm builds of PyTorch keep the "cuda" device type: the guard and stream
@@ -451,6 +453,85 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> fold_in_users(
   return {P_new, acc_new, loss};
 }
 
+// a CSR's offsets: int64 [n + 1] on `like`'s device, 0 = off[0] <= ... <= off[n] = total (read back once)
+void need_csr(const at::Tensor& off, const char* name, int64_t n, int64_t total, const at::Tensor& like) {
+  need(off, name, at::kLong, 1);
+  TORCH_CHECK(off.device() == like.device(), name, " must live on ", like.device());
+  TORCH_CHECK(off.numel() == n + 1, name, " must have ", n + 1, " entries, got ", off.numel());
+  const at::Tensor h = off.cpu();
+  const int64_t* o = h.data_ptr<int64_t>();
+  TORCH_CHECK(o[0] == 0 && o[n] == total, name, " must start at 0 and end at ", total);
+  for (int64_t r = 0; r < n; ++r) TORCH_CHECK(o[r] <= o[r + 1], name, " must be non-decreasing");
+}
+
+// positions of every test item of every entry's list (acf_eval_positions_multi).  users and
+// test items are range-checked here, before any gather; an exclusion list is a set and may
+// hold entries outside [0, num_candidates) (ignored).  Empty excl_off and excl_items: no exclusions.
+at::Tensor eval_positions_multi(const at::Tensor& P, const at::Tensor& Q, const at::Tensor& users_,
+                                const at::Tensor& test_off, const at::Tensor& test_items_, int64_t num_candidates,
+                                const at::Tensor& excl_off, const at::Tensor& excl_items_) {
+  need_table(P, "embedding_P", P);
+  need_table(Q, "embedding_Q", P);
+  TORCH_CHECK(P.size(1) == Q.size(1), "embedding_P and embedding_Q dims differ");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(P.device());
+  at::Tensor users = idx32(users_, "users", P), tests = idx32(test_items_, "test_items", P);
+  at::Tensor excl = idx32(excl_items_, "excl_items", P);
+  const int64_t n = users.numel(), T = tests.numel();
+  TORCH_CHECK(n < (1ll << 31) && T < (1ll << 31), "too many users or test items");
+  TORCH_CHECK(num_candidates >= 1 && num_candidates <= Q.size(0), "num_candidates must lie in [1, item rows]");
+  need_csr(test_off, "test_off", n, T, P);
+  const bool no_excl = excl_off.numel() == 0 && excl.numel() == 0;
+  if (!no_excl) need_csr(excl_off, "excl_off", n, excl.numel(), P);
+  check_range(users, P.size(0), "users");
+  check_range(tests, Q.size(0), "test_items");
+  if (excl.numel() == 0) excl = at::zeros({1}, users.options());
+  at::Tensor pos = at::empty({T}, users.options());
+  if (n == 0 || T == 0) return pos;
+  size_t ws = 0;
+  ok(acf_eval_positions_multi_workspace((int32_t)n, T, (int32_t)num_candidates, &ws),
+     "acf_eval_positions_multi_workspace");
+  at::Tensor work = at::empty({(int64_t)((ws + 3) / 4)}, users.options());
+  ok(acf_eval_positions_multi(P.data_ptr<float>(), Q.data_ptr<float>(), P.size(0), Q.size(0), (int32_t)P.size(1),
+                              users.data_ptr<int32_t>(), test_off.data_ptr<int64_t>(), tests.data_ptr<int32_t>(),
+                              (int32_t)n, T, (int32_t)num_candidates,
+                              no_excl ? nullptr : excl_off.data_ptr<int64_t>(),
+                              no_excl ? nullptr : excl.data_ptr<int32_t>(), pos.data_ptr<int32_t>(),
+                              work.data_ptr(), ws, 0, stream_of(P)),
+     "acf_eval_positions_multi");
+  return pos;
+}
+
+// (per_user [n, n_cut, 5], per_user_free [n, 2], mean_cut [n_cut, 5], mean_free [2], n_scored [1]) in fp64
+// (acf_eval_rank_metrics); columns: hit, recall, precision, ndcg, map / mrr, auc
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> rank_metrics(
+    const at::Tensor& positions, const at::Tensor& test_off, const at::Tensor& n_neg, at::IntArrayRef cutoffs) {
+  need(positions, "positions", at::kInt, 1);
+  need(n_neg, "n_neg", at::kInt, 1);
+  TORCH_CHECK(n_neg.device() == positions.device(), "n_neg must live on ", positions.device());
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(positions.device());
+  const int64_t n = n_neg.numel(), T = positions.numel(), nc = (int64_t)cutoffs.size();
+  TORCH_CHECK(n < (1ll << 31), "too many users");
+  TORCH_CHECK(nc <= 8, "at most 8 cutoffs, got ", nc);
+  int32_t cuts[8] = {0};
+  for (int64_t c = 0; c < nc; ++c) {
+    TORCH_CHECK(cutoffs[c] >= 1 && cutoffs[c] <= 1024, "a cutoff must lie in [1, 1024], got ", cutoffs[c]);
+    cuts[c] = (int32_t)cutoffs[c];
+  }
+  need_csr(test_off, "test_off", n, T, positions);
+  const auto f64 = positions.options().dtype(at::kDouble);
+  at::Tensor per_user = at::empty({n, nc, 5}, f64), per_free = at::empty({n, 2}, f64);
+  at::Tensor mean_cut = at::empty({nc, 5}, f64), mean_free = at::empty({2}, f64);
+  at::Tensor n_scored = at::empty({1}, positions.options().dtype(at::kLong));
+  const at::Tensor pos = T ? positions : at::zeros({1}, positions.options());  // never read, never NULL
+  ok(acf_eval_rank_metrics(pos.data_ptr<int32_t>(), test_off.data_ptr<int64_t>(), (int32_t)n,
+                           n ? n_neg.data_ptr<int32_t>() : nullptr, cuts, (int32_t)nc,
+                           n && nc ? per_user.data_ptr<double>() : nullptr, n ? per_free.data_ptr<double>() : nullptr,
+                           nc ? mean_cut.data_ptr<double>() : nullptr, mean_free.data_ptr<double>(),
+                           n_scored.data_ptr<int64_t>(), stream_of(positions)),
+     "acf_eval_rank_metrics");
+  return {per_user, per_free, mean_cut, mean_free, n_scored};
+}
+
 }  // namespace
 
 #ifndef ACF_BUILD_HASH
@@ -485,6 +566,10 @@ TORCH_LIBRARY(acf, m) {
   m.def("fold_in_users(Tensor Q, Tensor user_off, Tensor item_pos, Tensor item_neg, int epochs, int batch=512, "
         "Tensor? init=None, Tensor? acc_init=None, float lr=0.05, float eps=0.5, float reg=0., float reg_adv=1., "
         "bool adver=True, float clip_lo=-80., float clip_hi=100000000.) -> (Tensor P_new, Tensor acc_new, Tensor loss)");
+  m.def("eval_positions_multi(Tensor P, Tensor Q, Tensor users, Tensor test_off, Tensor test_items, "
+        "int num_candidates, Tensor excl_off, Tensor excl_items) -> Tensor");
+  m.def("rank_metrics(Tensor positions, Tensor test_off, Tensor n_neg, int[] cutoffs) -> "
+        "(Tensor per_user, Tensor per_user_free, Tensor mean_cut, Tensor mean_free, Tensor n_scored)");
 }
 
 TORCH_LIBRARY_IMPL(acf, CUDA, m) {
@@ -500,4 +585,6 @@ TORCH_LIBRARY_IMPL(acf, CUDA, m) {
   m.impl("adv_direction", &adv_direction);
   m.impl("adv_apply", &adv_apply);
   m.impl("fold_in_users", &fold_in_users);
+  m.impl("eval_positions_multi", &eval_positions_multi);
+  m.impl("rank_metrics", &rank_metrics);
 }

@@ -300,3 +300,26 @@ def get_dataset(name: str, path: str = "", seed: int = 2019):
         return synthetic_dataset(int(U), int(I), int(N), seed=seed)
     prefix = os.path.join(path, "data", name) if not os.path.exists(name + ".train.rating") else name
     return OriginalDataset(prefix)
+
+
+def load_test_lists(path: str) -> dict:
+    """{uid: [items]} of a rating file ("uid<TAB>item[<TAB>...]", ids possibly
+    written as floats): every row of a uid goes to that user's test list, in file
+    order, repeats kept (evaluate.init_eval_multi drops them)."""
+    lists: dict = {}
+    with open(path) as f:
+        for n, line in enumerate(f):
+            line = line.strip()
+            if not line:
+                continue
+            parts = line.split("\t")
+            if len(parts) < 2:
+                raise ValueError(f"{path}: line {n} has {len(parts)} field(s), expected uid<TAB>item")
+            try:
+                uid, item = float(parts[0]), float(parts[1])
+            except ValueError:
+                raise ValueError(f"{path}: line {n}: uid and item must be numbers") from None
+            if uid != int(uid) or item != int(item) or uid < 0 or item < 0:
+                raise ValueError(f"{path}: line {n}: uid and item must be integers >= 0")
+            lists.setdefault(int(uid), []).append(int(item))
+    return lists

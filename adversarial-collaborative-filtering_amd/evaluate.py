@@ -350,3 +350,165 @@ def recommend_new(model_or_tables, lists, k: int, **fold_args):
     users = torch.arange(len(f), dtype=torch.int32, device=Q.device)
     items, scores = ops.recommend_topk(f.P, Q, users, int(k), n_items, excl_off=f.user_off, excl_items=f.item_pos)
     return items.cpu().numpy(), scores.cpu().numpy()
+
+
+# ---- several held-out items per user ----------------------------------------
+CUT_METRICS = ("hit", "recall", "precision", "ndcg", "map")  # ops.RANK_CUT_METRICS
+FREE_METRICS = ("mrr", "auc")                                # ops.RANK_FREE_METRICS
+
+
+def metrics_from_positions_multi(pos, test_off, n_neg, cutoffs):
+    """Ranking metrics of the positions of several test items per user, in fp64
+    on the host: the yardstick of ops.rank_metrics.  User u owns
+    pos[test_off[u]:test_off[u+1]]; sorted ascending they are r_0 <= ... <=
+    r_{m-1} (ties: the smaller index first).  Per cutoff K
+      hit = [r_0 < K]      recall = #{r_j < K} / m      precision = #{r_j < K} / K
+      ndcg = sum_{r_j<K} 1/log2(r_j + 2) / sum_{i<min(m,K)} 1/log2(i + 2)
+      map = sum_{r_j<K} (j + 1)/(r_j + 1) / min(m, K)
+    and mrr = 1/(r_0 + 1), auc = (1/m) sum_j (1 - (r_j - j)/n_neg[u]).  They
+    assume that every test item is a candidate and that a list holds no item
+    twice: then r_j - j is the number of non-test candidates ahead of item j and
+    n_neg[u] the number of non-test candidates.  Returns a dict: per_user
+    [n, n_cut, 5] (CUT_METRICS order), per_user_free [n, 2] (FREE_METRICS order),
+    mean_cut [n_cut, 5] and mean_free [2] over the users with m > 0 (zeros when
+    there is none), n_scored."""
+    pos = np.asarray(pos, dtype=np.int64).reshape(-1)
+    off = np.asarray(test_off, dtype=np.int64).reshape(-1)
+    nn = np.asarray(n_neg, dtype=np.float64).reshape(-1)
+    ks = [int(k) for k in cutoffs]
+    n = len(off) - 1
+    per_user = np.zeros((n, len(ks), 5), dtype=np.float64)
+    free = np.zeros((n, 2), dtype=np.float64)
+    scored = np.zeros(n, dtype=bool)
+    for u in range(n):
+        r = np.sort(pos[off[u]:off[u + 1]], kind="stable").astype(np.float64)
+        m = len(r)
+        if m == 0:
+            continue
+        scored[u] = True
+        j = np.arange(m, dtype=np.float64)
+        free[u, 0] = 1.0 / (r[0] + 1.0)
+        free[u, 1] = float(np.sum(1.0 - (r - j) / nn[u])) / m
+        disc = 1.0 / np.log2(r + 2.0)
+        prec = (j + 1.0) / (r + 1.0)
+        for c, K in enumerate(ks):
+            inside = r < K
+            top = min(m, K)
+            idcg = float(np.sum(1.0 / np.log2(np.arange(top, dtype=np.float64) + 2.0)))
+            cnt = float(inside.sum())
+            per_user[u, c] = (float(r[0] < K), cnt / m, cnt / K, float(disc[inside].sum()) / idcg,
+                              float(prec[inside].sum()) / top)
+    ns = int(scored.sum())
+    mean_cut = per_user[scored].sum(axis=0) / ns if ns else np.zeros((len(ks), 5))
+    mean_free = free[scored].sum(axis=0) / ns if ns else np.zeros(2)
+    return {"per_user": per_user, "per_user_free": free, "mean_cut": mean_cut, "mean_free": mean_free,
+            "n_scored": ns}
+
+
+class MultiEvalPlan:
+    """What init_eval_multi returns (numpy): users int64 [n]; the test lists as a
+    CSR test_off int64 [n + 1] / test_items int32 (duplicates dropped, first
+    occurrence kept); the exclusions excl_off / excl (sorted train items minus the
+    user's test items); n_neg int32 [n], the candidates that are not test items;
+    num_candidates."""
+
+    def __init__(self, users, test_off, test_items, excl_off, excl, n_neg, num_candidates):
+        self.users, self.test_off, self.test_items = users, test_off, test_items
+        self.excl_off, self.excl, self.n_neg, self.num_candidates = excl_off, excl, n_neg, num_candidates
+        self._dev = {}
+
+    def device_arrays(self, device):
+        import torch
+        key = str(device)
+        if key not in self._dev:
+            T = lambda a, dt: torch.as_tensor(a, dtype=dt, device=device)  # noqa: E731
+            self._dev[key] = (T(self.users, torch.int32), T(self.test_off, torch.int64),
+                              T(self.test_items, torch.int32), T(self.excl_off, torch.int64),
+                              T(self.excl, torch.int32), T(self.n_neg, torch.int32))
+        return self._dev[key]
+
+
+def init_eval_multi(dataset, test_lists, users=None) -> MultiEvalPlan:
+    """The plan of an all-items evaluation against several held-out items per
+    user.  test_lists: a dict user -> items (users: default its keys ascending) or
+    a list of lists (users: default 0..n-1; with `users`, the list of users[k] is
+    test_lists[k]).  A user missing from a dict has an empty list and is not
+    scored.  Duplicates within a list are dropped, the first occurrence kept;
+    items must lie in [0, dataset.num_items).  The candidates of a user are all
+    items minus its sorted train items that are not test items, so every test
+    item is a candidate; n_neg = the candidates that are not test items (>= 1:
+    ValueError otherwise).  Pure numpy."""
+    n_items = int(dataset.num_items)
+    if isinstance(test_lists, dict):
+        if users is None:
+            users = sorted(test_lists)
+        rows = [test_lists.get(int(u), ()) for u in users]
+    else:
+        rows = list(test_lists)
+        if users is None:
+            users = range(len(rows))
+    users = np.asarray(list(users), dtype=np.int64).reshape(-1)
+    if len(rows) != len(users):
+        raise ValueError(f"{len(rows)} test lists for {len(users)} users")
+    if len(users) and (users.min() < 0 or users.max() >= dataset.num_users):
+        raise ValueError(f"a user is outside [0, {dataset.num_users})")
+    soff, sitems = dataset.sorted_lists()
+    tests, excls = [], []
+    n_neg = np.zeros(len(users), dtype=np.int32)
+    for k, (u, row) in enumerate(zip(users.tolist(), rows)):
+        a = np.asarray(list(row) if not isinstance(row, np.ndarray) else row).reshape(-1)
+        if a.size and a.dtype.kind not in "iu":
+            raise ValueError(f"test list of user {u}: items must be integers")
+        a = a.astype(np.int64)
+        if a.size and (a.min() < 0 or a.max() >= n_items):
+            raise ValueError(f"test list of user {u}: item outside [0, {n_items})")
+        _, first = np.unique(a, return_index=True)
+        t = a[np.sort(first)].astype(np.int32)
+        tl = sitems[soff[u]:soff[u + 1]] if u < len(soff) - 1 else np.zeros(0, np.int32)
+        ex = np.setdiff1d(tl[(tl >= 0) & (tl < n_items)], t).astype(np.int32)
+        n_neg[k] = n_items - len(ex) - len(t)
+        if n_neg[k] < 1:
+            raise ValueError(f"user {u} has no candidate besides its test items")
+        tests.append(t)
+        excls.append(ex)
+    to = np.zeros(len(users) + 1, dtype=np.int64)
+    np.cumsum([len(t) for t in tests], out=to[1:])
+    eo = np.zeros(len(users) + 1, dtype=np.int64)
+    np.cumsum([len(e) for e in excls], out=eo[1:])
+    cat = lambda xs: np.concatenate(xs).astype(np.int32) if xs else np.zeros(0, np.int32)  # noqa: E731
+    return MultiEvalPlan(users, to, cat(tests), eo, cat(excls), n_neg, n_items)
+
+
+def metric_names(cutoffs):
+    """The keys of evaluate_multi's dict, in the order of the .multi file."""
+    return [f"{m}@{int(k)}" for k in cutoffs for m in CUT_METRICS] + list(FREE_METRICS) + ["n_users"]
+
+
+def evaluate_multi(model_or_tables, plan: MultiEvalPlan, cutoffs=(10, 50, 100), raw: bool = False):
+    """Recall / NDCG / MAP / precision / hit @K, MRR and AUC against the plan's
+    test lists, positions and metrics both on the GPU (ops.eval_positions_multi:
+    one candidate sweep per user; ops.rank_metrics): {"hit@10": ..., "recall@10":
+    ..., ..., "mrr": ..., "auc": ..., "n_users": the users scored}, means over the
+    users with a non-empty list.  raw=True: (that dict, {"positions",
+    "per_user", "per_user_free"} as numpy arrays).  model_or_tables: an MF (or
+    anything with embedding_P / embedding_Q) or a (P, Q) pair of device tensors."""
+    if hasattr(model_or_tables, "embedding_P"):
+        P, Q = model_or_tables.embedding_P, model_or_tables.embedding_Q
+    else:
+        P, Q = model_or_tables[0], model_or_tables[1]
+    cutoffs = tuple(int(k) for k in cutoffs)
+    u, to, t, eo, ex, nn = plan.device_arrays(P.device)
+    pos = ops.eval_positions_multi(P, Q, u, to, t, int(plan.num_candidates), eo, ex)
+    rm = ops.rank_metrics(pos, to, nn, cutoffs)
+    mean_cut, mean_free = rm.mean_cut.cpu().numpy(), rm.mean_free.cpu().numpy()
+    out = {}
+    for c, k in enumerate(cutoffs):
+        for q, name in enumerate(CUT_METRICS):
+            out[f"{name}@{k}"] = float(mean_cut[c, q])
+    for q, name in enumerate(FREE_METRICS):
+        out[name] = float(mean_free[q])
+    out["n_users"] = int(rm.n_scored.item())
+    if raw:
+        return out, {"positions": pos.cpu().numpy(), "per_user": rm.per_user.cpu().numpy(),
+                     "per_user_free": rm.per_user_free.cpu().numpy()}
+    return out

@@ -217,6 +217,12 @@ class MF:
         from .evaluate import recommend_new
         return recommend_new(self, lists, k, **fold_args)
 
+    def evaluate_multi(self, plan, cutoffs=(10, 50, 100), raw=False):
+        """evaluate.evaluate_multi: recall / ndcg / map / ... @K, mrr and auc against
+        several held-out items per user (plan: evaluate.init_eval_multi)."""
+        from .evaluate import evaluate_multi
+        return evaluate_multi(self, plan, cutoffs=cutoffs, raw=raw)
+
     def adv_update(self, train_batches, adv=None):
         """train.adv_update: delta_P / delta_Q over all the triplets as one batch."""
         from .train import adv_update

@@ -742,6 +742,176 @@ def recommend_topk(P, Q, users, k: int, num_candidates: int | None = None, excl_
     return items, scores
 
 
+RANK_MAX_CUTOFFS, RANK_MAX_K = 8, 1024          # EVX_MAX_CUT, EVX_MAX_K
+RANK_CUT_METRICS = ("hit", "recall", "precision", "ndcg", "map")
+RANK_FREE_METRICS = ("mrr", "auc")
+
+_CSR_OK: dict = {}  # as _RANGE_OK, for offset tensors that passed _csr_offsets
+
+
+def _csr_offsets(off, n_rows: int, n_items: int, name: str) -> torch.Tensor:
+    """`off` as a tensor (where it is) after the CSR checks (ValueError): 1-D
+    integers, n_rows + 1 entries, off[0] = 0, non-decreasing, off[-1] = n_items.
+    A host array is checked on the host; a device tensor is checked on the device
+    (one read-back, remembered like _check_range's)."""
+    import numpy as np
+    if not isinstance(off, torch.Tensor):
+        off = np.asarray(off)
+        if off.dtype.kind not in "iu":
+            raise ValueError(f"{name} must be an integer array, got {off.dtype}")
+        off = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64))
+    if off.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name} must be an integer array, got {off.dtype}")
+    if off.dim() != 1 or off.numel() != n_rows + 1:
+        raise ValueError(f"{name} must be 1-D with {n_rows + 1} entries, got shape {tuple(off.shape)}")
+    key = (off.data_ptr(), off.numel(), off._version, n_items, off.device, off.dtype)
+    ref = _CSR_OK.get(key)
+    if not (off.is_cuda and ref is not None and ref() is off):
+        bad = torch.stack([off[0] != 0, (off[1:] < off[:-1]).any(), off[-1] != n_items]).tolist()
+        if bad[0]:
+            raise ValueError(f"{name}[0] must be 0, got {int(off[0])}")
+        if bad[1]:
+            raise ValueError(f"{name} must be non-decreasing")
+        if bad[2]:
+            raise ValueError(f"{name}[-1] must be {n_items}, got {int(off[-1])}")
+        if off.is_cuda:
+            def _evict(r, k=key):
+                if _CSR_OK.get(k) is r:
+                    del _CSR_OK[k]
+            _CSR_OK[key] = weakref.ref(off, _evict)
+    return off
+
+
+def _csr_items(t, name: str) -> torch.Tensor:
+    """A flat int32 / int64 item array as a (host or device) tensor (ValueError)."""
+    if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(t)
+    if t.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name} must be int32 or int64, got {t.dtype}")
+    if t.dim() != 1:
+        raise ValueError(f"{name} must be 1-D, got shape {tuple(t.shape)}")
+    return t
+
+
+def eval_positions_multi_workspace(n_users: int, n_tests: int, num_candidates: int) -> int:
+    """Bytes of device workspace acf_eval_positions_multi needs (a host-only query)."""
+    size = ctypes.c_size_t()
+    call("acf_eval_positions_multi_workspace", int(n_users), int(n_tests), int(num_candidates), ctypes.byref(size))
+    return int(size.value)
+
+
+def eval_positions_multi(P, Q, users, test_off, test_items, num_candidates: int, excl_off=None, excl_items=None,
+                         check: bool = True):
+    """Positions of SEVERAL held-out items per entry, one candidate sweep per
+    entry whatever the length of its list (acf_eval_positions_multi): int32
+    [len(test_items)].  Entry r is row users[r] of P with the test list
+    test_items[test_off[r]:test_off[r+1]] (CSR) and the candidates
+    [0, num_candidates) minus the SET of excl_items[excl_off[r]:excl_off[r+1]]
+    (unsorted, repeated and out-of-range entries are fine; no exclusion
+    arguments: nothing is excluded).  positions[x] = the number of candidates
+    other than test_items[x] that score >= it, by the evaluation's sequential dot
+    product: the same integers as eval_positions_all on the entry repeated once
+    per item with that item added to its exclusions.  The other test items stay
+    candidates unless excluded.  Bad shapes and dtypes raise ValueError /
+    TypeError before any native call; with check, a user or test item outside
+    its table raises NativeIndexError (one sync)."""
+    ti = _csr_items(test_items, "test_items")
+    us = _csr_items(users, "users")
+    n, T = us.numel(), ti.numel()
+    if (excl_off is None) != (excl_items is None):
+        raise ValueError("excl_off and excl_items go together")
+    ex = None if excl_items is None else _csr_items(excl_items, "excl_items")
+    if isinstance(num_candidates, bool) or not isinstance(num_candidates, int) or num_candidates < 1:
+        raise ValueError(f"num_candidates must be an int >= 1, got {num_candidates!r}")
+    for tab, name in ((P, "embedding_P"), (Q, "embedding_Q")):
+        if not isinstance(tab, torch.Tensor) or tab.dtype != torch.float32 or tab.dim() != 2:
+            raise TypeError(f"{name} must be a 2-D torch.float32 tensor")
+    if P.shape[1] != Q.shape[1]:
+        raise ValueError("embedding_P and embedding_Q dims differ")
+    if num_candidates > Q.shape[0]:
+        raise ValueError("num_candidates exceeds item rows")
+    toff = _csr_offsets(test_off, n, T, "test_off")
+    eoff = None if ex is None else _csr_offsets(excl_off, n, ex.numel(), "excl_off")
+    _require(P, "embedding_P", torch.float32, None, 2)
+    dev = P.device
+    _require(Q, "embedding_Q", torch.float32, dev, 2)
+    toff = toff.to(device=dev, dtype=torch.int64).contiguous()
+    eoff = None if eoff is None else eoff.to(device=dev, dtype=torch.int64).contiguous()
+    settle_tables()
+    u = us.to(device=dev, dtype=torch.int32).contiguous()
+    t = ti.to(device=dev, dtype=torch.int32).contiguous()
+    if ex is not None:
+        ex = (ex.to(device=dev, dtype=torch.int32).contiguous() if ex.numel()
+              else torch.zeros(1, dtype=torch.int32, device=dev))
+    pos = torch.empty(T, dtype=torch.int32, device=dev)
+    if n == 0 or T == 0:
+        return pos
+    nbytes = eval_positions_multi_workspace(n, T, num_candidates)
+    work = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+    with _on(dev):
+        call("acf_eval_positions_multi", P.data_ptr(), Q.data_ptr(), P.shape[0], Q.shape[0], P.shape[1],
+             u.data_ptr(), toff.data_ptr(), t.data_ptr(), n, T, num_candidates,
+             eoff.data_ptr() if eoff is not None else None, ex.data_ptr() if ex is not None else None,
+             pos.data_ptr(), work.data_ptr(), nbytes, int(bool(check)), _stream_ptr(dev))
+    return pos
+
+
+@dataclass
+class RankMetrics:
+    """What rank_metrics returns (device tensors, fp64 unless noted): per_user
+    [n, n_cut, 5] in RANK_CUT_METRICS order, per_user_free [n, 2] in
+    RANK_FREE_METRICS order, their means over the users with a non-empty list
+    mean_cut [n_cut, 5] / mean_free [2], and n_scored (int64 [1]), their number."""
+    cutoffs: tuple
+    per_user: torch.Tensor
+    per_user_free: torch.Tensor
+    mean_cut: torch.Tensor
+    mean_free: torch.Tensor
+    n_scored: torch.Tensor
+
+
+def _cutoffs(cutoffs) -> tuple:
+    try:
+        ks = tuple(cutoffs)
+    except TypeError:
+        raise ValueError(f"cutoffs must be a sequence of ints, got {cutoffs!r}") from None
+    if len(ks) > RANK_MAX_CUTOFFS:
+        raise ValueError(f"at most {RANK_MAX_CUTOFFS} cutoffs, got {len(ks)}")
+    for k in ks:
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= RANK_MAX_K:
+            raise ValueError(f"a cutoff must be an int in [1, {RANK_MAX_K}], got {k!r}")
+    return ks
+
+
+def rank_metrics(positions, test_off, n_neg, cutoffs) -> RankMetrics:
+    """Ranking metrics of eval_positions_multi's positions, reduced on the device
+    in fp64 (acf_eval_rank_metrics; definitions in include/acf_apr.h and
+    evaluate.metrics_from_positions_multi, the host yardstick).  positions int32
+    [T] and n_neg int32 [n] (>= 1: the user's candidates that are not test items)
+    are device tensors, test_off the lists' CSR offsets [n + 1], cutoffs up to 8
+    ints in [1, 1024].  Deterministic: equal inputs give equal bits."""
+    ks = _cutoffs(cutoffs)
+    _require(positions, "positions", torch.int32, None, 1)
+    dev = positions.device
+    _require(n_neg, "n_neg", torch.int32, dev, 1)
+    n, T = n_neg.numel(), positions.numel()
+    toff = _csr_offsets(test_off, n, T, "test_off").to(device=dev, dtype=torch.int64).contiguous()
+    nc = len(ks)
+    out = RankMetrics(ks, torch.empty((n, nc, 5), dtype=torch.float64, device=dev),
+                      torch.empty((n, 2), dtype=torch.float64, device=dev),
+                      torch.empty((nc, 5), dtype=torch.float64, device=dev),
+                      torch.empty(2, dtype=torch.float64, device=dev),
+                      torch.empty(1, dtype=torch.int64, device=dev))
+    cuts = (ctypes.c_int32 * max(nc, 1))(*ks)
+    if T == 0:  # every list is empty: nothing is read, but the pointer must not be NULL
+        positions = torch.zeros(1, dtype=torch.int32, device=dev)
+    with _on(dev):
+        call("acf_eval_rank_metrics", positions.data_ptr(), toff.data_ptr(), n, n_neg.data_ptr(), cuts, nc,
+             out.per_user.data_ptr(), out.per_user_free.data_ptr(), out.mean_cut.data_ptr(),
+             out.mean_free.data_ptr(), out.n_scored.data_ptr(), _stream_ptr(dev))
+    return out
+
+
 ADV_MODES = {"grad": 0, "random": 1}
 ADV_MAX_TRIPLETS = (1 << 29) - 1
 

@@ -171,6 +171,12 @@ class APR(Recommender):
         fold_args.setdefault("num_items", self.iNum)
         return self.model.recommend_new(self._new_lists(train), k, **fold_args)
 
+    def evaluate_multi(self, plan, cutoffs=(10, 50, 100), raw=False):
+        """evaluate.evaluate_multi against the test lists of `plan`
+        (evaluate.init_eval_multi): a dict of recall / ndcg / map / ... @K, mrr, auc."""
+        self._ensure()
+        return self.model.evaluate_multi(plan, cutoffs=cutoffs, raw=raw)
+
     def adv_update(self, x_train, adv=None):
         """train.adv_update on the triplets of get_train_instances: the model's
         delta_P / delta_Q over all of them as one batch."""

@@ -25,6 +25,12 @@ SURVEY.md §8(b) proposes:
   of the items (``check=1``: a small stream-ordered allocation, one kernel and a stream
   synchronise before the fold-in launch).  Use ``ops.fold_in_users(..., check=False)`` with a
   host ``user_off`` for a call that stays asynchronous;
+- ``eval_positions_multi(P, Q, users, test_off, test_items, num_candidates, excl_off, excl_items)
+  -> positions`` and ``rank_metrics(positions, test_off, n_neg, cutoffs) -> (per_user,
+  per_user_free, mean_cut, mean_free, n_scored)``: evaluation against several held-out items
+  per user (``ops.eval_positions_multi`` / ``ops.rank_metrics``, the same values).  Both copy
+  their CSR offsets back to validate them, and the positions op checks users and test items
+  before any gather; empty ``excl_off`` and ``excl_items`` exclude nothing;
 - ``release_contexts() -> int``: frees the cached step contexts (plan workspace and
   the streamed step's version buffers) that ``apr_train`` / ``bpr_apr_step`` keep per
   (device, table shape, batch shape).
@@ -43,7 +49,7 @@ from . import build_native
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libacf_torch.so")
 OPS = ("bpr_apr_step", "apr_train", "gather_bpr_fwd_bwd", "row_segment_sum", "l2norm_perturb",
        "sparse_adagrad_apply", "score_rank", "score_rank_all", "recommend_topk", "adv_direction", "adv_apply",
-       "fold_in_users", "release_contexts")
+       "fold_in_users", "eval_positions_multi", "rank_metrics", "release_contexts")
 _lock = threading.Lock()
 _loaded = False
 

@@ -375,6 +375,67 @@ int acf_recommend_topk(const float* P, const float* Q, int64_t num_user_rows, in
                        int32_t* out_items, float* out_scores, void* workspace, size_t workspace_bytes,
                        int32_t kernel, void* stream);
 
+/* ---- evaluation against several held-out items per user --------------------
+ * (no reference counterpart: the reference holds out one item per user.)
+ * Entry r (row users[r] of P; any order, repeats allowed) has the test list
+ * test_items[test_off[r] .. test_off[r+1]) (test_off: int64 [n_users + 1],
+ * non-decreasing within [0, n_tests]; offsets outside are clamped) and the
+ * candidates C_r = [0, num_candidates) minus the SET of
+ * excl_items[excl_off[r] .. excl_off[r+1]) -- unsorted, repeated and
+ * out-of-range entries (-1 included) are fine, as for acf_recommend_topk;
+ * excl_off = excl_items = NULL excludes nothing.  For every x of r's list with
+ * t = test_items[x]:
+ *   positions[x] = #{ c in C_r, c != t : score(u,c) >= score(u,t) }
+ * with the evaluation's sequential round-then-add dot product, so ties are
+ * decided on equal bits exactly as by acf_eval_positions_all.  The other test
+ * items of the list stay candidates unless the caller excluded them; t itself
+ * never counts, excluded or not; a repeated test item gets the same position
+ * each time; an empty list writes nothing.  A position depends on (u, t, C_r,
+ * P, Q) only: not on the list's other items, not on the other entries.
+ * The candidates are swept once per (entry, chunk of 256 test items, strip of
+ * the candidate range), whatever the length of a list.  Exact integers,
+ * identical bits run to run; no [n_users, num_candidates] array is formed.
+ * `workspace`: device memory, 4-byte aligned, at least
+ * acf_eval_positions_multi_workspace(n_users, n_tests, num_candidates) bytes --
+ * a host-only query that touches no device; a smaller one is ACF_E_INVALID.
+ * 1 <= num_candidates <= num_item_rows; 0 <= n_tests < 2^31.
+ * A user outside [0, num_user_rows) or a test item outside [0, num_item_rows)
+ * is read as row 0; with check != 0 the call then synchronises once, after its
+ * launches, and returns ACF_E_RANGE (check == 0: no error, no sync). */
+int acf_eval_positions_multi_workspace(int32_t n_users, int64_t n_tests, int32_t num_candidates,
+                                       size_t* bytes);
+int acf_eval_positions_multi(const float* P, const float* Q, int64_t num_user_rows, int64_t num_item_rows,
+                             int32_t dim, const int32_t* users, const int64_t* test_off,
+                             const int32_t* test_items, int32_t n_users, int64_t n_tests,
+                             int32_t num_candidates, const int64_t* excl_off, const int32_t* excl_items,
+                             int32_t* positions, void* workspace, size_t workspace_bytes, int32_t check,
+                             void* stream);
+
+/* Ranking metrics of such positions, reduced on the device in fp64.  User u's
+ * m = test_off[u+1] - test_off[u] positions sorted ascending are r_0 <= ... <=
+ * r_{m-1}; item x's j is the number of the user's entries with a smaller
+ * position, or an equal position and a smaller index (exact for any m).
+ * n_neg[u] >= 1 (device int32): the user's candidates that are not test items.
+ * cutoffs: a HOST array of n_cutoffs <= 8 values K in [1, 1024].  Per user and
+ * cutoff, per_user [n_users][n_cutoffs][5] (device fp64) =
+ *   hit       [r_0 < K]
+ *   recall    #{j : r_j < K} / m
+ *   precision #{j : r_j < K} / K
+ *   ndcg      sum_{r_j < K} 1/log2(r_j + 2)  /  sum_{i < min(m,K)} 1/log2(i + 2)
+ *   map       sum_{r_j < K} (j + 1)/(r_j + 1)  /  min(m, K)
+ * and per_user_free [n_users][2] = mrr 1/(r_0 + 1), auc (1/m) sum_j (1 - (r_j -
+ * j)/n_neg); a user with m = 0 gets zeros.  mean_cut [n_cutoffs][5] and
+ * mean_free [2]: the means over the users with m > 0 (zeros when there is
+ * none); n_scored (device int64): their number.  Pure functions of the integer
+ * positions; they assume that every test item is a candidate and that a list
+ * holds no item twice (then r_j - j is the number of non-test candidates ahead
+ * of the item).  Every sum is taken in a fixed order (no float atomics): equal
+ * inputs give equal bits.  Asynchronous on `stream`. */
+int acf_eval_rank_metrics(const int32_t* positions, const int64_t* test_off, int32_t n_users,
+                          const int32_t* n_neg, const int32_t* cutoffs, int32_t n_cutoffs,
+                          double* per_user, double* per_user_free, double* mean_cut, double* mean_free,
+                          int64_t* n_scored, void* stream);
+
 /* ---- robustness evaluation: a whole-stream adversarial direction ------------
  * utils.py:145-154 (adv_update): ONE delta over all n triplets as one batch, as
  * dense tables.  acf_adv_direction fills EVERY row of the unit-direction tables
