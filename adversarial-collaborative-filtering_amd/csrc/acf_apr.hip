@@ -3577,6 +3577,7 @@ __global__ void __launch_bounds__(256) k_forward(const float* __restrict__ P,
   }
 }
 
+#include "acf_sweep.h"  // seq_dot and the score sweep the ranking kernels share: DESIGN.md §4
 #include "acf_eval.h"  // all-items evaluation (k_eval_*): DESIGN.md §4
 #include "acf_topk.h"  // top-K recommendation lists (k_topk_*): DESIGN.md §4b
 #include "acf_adv.h"   // whole-stream adversarial direction (k_adv_*): DESIGN.md §4c
@@ -5603,8 +5604,8 @@ static int eval_positions_all(const float* P, const float* Q, int64_t U1, int64_
   HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&tscore), (size_t)n_users * sizeof(float), s));
   k_eval_tscore<<<grid_for(n_users), 256, 0, s>>>(P, Q, d, users, tests, n_users, tscore, positions);
   if (num_cand > 0) {
-    const float eb = 4.0f * (float)(d + 2) * 5.9604645e-8f;  // 4 (d + 2) 2^-24
-    const float floor_e = (float)d * 1.1754944e-38f * 4.0f;   // denormal products flushed by MFMA
+    float eb, floor_e;
+    mfma_err_band(d, &eb, &floor_e);
     const dim3 grid((unsigned)((num_cand + EVM_C - 1) / EVM_C), (unsigned)((n_users + EVM_U - 1) / EVM_U));
     k_eval_fused<<<grid, 256, 0, s>>>(P, Q, d, users, tscore, n_users, num_cand, excl_off, excl, eb, floor_e,
                                       positions);
@@ -5698,8 +5699,8 @@ extern "C" int acf_recommend_topk(const float* P, const float* Q, int64_t U1, in
     const dim3 grid((unsigned)((n_users + TKV_UB - 1) / TKV_UB), (unsigned)S);
     k_topk_valu<<<grid, 256, lds, s>>>(P, Q, d, users, n_users, num_cand, excl_off, excl, k, wper, S, ws);
   } else {
-    const float eb = 4.0f * (float)(d + 2) * 5.9604645e-8f;  // as k_eval_fused: 4 (d + 2) 2^-24
-    const float floor_e = (float)d * 1.1754944e-38f * 4.0f;   // denormal products flushed by MFMA
+    float eb, floor_e;
+    mfma_err_band(d, &eb, &floor_e);
     const int cap = topk_mfma_cap(k);
     const dim3 grid((unsigned)((n_users + EVM_U - 1) / EVM_U), (unsigned)S);
     k_topk_mfma<<<grid, 256, (size_t)EVM_U * cap * sizeof(uint64_t), s>>>(P, Q, d, users, n_users, num_cand,

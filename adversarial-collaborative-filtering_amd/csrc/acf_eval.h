@@ -1,27 +1,13 @@
 // All-items evaluation kernels of libacf_apr.so (k_eval_*): included by
-// acf_apr.hip; one translation unit.
+// acf_apr.hip after acf_sweep.h (seq_dot and the shared sweep pieces); one
+// translation unit.
 #pragma once
 
 // ---------------------------------------------------------------------------
-// evaluation (_eval_by_user, utils.py:244-254)
-// score(u,c) = sequential sum over k of round(P[u][k]*Q[c][k]); the same chain
-// is used for the test item, the dense sweep and the exclusion correction so
-// that equal pairs give equal bits and ">=" ties are decided exactly.
+// evaluation (_eval_by_user, utils.py:244-254): position = #(candidates scoring
+// >= the test item), on seq_dot scores (acf_sweep.h) for the test item, the
+// dense sweep and the exclusion correction alike.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ float seq_dot(const float* __restrict__ p, const float* __restrict__ q,
-                                         int d) {
-  float s = 0.f;
-  for (int k = 0; k < d; k += 4) {
-    const float4 qv = *reinterpret_cast<const float4*>(q + k);
-    const float4 pv = *reinterpret_cast<const float4*>(p + k);
-    s = s + pv.x * qv.x;
-    s = s + pv.y * qv.y;
-    s = s + pv.z * qv.z;
-    s = s + pv.w * qv.w;
-  }
-  return s;
-}
-
 constexpr int EVAL_UB = 8;  // users per workgroup
 
 __global__ void __launch_bounds__(256) k_eval_all(const float* __restrict__ P,
@@ -36,10 +22,7 @@ __global__ void __launch_bounds__(256) k_eval_all(const float* __restrict__ P,
   __shared__ int s_cnt[EVAL_UB];
   const int u0 = blockIdx.x * EVAL_UB;
   const int nu = min(EVAL_UB, n_users - u0);
-  for (int idx = threadIdx.x; idx < EVAL_UB * d; idx += blockDim.x) {
-    const int uu = idx / d, k = idx - uu * d;
-    smem[idx] = uu < nu ? P[(int64_t)users[u0 + uu] * d + k] : 0.f;
-  }
+  sweep_load_rows<EVAL_UB, false>(smem, P, d, users, u0, nu, 0, nullptr);
   __syncthreads();
   if (threadIdx.x < EVAL_UB) {
     s_cnt[threadIdx.x] = 0;
@@ -56,18 +39,11 @@ __global__ void __launch_bounds__(256) k_eval_all(const float* __restrict__ P,
     float acc[EVAL_UB];
 #pragma unroll
     for (int uu = 0; uu < EVAL_UB; ++uu) acc[uu] = 0.f;
-    for (int k = 0; k < d; k += 4) {
+    for (int k = 0; k < d; k += 4) {  // acc[uu] = seq_dot(row uu, q): the loop stays here (acf_sweep.h)
       const float4 qv = *reinterpret_cast<const float4*>(q + k);
 #pragma unroll
-      for (int uu = 0; uu < EVAL_UB; ++uu) {
-        const float4 pv = *reinterpret_cast<const float4*>(smem + uu * d + k);
-        float s = acc[uu];
-        s = s + pv.x * qv.x;
-        s = s + pv.y * qv.y;
-        s = s + pv.z * qv.z;
-        s = s + pv.w * qv.w;
-        acc[uu] = s;
-      }
+      for (int uu = 0; uu < EVAL_UB; ++uu)
+        acc[uu] = seq_step(acc[uu], *reinterpret_cast<const float4*>(smem + uu * d + k), qv);
     }
 #pragma unroll
     for (int uu = 0; uu < EVAL_UB; ++uu) cnt[uu] += acc[uu] >= s_test[uu] ? 1 : 0;

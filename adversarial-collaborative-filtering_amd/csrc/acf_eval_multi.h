@@ -1,5 +1,6 @@
 // Multi-item all-items evaluation kernels of libacf_apr.so (k_evx_*): included by
-// acf_apr.hip after acf_eval.h (seq_dot); one translation unit.  DESIGN.md §4f.
+// acf_apr.hip after acf_sweep.h (seq_dot, the shared sweep pieces); one
+// translation unit.  DESIGN.md §4f.
 #pragma once
 
 // ---------------------------------------------------------------------------
@@ -49,19 +50,7 @@ __global__ void __launch_bounds__(256) k_evx_sweep(const float* __restrict__ P, 
   const int64_t c_begin = (int64_t)strip * wper * EVX_WIN;
   const int64_t c_end = min((int64_t)num_cand, c_begin + (int64_t)wper * EVX_WIN);
   int32_t* const dst = out + (int64_t)strip * n_tests;
-  for (int idx = tid; idx < EVX_UB * d; idx += 256) {
-    const int uu = idx / d, k = idx - uu * d;
-    float v = 0.f;
-    if (uu < nu) {
-      int64_t row = users[u0 + uu];
-      if (row < 0 || row >= U1) {  // read as row 0; reported when the caller checks
-        row = 0;
-        if (k == 0) atomicOr(err, 1);
-      }
-      v = P[row * d + k];
-    }
-    evx_rows[idx] = v;
-  }
+  sweep_load_rows<EVX_UB, true>(evx_rows, P, d, users, u0, nu, U1, err);  // reported when the caller checks
   if (tid <= EVX_UB) {
     const int r = min(tid, nu);  // entries past the tile repeat its end: empty lists
     s_toff[tid] = min(max(test_off[u0 + r], (int64_t)0), n_tests);
@@ -121,16 +110,7 @@ __global__ void __launch_bounds__(256) k_evx_sweep(const float* __restrict__ P, 
     for (int64_t cc = c_begin; cc < c_end; cc += EVX_BM) {
       const int64_t ce = min(c_end, cc + EVX_BM);
       __syncthreads();  // the previous bitmap's reads (first pass: the sorted scores' writes)
-      for (int x = tid; x < EVX_UB * (EVX_BM / 32); x += 256) (&s_ex[0][0])[x] = 0u;
-      __syncthreads();
-      if (excl_off) {
-        for (int uu = 0; uu < nu; ++uu) {
-          for (int64_t x = s_eoff[uu] + tid; x < s_eoff[uu + 1]; x += 256) {
-            const int64_t it = (int64_t)excl[x] - cc;
-            if (it >= 0 && it < ce - cc) atomicOr(&s_ex[uu][it >> 5], 1u << (it & 31));
-          }
-        }
-      }
+      sweep_excl_strided<EVX_UB, EVX_BM>(s_ex, s_eoff, nu, excl, cc, ce - cc);  // no lists: s_eoff is all 0
       __syncthreads();
       // a test item inside this bitmap that is not excluded counts itself below
 #pragma unroll
@@ -149,18 +129,11 @@ __global__ void __launch_bounds__(256) k_evx_sweep(const float* __restrict__ P, 
         float acc[EVX_UB];
 #pragma unroll
         for (int uu = 0; uu < EVX_UB; ++uu) acc[uu] = 0.f;
-        for (int k = 0; k < d; k += 4) {
+        for (int k = 0; k < d; k += 4) {  // acc[uu] = seq_dot(row uu, q): the loop stays here (acf_sweep.h)
           const float4 qv = *reinterpret_cast<const float4*>(q + k);
 #pragma unroll
-          for (int uu = 0; uu < EVX_UB; ++uu) {
-            const float4 pv = *reinterpret_cast<const float4*>(evx_rows + uu * d + k);
-            float s = acc[uu];
-            s = s + pv.x * qv.x;
-            s = s + pv.y * qv.y;
-            s = s + pv.z * qv.z;
-            s = s + pv.w * qv.w;
-            acc[uu] = s;
-          }
+          for (int uu = 0; uu < EVX_UB; ++uu)
+            acc[uu] = seq_step(acc[uu], *reinterpret_cast<const float4*>(evx_rows + uu * d + k), qv);
         }
         const int w = (int)(c - cc);
 #pragma unroll
@@ -216,14 +189,7 @@ __global__ void __launch_bounds__(256) k_evx_sum(const int32_t* __restrict__ par
 constexpr size_t EVX_WS_HEAD = 16;  // the range-error flag, padded
 
 static void evx_strips(int32_t n_users, int64_t n_tests, int32_t num_cand, int* wper, int* S) {
-  const int64_t W = std::max<int64_t>(1, ((int64_t)num_cand + EVX_WIN - 1) / EVX_WIN);
-  const int64_t tiles = std::max<int64_t>(1, ((int64_t)n_users + EVX_UB - 1) / EVX_UB);
-  int64_t s = (2048 + tiles - 1) / tiles;
-  s = std::min(s, ((int64_t)48 << 20) / (std::max<int64_t>(1, n_tests) * 4));
-  s = std::max<int64_t>(1, std::min(s, W));
-  const int64_t per = (W + s - 1) / s;
-  *wper = (int)per;
-  *S = (int)((W + per - 1) / per);
+  sweep_strips(num_cand, EVX_WIN, n_users, EVX_UB, 2048, std::max<int64_t>(1, n_tests) * 4, wper, S);
 }
 
 static size_t evx_workspace(int32_t n_users, int64_t n_tests, int32_t num_cand) {

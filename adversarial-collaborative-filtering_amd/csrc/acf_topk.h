@@ -1,5 +1,6 @@
 // Top-K recommendation kernels of libacf_apr.so (k_topk_*): included by
-// acf_apr.hip after acf_eval.h (seq_dot, the EVM_* tiling); one translation unit.
+// acf_apr.hip after acf_sweep.h and acf_eval.h (seq_dot, the shared sweep pieces,
+// the EVM_* tiling); one translation unit.
 #pragma once
 
 // ---------------------------------------------------------------------------
@@ -41,11 +42,10 @@ constexpr int TKM_BURST = 64;    // ... keys per user and half epilogue (4 waves
 constexpr int TKM_CAP_MAX = TOPK_MAX_K + TKM_BURST;  // 192
 
 // ---- VALU sweep: the straightforward restatement ---------------------------
-// A workgroup holds TKV_UB users' rows in LDS (as k_eval_all) and sweeps its
-// strip [strip * wper * 128, ...) 256 candidates a step, every thread one
-// candidate against the 8 rows with the seq_dot chain; the exclusion lists are
-// applied as a bitmap per TKV_CHUNK candidates (set semantics: unsorted,
-// repeated and out-of-range entries need no preparation).
+// A workgroup holds TKV_UB users' rows in LDS and sweeps its strip
+// [strip * wper * 128, ...) 256 candidates a step, every thread one candidate
+// against the 8 rows (seq_step); the exclusion lists are applied as a bitmap per
+// TKV_CHUNK candidates (sweep_excl_strided).
 __global__ void __launch_bounds__(256) k_topk_valu(const float* __restrict__ P, const float* __restrict__ Q, int d,
                                                    const int32_t* __restrict__ users, int n_users, int num_cand,
                                                    const int64_t* __restrict__ excl_off,
@@ -63,10 +63,7 @@ __global__ void __launch_bounds__(256) k_topk_valu(const float* __restrict__ P, 
   const int nu = min(TKV_UB, n_users - u0);
   const int64_t c_begin = (int64_t)strip * wper * EVM_C;
   const int64_t c_end = min((int64_t)num_cand, c_begin + (int64_t)wper * EVM_C);
-  for (int idx = tid; idx < TKV_UB * d; idx += 256) {
-    const int uu = idx / d, k = idx - uu * d;
-    rows[idx] = uu < nu ? P[(int64_t)users[u0 + uu] * d + k] : 0.f;
-  }
+  sweep_load_rows<TKV_UB, false>(rows, P, d, users, u0, nu, 0, nullptr);
   if (tid < TKV_UB) {
     s_cnt[tid] = 0;
     s_thr[tid] = 0;
@@ -74,15 +71,8 @@ __global__ void __launch_bounds__(256) k_topk_valu(const float* __restrict__ P, 
   if (tid <= nu) s_off[tid] = excl_off[u0 + tid];
   for (int64_t cc = c_begin; cc < c_end; cc += TKV_CHUNK) {
     const int64_t ce = min(c_end, cc + TKV_CHUNK);
-    __syncthreads();  // the previous chunk's bitmap reads (first pass: s_off)
-    for (int x = tid; x < TKV_UB * (TKV_CHUNK / 32); x += 256) (&s_ex[0][0])[x] = 0u;
-    __syncthreads();
-    for (int uu = 0; uu < nu; ++uu) {
-      for (int64_t x = s_off[uu] + tid; x < s_off[uu + 1]; x += 256) {
-        const int64_t it = (int64_t)excl[x] - cc;
-        if (it >= 0 && it < ce - cc) atomicOr(&s_ex[uu][it >> 5], 1u << (it & 31));
-      }
-    }
+    __syncthreads();  // the previous chunk's bitmap reads (first pass: the rows)
+    sweep_excl_strided<TKV_UB, TKV_CHUNK>(s_ex, s_off, nu, excl, cc, ce - cc);
     __syncthreads();
     for (int64_t base = cc; base < ce; base += 256) {
       const int64_t c = base + tid;
@@ -91,18 +81,11 @@ __global__ void __launch_bounds__(256) k_topk_valu(const float* __restrict__ P, 
         float acc[TKV_UB];
 #pragma unroll
         for (int uu = 0; uu < TKV_UB; ++uu) acc[uu] = 0.f;
-        for (int k = 0; k < d; k += 4) {
+        for (int k = 0; k < d; k += 4) {  // acc[uu] = seq_dot(row uu, q): the loop stays here (acf_sweep.h)
           const float4 qv = *reinterpret_cast<const float4*>(q + k);
 #pragma unroll
-          for (int uu = 0; uu < TKV_UB; ++uu) {
-            const float4 pv = *reinterpret_cast<const float4*>(rows + uu * d + k);
-            float s = acc[uu];
-            s = s + pv.x * qv.x;
-            s = s + pv.y * qv.y;
-            s = s + pv.z * qv.z;
-            s = s + pv.w * qv.w;
-            acc[uu] = s;
-          }
+          for (int uu = 0; uu < TKV_UB; ++uu)
+            acc[uu] = seq_step(acc[uu], *reinterpret_cast<const float4*>(rows + uu * d + k), qv);
         }
         const int w = (int)(c - cc);
 #pragma unroll
@@ -283,23 +266,12 @@ __global__ void __launch_bounds__(256) k_topk_mfma(const float* __restrict__ P, 
 
 
 // ---- host: strips and workspace ----------------------------------------------
-// kernel 1 (MFMA) / 2 (VALU) -> windows per strip and the number of strips S.
-// Enough strips that the grid fills the device when n_users is small (64 users
-// x 5M items: 1 user tile x 512 strips), few enough that thresholds stay useful
-// and that the partial lists (n_users * S * K keys) stay under 48 MiB.
+// kernel 1 (MFMA) / 2 (VALU) -> windows per strip and the number of strips S
+// (sweep_strips; 64 users x 5M items: 1 user tile x 512 strips); a strip's
+// partial lists are n_users * K keys.
 static void topk_strips(int32_t n_users, int32_t num_cand, int32_t k, int kernel, int* wper, int* S) {
-  const int64_t W = ((int64_t)num_cand + EVM_C - 1) / EVM_C;  // windows
-  const int64_t ub = kernel == 1 ? EVM_U : TKV_UB;
-  const int64_t tiles = std::max<int64_t>(1, ((int64_t)n_users + ub - 1) / ub);
-  const int64_t target = kernel == 1 ? 512 : 2048;  // workgroups
-  int64_t s = (target + tiles - 1) / tiles;
-  const int64_t by_ws = ((int64_t)48 << 20) / (std::max<int64_t>(1, n_users) * k * 8);
-  s = std::min(s, by_ws);
-  s = std::min<int64_t>(s, 4096);
-  s = std::max<int64_t>(1, std::min(s, W));
-  const int64_t per = std::max<int64_t>(1, (W + s - 1) / s);
-  *wper = (int)per;
-  *S = (int)std::max<int64_t>(1, (W + per - 1) / per);
+  sweep_strips(num_cand, EVM_C, n_users, kernel == 1 ? EVM_U : TKV_UB, kernel == 1 ? 512 : 2048,
+               std::max<int64_t>(1, n_users) * k * 8, wper, S);
 }
 
 static int topk_mfma_cap(int k) { return std::min(2 * k + TKM_BURST, TKM_CAP_MAX); }

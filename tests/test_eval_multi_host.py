@@ -4,6 +4,7 @@ builder, the rating-file reader, the CLI flag and file, and the checks that fire
 before any native call."""
 import ctypes
 import importlib
+import json
 import os
 import re
 from types import SimpleNamespace
@@ -64,6 +65,16 @@ def test_workspace_query_is_host_only(native):
     assert native.load().acf_eval_positions_multi_workspace(3, 5, 100, None) == native.ACF_E_INVALID
     ops = importlib.import_module(PKG + ".ops")
     assert ops.eval_positions_multi_workspace(3, 15, 70000) == few
+
+
+def test_workspace_grid_matches_the_recorded_bytes(native):
+    """The strip cut is ABI: every byte count equals the one recorded before the
+    sweeps shared one strip function (tests/golden/make_sweep_strips.py)."""
+    with open(os.path.join(REPO, "tests", "golden", "sweep_strips.json")) as f:
+        want = json.load(f)["multi"]
+    assert len(want) == 8 * 7 * 2
+    got = {key: _ws(native, *map(int, key.split(","))) for key in want}
+    assert got == {key: (native.ACF_OK, size) for key, size in want.items()}
 
 
 def test_bad_arguments_are_invalid_before_any_launch(native):

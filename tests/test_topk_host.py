@@ -3,6 +3,7 @@ host-only workspace query, argument validation of ops.recommend_topk, the
 exclusion-CSR helper, and the CLI's --topk flag with its writer / reader."""
 import ctypes
 import importlib
+import json
 import os
 import re
 from types import SimpleNamespace
@@ -47,6 +48,16 @@ def test_workspace_is_far_below_a_score_matrix(native, kernel):
     assert 0 < b < 64 * MiB
     # the partial lists hold at least one list of k entries per user
     assert a >= 6040 * 100 * 8 and b >= 64 * 100 * 8
+
+
+def test_workspace_grid_matches_the_recorded_bytes(native):
+    """The strip cut is ABI: every byte count equals the one recorded before the
+    sweeps shared one strip function (tests/golden/make_sweep_strips.py)."""
+    with open(os.path.join(REPO, "tests", "golden", "sweep_strips.json")) as f:
+        want = json.load(f)["topk"]
+    assert len(want) == 8 * 7 * 3 * 3
+    got = {key: _workspace(native, *map(int, key.split(","))) for key in want}
+    assert got == want
 
 
 def test_workspace_rejects_bad_arguments(native):
