@@ -67,6 +67,13 @@ def parse_args(argv=None, flavor="ori"):
                    help="After training, evaluate under perturbed tables at these eps (comma separated, e.g. "
                         "\"0.5,1,2\"), gradient and random directions over the last epoch's triplets, and write "
                         "<out>/<runName>.robust (empty: off).")
+    p.add_argument("--certify_eps", type=parse_eps_list, default=[],
+                   help="After training, certify the ranking at these eps (comma separated, e.g. \"0.1,0.5,1\"): "
+                        "lower bounds of HR@K, NDCG@K and AUC (all-items evaluation) under EVERY perturbation of "
+                        "at most eps per embedding row in L2; writes <out>/<runName>.certified (empty: off).")
+    p.add_argument("--certify_side", choices=["user", "item", "both"], default="user",
+                   help="Which rows --certify_eps lets the attacker move: the user rows, the item rows, or both "
+                        "as two separate passes (not a joint attack).")
     p.add_argument("--fold_in", type=str, default=None, metavar="FILE",
                    help="After training, fold in the new users of FILE (rating TSV: uid<TAB>item<TAB>...; its "
                         "uids are keys of new users, not rows of the user table) and write their --topk best "
@@ -162,6 +169,27 @@ def read_robust(file):
             if len(parts) != 5:
                 raise ValueError(f"{file}: line {n} has {len(parts)} fields, expected 5")
             rows.append((parts[0], *[float(x) for x in parts[1:]]))
+    return rows
+
+
+def write_certified(path, name, rows):
+    """One line "side<TAB>eps<TAB>K<TAB>hr_lb<TAB>ndcg_lb<TAB>auc_lb" per row of
+    evaluate.certified (floats by repr: the reader gets the same values back)."""
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, name), "w") as f:
+        for side, eps, K, hr, ndcg, auc in rows:
+            f.write("%s\t%r\t%d\t%r\t%r\t%r\n" % (side, float(eps), int(K), float(hr), float(ndcg), float(auc)))
+
+
+def read_certified(file):
+    """The rows [(side, eps, K, hr_lb, ndcg_lb, auc_lb)] write_certified wrote."""
+    rows = []
+    with open(file) as f:
+        for n, line in enumerate(f):
+            parts = line.rstrip("\n").split("\t")
+            if len(parts) != 6:
+                raise ValueError(f"{file}: line {n} has {len(parts)} fields, expected 6")
+            rows.append((parts[0], float(parts[1]), int(parts[2]), *[float(x) for x in parts[3:]]))
     return rows
 
 
@@ -295,4 +323,11 @@ def main(argv=None, flavor="ori"):
             rows = robustness(final, dataset, init_eval_model(dataset, args), trip, args.robust_eps,
                               seed=args.seed)
             write_robust(out, runName + ".robust", rows)
+    if args.certify_eps:
+        from .evaluate import certified, init_eval_model
+        final = amf if args.model == "apr" else m
+        plan = init_eval_model(dataset, argparse.Namespace(eval_mode="all"))  # certified positions rank all items
+        sides = ("user", "item") if args.certify_side == "both" else (args.certify_side,)
+        rows = [row for side in sides for row in certified(final, plan, args.certify_eps, side=side)]
+        write_certified(out, runName + ".certified", rows)
     return 0

@@ -3582,6 +3582,7 @@ __global__ void __launch_bounds__(256) k_forward(const float* __restrict__ P,
 #include "acf_topk.h"  // top-K recommendation lists (k_topk_*): DESIGN.md §4b
 #include "acf_adv.h"   // whole-stream adversarial direction (k_adv_*): DESIGN.md §4c
 #include "acf_eval_multi.h"  // multi-item evaluation and rank metrics (k_evx_*): DESIGN.md §4f
+#include "acf_eval_worst.h"  // certified worst-case positions (k_evw_*): DESIGN.md §4g
 
 // ---------------------------------------------------------------------------
 // sampler (shuffle / _get_train_batch, APR.py:39-81)
@@ -5757,6 +5758,82 @@ extern "C" int acf_eval_positions_multi(const float* P, const float* Q, int64_t 
   HIP_TRY(hipGetLastError());
   if (S > 1) {
     k_evx_sum<<<grid_for(n_tests), 256, 0, s>>>(part, S, n_tests, positions);
+    HIP_TRY(hipGetLastError());
+  }
+  if (check) {
+    int32_t herr = 0;
+    HIP_TRY(hipMemcpyAsync(&herr, err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    ACF_CHECK(herr == 0, ACF_E_RANGE, "index out of range (%s%s)", (herr & 1) ? "user >= num_user_rows " : "",
+              (herr & 2) ? "test item >= num_item_rows" : "");
+  }
+  return ACF_OK;
+}
+
+// ---- certified worst-case positions (acf_eval_worst.h) -------------------------
+static int evw_check(int32_t n_users, int32_t num_cand, int32_t n_eps) {
+  ACF_CHECK(n_users >= 0, ACF_E_INVALID, "negative count");
+  ACF_CHECK(num_cand >= 1, ACF_E_INVALID, "num_candidates must be >= 1, got %d", num_cand);
+  ACF_CHECK(n_eps >= 1 && n_eps <= EVW_MAX_EPS, ACF_E_INVALID, "n_eps %d outside [1, %d]", n_eps, EVW_MAX_EPS);
+  return ACF_OK;
+}
+
+extern "C" int acf_eval_positions_worst_workspace(int32_t n_users, int32_t num_cand, int32_t n_eps, size_t* bytes) {
+  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
+  ACF_RET(evw_check(n_users, num_cand, n_eps));
+  *bytes = evw_workspace(n_users, num_cand, n_eps);
+  return ACF_OK;
+}
+
+template <int UB, bool USER>
+static void launch_evw(const float* P, const float* Q, int d, int64_t U1, int64_t I1, const int32_t* users,
+                       const int32_t* tests, int n_users, int num_cand, const int64_t* excl_off, const int32_t* excl,
+                       const EvwEps& eps, int wper, int S, int32_t* out, int32_t* err, hipStream_t s) {
+  const dim3 grid((unsigned)((n_users + UB - 1) / UB), (unsigned)S);
+  const size_t lds = (size_t)(USER ? 2 : 1) * UB * d * sizeof(float);
+  k_evw_sweep<UB, USER><<<grid, 256, lds, s>>>(P, Q, d, U1, I1, users, tests, n_users, num_cand, excl_off, excl, eps,
+                                               wper, out, err);
+}
+
+extern "C" int acf_eval_positions_worst(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
+                                        const int32_t* users, const int32_t* test_items, int32_t n_users,
+                                        int32_t num_cand, const int64_t* excl_off, const int32_t* excl,
+                                        const float* eps, int32_t n_eps, int32_t side, int32_t* worst,
+                                        void* workspace, size_t workspace_bytes, int32_t check, void* stream_) {
+  ACF_RET(check_dim(d));
+  ACF_RET(evw_check(n_users, num_cand, n_eps));
+  ACF_CHECK(side == 0 || side == 1, ACF_E_INVALID, "side must be 0 (user) or 1 (item), got %d", side);
+  ACF_CHECK(eps, ACF_E_INVALID, "NULL argument");
+  EvwEps ev{};
+  ev.n = n_eps;
+  for (int e = 0; e < EVW_MAX_EPS; ++e) {
+    const float v = eps[std::min(e, n_eps - 1)];  // the unused slots repeat the last one
+    ACF_CHECK(std::isfinite(v) && v >= 0.f, ACF_E_INVALID, "eps must be finite and >= 0, got %g", (double)v);
+    ev.e[e] = v;
+  }
+  ACF_CHECK(U1 > 0 && I1 > 0, ACF_E_INVALID, "empty table");
+  ACF_CHECK(num_cand <= I1, ACF_E_INVALID, "num_candidates %d > item rows", num_cand);
+  ACF_CHECK(P && Q && users && test_items && worst && workspace, ACF_E_INVALID, "NULL argument");
+  ACF_CHECK((excl_off == nullptr) == (excl == nullptr), ACF_E_INVALID, "excl_off and excl_items go together");
+  ACF_CHECK(reinterpret_cast<uintptr_t>(workspace) % 4 == 0, ACF_E_INVALID, "workspace must be 4-byte aligned");
+  const size_t need = evw_workspace(n_users, num_cand, n_eps);
+  ACF_CHECK(workspace_bytes >= need, ACF_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+  if (n_users == 0) return ACF_OK;
+  int wper = 0, S = 0;
+  evw_strips(n_users, num_cand, n_eps, &wper, &S);
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  int32_t* err = static_cast<int32_t*>(workspace);
+  int32_t* part = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + EVW_WS_HEAD);
+  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+  int32_t* out = S > 1 ? part : worst;
+  const bool wide = d <= EVW_D_SPLIT;  // 8 entries per workgroup, 4 above: the rows stay within 32 KB of LDS
+  const auto launch = side == 0 ? (wide ? &launch_evw<EVW_UB, true> : &launch_evw<EVW_UB / 2, true>)
+                                : (wide ? &launch_evw<EVW_UB, false> : &launch_evw<EVW_UB / 2, false>);
+  launch(P, Q, d, U1, I1, users, test_items, n_users, num_cand, excl_off, excl, ev, wper, S, out, err, s);
+  HIP_TRY(hipGetLastError());
+  if (S > 1) {
+    const int64_t n_out = (int64_t)n_eps * n_users;
+    k_evx_sum<<<grid_for(n_out), 256, 0, s>>>(part, S, n_out, worst);
     HIP_TRY(hipGetLastError());
   }
   if (check) {

@@ -20,6 +20,7 @@
 //   acf::fold_in_users         rows for new users against a frozen Q (no reference counterpart)
 //   acf::eval_positions_multi  positions of several held-out items per user, one sweep per user
 //   acf::rank_metrics          hit / recall / precision / ndcg / map @K, mrr, auc of such positions (fp64)
+//   acf::eval_positions_worst  certified worst-case positions under an eps attack on the user or the item rows
 #include <torch/library.h>
 #include <ATen/ATen.h>
 // ROCm builds of PyTorch keep the "cuda" device type: the guard and stream
@@ -27,6 +28,7 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
+#include <cmath>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -532,6 +534,50 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> rank_metr
   return {per_user, per_free, mean_cut, mean_free, n_scored};
 }
 
+// worst-case positions [n_eps, n] of every entry's test item under an attack of budget eps on the
+// side's rows (acf_eval_positions_worst; side: "user" | "item").  users and test items are
+// range-checked here, before any gather; empty excl_off and excl_items: no exclusions.
+at::Tensor eval_positions_worst(const at::Tensor& P, const at::Tensor& Q, const at::Tensor& users_,
+                                const at::Tensor& test_items_, int64_t num_candidates, const at::Tensor& excl_off,
+                                const at::Tensor& excl_items_, at::ArrayRef<double> eps, c10::string_view side) {
+  need_table(P, "embedding_P", P);
+  need_table(Q, "embedding_Q", P);
+  TORCH_CHECK(P.size(1) == Q.size(1), "embedding_P and embedding_Q dims differ");
+  TORCH_CHECK(side == "user" || side == "item", "side must be \"user\" or \"item\", got \"", side, "\"");
+  const int64_t ne = (int64_t)eps.size();
+  TORCH_CHECK(ne >= 1 && ne <= 8, "1 to 8 eps, got ", ne);
+  float ev[8] = {0};
+  for (int64_t e = 0; e < ne; ++e) {
+    ev[e] = (float)eps[e];
+    TORCH_CHECK(std::isfinite(ev[e]) && ev[e] >= 0.f, "eps must be finite and >= 0, got ", eps[e]);
+  }
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(P.device());
+  at::Tensor users = idx32(users_, "users", P), tests = idx32(test_items_, "test_items", P);
+  at::Tensor excl = idx32(excl_items_, "excl_items", P);
+  const int64_t n = users.numel();
+  TORCH_CHECK(n < (1ll << 31), "too many users");
+  TORCH_CHECK(tests.numel() == n, "test_items must have one entry per user");
+  TORCH_CHECK(num_candidates >= 1 && num_candidates <= Q.size(0), "num_candidates must lie in [1, item rows]");
+  const bool no_excl = excl_off.numel() == 0 && excl.numel() == 0;
+  if (!no_excl) need_csr(excl_off, "excl_off", n, excl.numel(), P);
+  check_range(users, P.size(0), "users");
+  check_range(tests, Q.size(0), "test_items");
+  if (excl.numel() == 0) excl = at::zeros({1}, users.options());
+  at::Tensor worst = at::empty({ne, n}, users.options());
+  if (n == 0) return worst;
+  size_t ws = 0;
+  ok(acf_eval_positions_worst_workspace((int32_t)n, (int32_t)num_candidates, (int32_t)ne, &ws),
+     "acf_eval_positions_worst_workspace");
+  at::Tensor work = at::empty({(int64_t)((ws + 3) / 4)}, users.options());
+  ok(acf_eval_positions_worst(P.data_ptr<float>(), Q.data_ptr<float>(), P.size(0), Q.size(0), (int32_t)P.size(1),
+                              users.data_ptr<int32_t>(), tests.data_ptr<int32_t>(), (int32_t)n,
+                              (int32_t)num_candidates, no_excl ? nullptr : excl_off.data_ptr<int64_t>(),
+                              no_excl ? nullptr : excl.data_ptr<int32_t>(), ev, (int32_t)ne, side == "user" ? 0 : 1,
+                              worst.data_ptr<int32_t>(), work.data_ptr(), ws, 0, stream_of(P)),
+     "acf_eval_positions_worst");
+  return worst;
+}
+
 }  // namespace
 
 #ifndef ACF_BUILD_HASH
@@ -570,6 +616,8 @@ TORCH_LIBRARY(acf, m) {
         "int num_candidates, Tensor excl_off, Tensor excl_items) -> Tensor");
   m.def("rank_metrics(Tensor positions, Tensor test_off, Tensor n_neg, int[] cutoffs) -> "
         "(Tensor per_user, Tensor per_user_free, Tensor mean_cut, Tensor mean_free, Tensor n_scored)");
+  m.def("eval_positions_worst(Tensor P, Tensor Q, Tensor users, Tensor test_items, int num_candidates, "
+        "Tensor excl_off, Tensor excl_items, float[] eps, str side=\"user\") -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(acf, CUDA, m) {
@@ -587,4 +635,5 @@ TORCH_LIBRARY_IMPL(acf, CUDA, m) {
   m.impl("fold_in_users", &fold_in_users);
   m.impl("eval_positions_multi", &eval_positions_multi);
   m.impl("rank_metrics", &rank_metrics);
+  m.impl("eval_positions_worst", &eval_positions_worst);
 }

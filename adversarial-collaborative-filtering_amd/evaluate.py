@@ -222,6 +222,96 @@ def robustness(model, dataset, plan: EvalPlan, triplets, eps_list, modes=("grad"
     return rows
 
 
+# ---- certified robustness: worst-case positions under an eps attack -----------
+CERT_SIDES = ("user", "item")
+
+
+def worst_margins_host(P, Q, users, test_items, num_candidates, excl_lists, side="user"):
+    """The pieces of the worst-case predicate in float64 numpy, [n, num_candidates]
+    each: m (score(u,t) - score(u,c)), base (the threshold is eps * base: |q_t -
+    q_c| for side "user", 2 |p| for "item") and cand (c is a candidate of the
+    entry: not in its exclusion set, not t).  excl_lists: None or one iterable
+    per entry; entries outside [0, num_candidates) are ignored."""
+    if side not in CERT_SIDES:
+        raise ValueError(f"side must be one of {CERT_SIDES}, got {side!r}")
+    P, Q = np.asarray(P, dtype=np.float64), np.asarray(Q, dtype=np.float64)
+    users = np.asarray(users, dtype=np.int64).reshape(-1)
+    tests = np.asarray(test_items, dtype=np.int64).reshape(-1)
+    C = int(num_candidates)
+    p, qt, qc = P[users], Q[tests], Q[:C]
+    m = np.einsum("nd,nd->n", p, qt)[:, None] - p @ qc.T
+    if side == "user":
+        base = np.empty((len(users), C), dtype=np.float64)
+        for r in range(len(users)):  # the difference form: identical rows give exactly 0
+            base[r] = np.sqrt(((qt[r][None, :] - qc) ** 2).sum(axis=1))
+    else:
+        base = np.repeat(2.0 * np.sqrt((p * p).sum(1))[:, None], C, axis=1)
+    cand = np.ones((len(users), C), dtype=bool)
+    for r in range(len(users)):
+        if excl_lists is not None:
+            ex = np.asarray(list(excl_lists[r]), dtype=np.int64).reshape(-1)
+            cand[r, ex[(ex >= 0) & (ex < C)]] = False
+        if 0 <= tests[r] < C:
+            cand[r, tests[r]] = False
+    return m, base, cand
+
+
+def worst_positions_host(P, Q, users, test_items, num_candidates, excl_lists, eps, side="user"):
+    """ops.eval_positions_worst restated in float64 numpy, the tests' yardstick:
+    int64 [len(eps), n], worst[e][r] = #{c in C_r, c != t : m_c <= eps_e *
+    base_c} (worst_margins_host).  Candidate c can be brought to score >= t by a
+    perturbation within the budget iff its inequality holds (Cauchy-Schwarz, with
+    equality for delta along q_c - q_t; for the item side q_t and q_c move
+    against each other along p), so no admissible perturbation puts more than
+    worst candidates at or above t."""
+    eps = [float(e) for e in eps]
+    if any(not (math.isfinite(e) and e >= 0) for e in eps):
+        raise ValueError("eps must be finite and >= 0")
+    m, base, cand = worst_margins_host(P, Q, users, test_items, num_candidates, excl_lists, side)
+    return np.stack([((m <= e * base) & cand).sum(axis=1) for e in eps]).astype(np.int64).reshape(len(eps), -1)
+
+
+def certified(model_or_tables, plan: EvalPlan, eps_list, side="user", cutoffs=None):
+    """Certified lower bounds of HR@K, NDCG@K and AUC under EVERY perturbation of
+    one side within eps per row in L2 (side "user": the user rows; "item": every
+    item row its own delta): rows (side, eps, K, hr_lb, ndcg_lb, auc_lb), for
+    every eps in eps_list's order and every K of cutoffs (default plan.K).  The
+    worst-case positions come from ops.eval_positions_worst on the plan's
+    exclusions (all-items plans only; up to 8 eps share one candidate sweep), the
+    metrics from ops.rank_metrics with one test item per user, both on the GPU.
+    The metrics do not increase with the position, so at the worst-case position
+    they bound every attack from below; evaluate.robustness, one particular
+    attack, bounds from above.  eps = 0 reproduces evaluate()'s means."""
+    import torch
+    if plan.mode != "all":
+        raise ValueError("certified needs an all-items plan (init_eval_model with eval_mode='all')")
+    if side not in CERT_SIDES:
+        raise ValueError(f"side must be one of {CERT_SIDES}, got {side!r}")
+    eps_list = [float(e) for e in eps_list]
+    if any(not (math.isfinite(e) and e >= 0) for e in eps_list):
+        raise ValueError("eps must be finite and >= 0")
+    cutoffs = (int(plan.K),) if cutoffs is None else tuple(int(k) for k in cutoffs)
+    if hasattr(model_or_tables, "embedding_P"):
+        P, Q = model_or_tables.embedding_P, model_or_tables.embedding_Q
+    else:
+        P, Q = model_or_tables[0], model_or_tables[1]
+    u, t, eo, ex = plan.device_arrays(P.device)
+    n = int(u.numel())
+    one_each = torch.arange(n + 1, dtype=torch.int64, device=P.device)
+    nn = torch.as_tensor(np.asarray(plan.n_neg), dtype=torch.int32, device=P.device)
+    rows = []
+    for a in range(0, len(eps_list), ops.WORST_MAX_EPS):
+        chunk = eps_list[a:a + ops.WORST_MAX_EPS]
+        worst = ops.eval_positions_worst(P, Q, u, t, int(plan.num_candidates), eo, ex, eps=chunk, side=side)
+        for e, eps in enumerate(chunk):
+            rm = ops.rank_metrics(worst[e], one_each, nn, cutoffs)
+            mean_cut, mean_free = rm.mean_cut.cpu().numpy(), rm.mean_free.cpu().numpy()
+            for c, K in enumerate(cutoffs):
+                rows.append((side, eps, K, float(mean_cut[c, CUT_METRICS.index("hit")]),
+                             float(mean_cut[c, CUT_METRICS.index("ndcg")]), float(mean_free[FREE_METRICS.index("auc")])))
+    return rows
+
+
 # ---- fold-in: rows for users who were not in the training set -----------------
 class FoldIn:
     """What fold_in returns: keys (the dict's keys ascending, or 0..n-1 for a

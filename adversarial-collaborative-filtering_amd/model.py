@@ -234,6 +234,12 @@ class MF:
         from .evaluate import robustness
         return robustness(self, dataset, plan, triplets, eps_list, modes=modes, seed=seed)
 
+    def certified(self, plan, eps_list, side="user", cutoffs=None):
+        """evaluate.certified: rows (side, eps, K, hr_lb, ndcg_lb, auc_lb), lower
+        bounds under EVERY perturbation of that side within eps per row."""
+        from .evaluate import certified
+        return certified(self, plan, eps_list, side=side, cutoffs=cutoffs)
+
 
 class Session:
     """Minimal ``tf.Session`` stand-in for the fetches the APR path uses."""

@@ -8,6 +8,7 @@ index ranges are validated on device by the plan / sampler (``NativeIndexError``
 from __future__ import annotations
 
 import ctypes
+import math
 import weakref
 from dataclasses import dataclass
 
@@ -910,6 +911,94 @@ def rank_metrics(positions, test_off, n_neg, cutoffs) -> RankMetrics:
              out.per_user.data_ptr(), out.per_user_free.data_ptr(), out.mean_cut.data_ptr(),
              out.mean_free.data_ptr(), out.n_scored.data_ptr(), _stream_ptr(dev))
     return out
+
+
+WORST_MAX_EPS = 8                       # EVW_MAX_EPS
+WORST_SIDES = {"user": 0, "item": 1}
+
+
+def _worst_eps(eps) -> tuple:
+    """eps as a tuple of 1..WORST_MAX_EPS finite floats >= 0 (ValueError)."""
+    try:
+        es = tuple(float(e) for e in eps)
+    except TypeError:
+        raise ValueError(f"eps must be a sequence of numbers, got {eps!r}") from None
+    if not 1 <= len(es) <= WORST_MAX_EPS:
+        raise ValueError(f"1 to {WORST_MAX_EPS} eps per call, got {len(es)}")
+    for e in es:
+        if not (math.isfinite(e) and e >= 0.0):
+            raise ValueError(f"eps must be finite and >= 0, got {e!r}")
+    return es
+
+
+def eval_positions_worst_workspace(n_users: int, num_candidates: int, n_eps: int) -> int:
+    """Bytes of device workspace acf_eval_positions_worst needs (a host-only query)."""
+    size = ctypes.c_size_t()
+    call("acf_eval_positions_worst_workspace", int(n_users), int(num_candidates), int(n_eps), ctypes.byref(size))
+    return int(size.value)
+
+
+def eval_positions_worst(P, Q, users, test_items, num_candidates: int, excl_off=None, excl_items=None,
+                         eps=(0.0,), side: str = "user", check: bool = True):
+    """Certified worst-case positions under an attack of budget eps
+    (acf_eval_positions_worst): int32 [len(eps), n].  Entry r is row users[r] of
+    P with the test item t = test_items[r] and the candidates [0, num_candidates)
+    minus the SET of excl_items[excl_off[r]:excl_off[r+1]] (unsorted, repeated
+    and out-of-range entries are fine; no exclusion arguments: nothing is
+    excluded; t itself never counts).  side="user": any delta with |delta|_2 <=
+    eps is added to the user row; side="item": every item row gets its own such
+    delta.  worst[e, r] = the number of candidates that SOME admissible
+    perturbation brings to score >= t (m_c <= eps |q_t - q_c|, or m_c <= 2 eps
+    |p|, in fp32 as include/acf_apr.h states); no single perturbation lifts
+    more, so worst < K certifies t in the top K.  eps = 0 gives
+    eval_positions_multi's positions; rows do not decrease in eps.  Up to 8 eps
+    per call share one sweep of the candidates.  Bad shapes, dtypes, eps and
+    side raise ValueError / TypeError before any native call; with check, a
+    user or test item outside its table raises NativeIndexError (one sync)."""
+    es = _worst_eps(eps)
+    if side not in WORST_SIDES:
+        raise ValueError(f"side must be one of {sorted(WORST_SIDES)}, got {side!r}")
+    ti = _csr_items(test_items, "test_items")
+    us = _csr_items(users, "users")
+    n = us.numel()
+    if ti.numel() != n:
+        raise ValueError(f"test_items must have one entry per user: {ti.numel()} for {n}")
+    if (excl_off is None) != (excl_items is None):
+        raise ValueError("excl_off and excl_items go together")
+    ex = None if excl_items is None else _csr_items(excl_items, "excl_items")
+    if isinstance(num_candidates, bool) or not isinstance(num_candidates, int) or num_candidates < 1:
+        raise ValueError(f"num_candidates must be an int >= 1, got {num_candidates!r}")
+    for tab, name in ((P, "embedding_P"), (Q, "embedding_Q")):
+        if not isinstance(tab, torch.Tensor) or tab.dtype != torch.float32 or tab.dim() != 2:
+            raise TypeError(f"{name} must be a 2-D torch.float32 tensor")
+    if P.shape[1] != Q.shape[1]:
+        raise ValueError("embedding_P and embedding_Q dims differ")
+    if num_candidates > Q.shape[0]:
+        raise ValueError("num_candidates exceeds item rows")
+    eoff = None if ex is None else _csr_offsets(excl_off, n, ex.numel(), "excl_off")
+    _require(P, "embedding_P", torch.float32, None, 2)
+    dev = P.device
+    _require(Q, "embedding_Q", torch.float32, dev, 2)
+    eoff = None if eoff is None else eoff.to(device=dev, dtype=torch.int64).contiguous()
+    settle_tables()
+    u = us.to(device=dev, dtype=torch.int32).contiguous()
+    t = ti.to(device=dev, dtype=torch.int32).contiguous()
+    if ex is not None:
+        ex = (ex.to(device=dev, dtype=torch.int32).contiguous() if ex.numel()
+              else torch.zeros(1, dtype=torch.int32, device=dev))
+    worst = torch.empty((len(es), n), dtype=torch.int32, device=dev)
+    if n == 0:
+        return worst
+    nbytes = eval_positions_worst_workspace(n, num_candidates, len(es))
+    work = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+    ceps = (ctypes.c_float * len(es))(*es)
+    with _on(dev):
+        call("acf_eval_positions_worst", P.data_ptr(), Q.data_ptr(), P.shape[0], Q.shape[0], P.shape[1],
+             u.data_ptr(), t.data_ptr(), n, num_candidates,
+             eoff.data_ptr() if eoff is not None else None, ex.data_ptr() if ex is not None else None,
+             ceps, len(es), WORST_SIDES[side], worst.data_ptr(), work.data_ptr(), nbytes, int(bool(check)),
+             _stream_ptr(dev))
+    return worst
 
 
 ADV_MODES = {"grad": 0, "random": 1}

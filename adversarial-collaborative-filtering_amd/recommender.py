@@ -189,3 +189,9 @@ class APR(Recommender):
         self._ensure()
         return self.model.robustness(dataset, plan, ([x_train[0]], [x_train[1]], [x_train[2]]), eps_list,
                                      modes=modes, seed=seed)
+
+    def certified(self, plan, eps_list, side="user", cutoffs=None):
+        """evaluate.certified against an all-items plan: rows (side, eps, K, hr_lb,
+        ndcg_lb, auc_lb), lower bounds under every attack of that budget."""
+        self._ensure()
+        return self.model.certified(plan, eps_list, side=side, cutoffs=cutoffs)

@@ -31,6 +31,10 @@ SURVEY.md §8(b) proposes:
   per user (``ops.eval_positions_multi`` / ``ops.rank_metrics``, the same values).  Both copy
   their CSR offsets back to validate them, and the positions op checks users and test items
   before any gather; empty ``excl_off`` and ``excl_items`` exclude nothing;
+- ``eval_positions_worst(P, Q, users, test_items, num_candidates, excl_off, excl_items, eps, side)
+  -> worst [n_eps, n]``: certified worst-case positions under an eps attack on the user or the
+  item rows (``ops.eval_positions_worst``, the same values); users and test items are checked
+  before any gather; empty ``excl_off`` and ``excl_items`` exclude nothing;
 - ``release_contexts() -> int``: frees the cached step contexts (plan workspace and
   the streamed step's version buffers) that ``apr_train`` / ``bpr_apr_step`` keep per
   (device, table shape, batch shape).
@@ -49,7 +53,7 @@ from . import build_native
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libacf_torch.so")
 OPS = ("bpr_apr_step", "apr_train", "gather_bpr_fwd_bwd", "row_segment_sum", "l2norm_perturb",
        "sparse_adagrad_apply", "score_rank", "score_rank_all", "recommend_topk", "adv_direction", "adv_apply",
-       "fold_in_users", "eval_positions_multi", "rank_metrics", "release_contexts")
+       "fold_in_users", "eval_positions_multi", "rank_metrics", "eval_positions_worst", "release_contexts")
 _lock = threading.Lock()
 _loaded = False
 

@@ -436,6 +436,50 @@ int acf_eval_rank_metrics(const int32_t* positions, const int64_t* test_off, int
                           double* per_user, double* per_user_free, double* mean_cut, double* mean_free,
                           int64_t* n_scored, void* stream);
 
+/* ---- certified ranking robustness: worst-case positions under an eps attack --
+ * (no reference counterpart.)  Entry r (row users[r] of P; any order, repeats
+ * allowed) has the test item t = test_items[r] and the candidates C_r =
+ * [0, num_candidates) minus the SET of excl_items[excl_off[r] .. excl_off[r+1])
+ * -- unsorted, repeated and out-of-range entries (-1 included) are fine;
+ * excl_off = excl_items = NULL excludes nothing; t itself never counts,
+ * excluded or not, exactly as for acf_eval_positions_multi.  With s_x the
+ * evaluation's sequential round-then-add dot product of P[users[r]] and Q[x]
+ * and m_c = s_t - s_c (one rounded fp32 subtraction),
+ *   worst[e * n_users + r] = #{ c in C_r, c != t : m_c <= thr_e(c) }
+ *   side 0 (user): the attacker adds any delta with |delta|_2 <= eps_e to the
+ *     user row.  thr_e(c) = eps_e * D_c, D_c = sqrtf(D2), D2 = the sum over k
+ *     ascending from +0.0 of round((Q[t][k] - Q[c][k])^2): identical rows give 0.
+ *   side 1 (item): the attacker adds to EVERY item row its own delta with
+ *     |delta|_2 <= eps_e.  thr_e = (2 eps_e) * Np, Np = sqrtf(N2), N2 = the same
+ *     chain over P[users[r]][k]^2.
+ * All of it fp32, every operation rounded on its own, the square roots
+ * correctly rounded.  Candidate c can be brought to score >= t within the
+ * budget iff its inequality holds, and one perturbation has to satisfy the
+ * inequality of every candidate it lifts, so no perturbation within the budget
+ * puts more than worst candidates at or above t: worst < K certifies t in the
+ * top K, and a metric that does not increase with the position, taken at
+ * worst, is a lower bound under every such attack.  eps = 0 gives
+ * acf_eval_positions_multi's positions; both thresholds grow with eps, so worst
+ * does not decrease in eps.  A count depends on (u, t, C_r, P, Q, eps_e) only.
+ * eps: a HOST array of 1 <= n_eps <= 8 finite values >= 0; the candidates are
+ * swept once whatever n_eps.  Exact integers, identical bits run to run; no
+ * [n_users, num_candidates] array is formed.  `worst`: device int32
+ * [n_eps][n_users].  `workspace`: device memory, 4-byte aligned, at least
+ * acf_eval_positions_worst_workspace(n_users, num_candidates, n_eps) bytes -- a
+ * host-only query that touches no device; a smaller one is ACF_E_INVALID, as
+ * are n_eps outside [1, 8], a negative or non-finite eps and a side other than
+ * 0 or 1, all before any launch.  1 <= num_candidates <= num_item_rows;
+ * n_users = 0 does nothing.  A user outside [0, num_user_rows) or a test item
+ * outside [0, num_item_rows) is read as row 0; with check != 0 the call then
+ * synchronises once, after its launches, and returns ACF_E_RANGE (check == 0:
+ * no error, no sync).  Tables are assumed finite. */
+int acf_eval_positions_worst_workspace(int32_t n_users, int32_t num_candidates, int32_t n_eps, size_t* bytes);
+int acf_eval_positions_worst(const float* P, const float* Q, int64_t num_user_rows, int64_t num_item_rows,
+                             int32_t dim, const int32_t* users, const int32_t* test_items, int32_t n_users,
+                             int32_t num_candidates, const int64_t* excl_off, const int32_t* excl_items,
+                             const float* eps, int32_t n_eps, int32_t side, int32_t* worst, void* workspace,
+                             size_t workspace_bytes, int32_t check, void* stream);
+
 /* ---- robustness evaluation: a whole-stream adversarial direction ------------
  * utils.py:145-154 (adv_update): ONE delta over all n triplets as one batch, as
  * dense tables.  acf_adv_direction fills EVERY row of the unit-direction tables
