@@ -78,6 +78,9 @@ SIGNATURES = {
     "acf_recommend_topk_workspace": (ctypes.c_int, [_I32, _I32, _I32, _I32, ctypes.POINTER(ctypes.c_size_t)]),
     "acf_recommend_topk": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _I32, _I32, _P, _P, _I32, _P, _P, _P,
                                           ctypes.c_size_t, _I32, _P]),
+    "acf_neighbors_topk_workspace": (ctypes.c_int, [_I32, _I32, _I32, ctypes.POINTER(ctypes.c_size_t)]),
+    "acf_neighbors_topk": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P,
+                                          _P, ctypes.c_size_t, _I32, _P]),
     "acf_eval_positions_multi_workspace": (ctypes.c_int, [_I32, _I64, _I32, ctypes.POINTER(ctypes.c_size_t)]),
     "acf_eval_positions_multi": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _P, _I32, _I64, _I32, _P, _P, _P,
                                                 _P, ctypes.c_size_t, _I32, _P]),

@@ -34,7 +34,7 @@ LIBS = {
                         f"{PKG}/csrc/acf_eval.h", f"{PKG}/csrc/acf_topk.h", f"{PKG}/csrc/acf_adv.h",
                         f"{PKG}/csrc/acf_fold.h", f"{PKG}/csrc/acf_topk_select.h",
                         f"{PKG}/csrc/acf_eval_multi.h", f"{PKG}/csrc/acf_sweep.h",
-                        f"{PKG}/csrc/acf_eval_worst.h"]},
+                        f"{PKG}/csrc/acf_eval_worst.h", f"{PKG}/csrc/acf_neighbors.h"]},
     "neumf": {"lib": f"{PKG}/lib/libacf_neumf.so",
               "srcs": [f"{PKG}/csrc/acf_neumf.hip"],
               "headers": ["include/acf_apr.h", "include/acf_neumf.h", f"{PKG}/csrc/acf_topk_select.h"]},

@@ -86,9 +86,17 @@ def parse_args(argv=None, flavor="ori"):
                         "ndcg, map at every --cutoffs K, then mrr, auc, n_users).")
     p.add_argument("--cutoffs", type=parse_cutoffs, default=[10, 50, 100],
                    help="The K of --test_multi's metrics: up to 8 integers in [1, 1024], comma separated.")
+    p.add_argument("--similar", type=str, default=None, metavar="FILE",
+                   help="After training, write the --topk items most like each item of FILE (one item id per line) "
+                        "to <out>/<runName>.similar: line n is for the n-th id of FILE, in --topk's format; an item "
+                        "is never its own neighbour.  Needs --topk.")
+    p.add_argument("--similar_metric", choices=["dot", "cosine", "euclid"], default="cosine",
+                   help="The similarity of --similar: cosine, the dot product, or euclid (nearest by L2 distance).")
     args = p.parse_args(argv)
     if args.fold_in is not None and args.topk <= 0:
         p.error("--fold_in needs --topk K (K > 0)")
+    if args.similar is not None and args.topk <= 0:
+        p.error("--similar needs --topk K (K > 0)")
     return args
 
 
@@ -216,6 +224,24 @@ def read_fold_file(file):
     return lists
 
 
+def read_id_file(file):
+    """The ids of a file with one integer >= 0 per line (blank lines skipped)."""
+    ids = []
+    with open(file) as f:
+        for n, line in enumerate(f):
+            line = line.strip()
+            if not line:
+                continue
+            try:
+                v = int(line)
+            except ValueError:
+                raise ValueError(f"{file}: line {n}: not an integer: {line!r}") from None
+            if v < 0:
+                raise ValueError(f"{file}: line {n}: an id must be >= 0, got {v}")
+            ids.append(v)
+    return ids
+
+
 def write_fold_users(path, name, keys):
     """One uid per line, in the row order of the .foldin.topk file."""
     os.makedirs(path, exist_ok=True)
@@ -307,6 +333,11 @@ def main(argv=None, flavor="ori"):
         items, _ = recommend_new(final, lists, args.topk, seed=args.seed, batch=min(args.batch_size, 512))
         write_topk(out, runName + ".foldin.topk", items)
         write_fold_users(out, runName + ".foldin.users", sorted(lists))
+    if args.similar is not None:
+        from .evaluate import similar_items
+        final = amf if args.model == "apr" else m
+        items, _ = similar_items(final, read_id_file(args.similar), k=args.topk, metric=args.similar_metric)
+        write_topk(out, runName + ".similar", items)  # line n: the n-th id of FILE
     if args.test_multi is not None:
         from .data import load_test_lists
         from .evaluate import evaluate_multi, init_eval_multi

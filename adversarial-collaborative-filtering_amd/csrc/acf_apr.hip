@@ -3580,6 +3580,7 @@ __global__ void __launch_bounds__(256) k_forward(const float* __restrict__ P,
 #include "acf_sweep.h"  // seq_dot and the score sweep the ranking kernels share: DESIGN.md §4
 #include "acf_eval.h"  // all-items evaluation (k_eval_*): DESIGN.md §4
 #include "acf_topk.h"  // top-K recommendation lists (k_topk_*): DESIGN.md §4b
+#include "acf_neighbors.h"  // nearest-neighbour lists (k_nbr_*): DESIGN.md §4h
 #include "acf_adv.h"   // whole-stream adversarial direction (k_adv_*): DESIGN.md §4c
 #include "acf_eval_multi.h"  // multi-item evaluation and rank metrics (k_evx_*): DESIGN.md §4f
 #include "acf_eval_worst.h"  // certified worst-case positions (k_evw_*): DESIGN.md §4g
@@ -5711,6 +5712,79 @@ extern "C" int acf_recommend_topk(const float* P, const float* Q, int64_t U1, in
   HIP_TRY(hipGetLastError());
   k_topk_merge<<<(unsigned)n_users, 256, 0, s>>>(ws, S, k, out_items, out_scores);
   HIP_TRY(hipGetLastError());
+  return ACF_OK;
+}
+
+// ---- nearest-neighbour lists (acf_neighbors.h) ---------------------------------
+static int nbr_check(int32_t n_q, int32_t num_cand, int32_t k) {
+  ACF_CHECK(k >= 1 && k <= TOPK_MAX_K, ACF_E_INVALID, "k must be in [1, %d], got %d", TOPK_MAX_K, k);
+  ACF_CHECK(n_q >= 0 && num_cand >= 0, ACF_E_INVALID, "negative size");
+  return ACF_OK;
+}
+
+extern "C" int acf_neighbors_topk_workspace(int32_t n_q, int32_t num_cand, int32_t k, size_t* bytes) {
+  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
+  ACF_RET(nbr_check(n_q, num_cand, k));
+  *bytes = nbr_workspace(n_q, num_cand, k, true);
+  return ACF_OK;
+}
+
+template <int METRIC>
+static int launch_nbr(const float* T, const float* X, int d, int64_t XR, const int32_t* queries, int n_q,
+                      int num_cand, int exclude_self, const int64_t* excl_off, const int32_t* excl,
+                      const float* cnorm, int K, int wper, int S, uint64_t* lists, int32_t* err, hipStream_t s) {
+  // 32 KB of keys + 8 rows: above the 64 KB default from d = 1024 (set per call, as topk_lds_optin)
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nbr_valu<METRIC>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)(TKV_UB * TKV_CAP * sizeof(uint64_t) + TKV_UB * 1024 * sizeof(float))));
+  const size_t lds = (size_t)TKV_UB * TKV_CAP * sizeof(uint64_t) + (size_t)TKV_UB * d * sizeof(float);
+  const dim3 grid((unsigned)((n_q + TKV_UB - 1) / TKV_UB), (unsigned)S);
+  k_nbr_valu<METRIC><<<grid, 256, lds, s>>>(T, X, d, XR, queries, n_q, num_cand, exclude_self, excl_off, excl, cnorm,
+                                            K, wper, S, lists, err);
+  HIP_TRY(hipGetLastError());
+  return ACF_OK;
+}
+
+extern "C" int acf_neighbors_topk(const float* T, int64_t TR, int32_t d, const float* X, int64_t XR,
+                                  const int32_t* queries, int32_t n_q, int32_t num_cand, int32_t metric,
+                                  int32_t exclude_self, const int64_t* excl_off, const int32_t* excl, int32_t k,
+                                  int32_t* out_items, float* out_scores, void* workspace, size_t workspace_bytes,
+                                  int32_t check, void* stream_) {
+  ACF_RET(check_dim(d));
+  ACF_RET(nbr_check(n_q, num_cand, k));
+  ACF_CHECK(metric >= NBR_DOT && metric <= NBR_EUC, ACF_E_INVALID,
+            "metric must be 0 (dot), 1 (cosine) or 2 (Euclidean), got %d", metric);
+  ACF_CHECK(TR > 0 && XR > 0, ACF_E_INVALID, "empty table");
+  ACF_CHECK(num_cand <= TR, ACF_E_INVALID, "num_candidates %d > table rows", num_cand);
+  ACF_CHECK(T && X && queries && out_items && out_scores && workspace, ACF_E_INVALID, "NULL argument");
+  ACF_CHECK((excl_off == nullptr) == (excl == nullptr), ACF_E_INVALID, "excl_off and excl_items go together");
+  ACF_CHECK(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, ACF_E_INVALID, "workspace must be 8-byte aligned");
+  int wper = 0, S = 0;
+  const size_t lists_bytes = nbr_lists_bytes(n_q, num_cand, k, &wper, &S);
+  const size_t need = nbr_workspace(n_q, num_cand, k, metric == NBR_COS);
+  ACF_CHECK(workspace_bytes >= need, ACF_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+  if (n_q == 0) return ACF_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  int32_t* err = static_cast<int32_t*>(workspace);
+  uint64_t* lists = reinterpret_cast<uint64_t*>(static_cast<char*>(workspace) + NBR_WS_HEAD);
+  float* cnorm = reinterpret_cast<float*>(static_cast<char*>(workspace) + NBR_WS_HEAD + lists_bytes);
+  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+  if (metric == NBR_COS && num_cand > 0) {
+    k_nbr_norms<<<grid_for(num_cand), 256, 0, s>>>(T, d, num_cand, cnorm);
+    HIP_TRY(hipGetLastError());
+  }
+  const auto launch = metric == NBR_DOT ? &launch_nbr<NBR_DOT> : metric == NBR_COS ? &launch_nbr<NBR_COS>
+                                                                                   : &launch_nbr<NBR_EUC>;
+  ACF_RET(launch(T, X, d, XR, queries, n_q, num_cand, exclude_self != 0, excl_off, excl, cnorm, k, wper, S, lists,
+                 err, s));
+  k_topk_merge<<<(unsigned)n_q, 256, 0, s>>>(lists, S, k, out_items, out_scores);
+  HIP_TRY(hipGetLastError());
+  if (check) {
+    int32_t herr = 0;
+    HIP_TRY(hipMemcpyAsync(&herr, err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    ACF_CHECK(herr == 0, ACF_E_RANGE, "index out of range (query >= num_query_rows)");
+  }
   return ACF_OK;
 }
 

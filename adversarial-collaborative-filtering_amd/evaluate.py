@@ -442,6 +442,51 @@ def recommend_new(model_or_tables, lists, k: int, **fold_args):
     return items.cpu().numpy(), scores.cpu().numpy()
 
 
+# ---- nearest neighbours: similar items, similar users -----------------------
+def _neighbor_tables(model_or_tables):
+    """(P, Q, num_users, num_items) of an MF-like model or a (P, Q) pair.  A
+    model's tables carry one padding row past its users / items (APR.py:108,111:
+    [U + 1, d] / [I + 1, d]), which the counts keep out of the candidates; a bare
+    pair has no counts, so every row is a candidate unless the caller says
+    otherwise."""
+    m = model_or_tables
+    if hasattr(m, "embedding_P"):
+        P, Q = m.embedding_P, m.embedding_Q
+        return P, Q, min(int(m.num_users), P.shape[0]), min(int(m.num_items), Q.shape[0])
+    return m[0], m[1], m[0].shape[0], m[1].shape[0]
+
+
+def similar_items(model_or_tables, items, k: int = 10, metric: str = "cosine", num_candidates=None):
+    """The k items most like each item of `items` (rows of the item table), on
+    the GPU (ops.neighbors_topk): (ids int32 [n, k], scores float32 [n, k]) numpy
+    arrays, best first, -1 / -inf past the candidates.  metric: 'cosine', 'dot'
+    or 'euclid' (minus the squared distance).  An item is never its own
+    neighbour, and the table's padding row (a model's row num_items) is never a
+    candidate: the candidates are [0, num_candidates), default the model's
+    num_items (a (P, Q) pair: every row of Q)."""
+    _, Q, _, n_items = _neighbor_tables(model_or_tables)
+    n_items = int(n_items if num_candidates is None else num_candidates)
+    items = np.asarray(items, dtype=np.int64).reshape(-1)
+    ids, scores = ops.neighbors_topk(Q, items.astype(np.int32), int(k), metric, num_candidates=n_items,
+                                     exclude_self=True)
+    return ids.cpu().numpy(), scores.cpu().numpy()
+
+
+def similar_users(model_or_tables, users, k: int = 10, metric: str = "cosine", rows=None):
+    """The k users most like each user of `users` (rows of the user table), as
+    similar_items: a user is never its own neighbour and the padding row (a
+    model's row num_users) is never a candidate.  rows: a [m, d] device tensor
+    of other rows, for example a FoldIn's P (or the FoldIn itself); `users` then
+    index `rows`, the candidates are still the model's users, and nothing is
+    self-excluded (row j of `rows` is not user j)."""
+    P, _, n_users, _ = _neighbor_tables(model_or_tables)
+    users = np.asarray(users, dtype=np.int64).reshape(-1)
+    X = rows.P if isinstance(rows, FoldIn) else rows
+    ids, scores = ops.neighbors_topk(P, users.astype(np.int32), int(k), metric, X=X, num_candidates=int(n_users),
+                                     exclude_self=X is None)
+    return ids.cpu().numpy(), scores.cpu().numpy()
+
+
 # ---- several held-out items per user ----------------------------------------
 CUT_METRICS = ("hit", "recall", "precision", "ndcg", "map")  # ops.RANK_CUT_METRICS
 FREE_METRICS = ("mrr", "auc")                                # ops.RANK_FREE_METRICS

@@ -97,6 +97,12 @@ class FastAdversarialMF(Recommender):
     def iEmb(self) -> torch.Tensor:
         return self.params[self.uNum * self.dim: (self.uNum + self.iNum) * self.dim].view(self.iNum, self.dim)
 
+    def neighbor_tables(self):
+        """uEmb / iEmb as evaluate.similar_items / similar_users take them (no padding rows)."""
+        from types import SimpleNamespace
+        return SimpleNamespace(embedding_P=self.uEmb, embedding_Q=self.iEmb, num_users=self.uNum,
+                               num_items=self.iNum)
+
     def discriminator(self, which: str) -> dict:
         """Views of D_u ("user") / D_i ("item"): W1 [d, d], b1 [d], W2 [d], b2 [1]."""
         d = self.dim

@@ -58,6 +58,12 @@ class BPR(Recommender):
     def iEmb(self) -> torch.Tensor:
         return self.params[self.uNum * self.dim:].view(self.iNum, self.dim)
 
+    def neighbor_tables(self):
+        """uEmb / iEmb as evaluate.similar_items / similar_users take them (no padding rows)."""
+        from types import SimpleNamespace
+        return SimpleNamespace(embedding_P=self.uEmb, embedding_Q=self.iEmb, num_users=self.uNum,
+                               num_items=self.iNum)
+
     def _context(self, batch):
         if batch > self._ctx_batch:
             if self._ctx:

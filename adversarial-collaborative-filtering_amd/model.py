@@ -217,6 +217,19 @@ class MF:
         from .evaluate import recommend_new
         return recommend_new(self, lists, k, **fold_args)
 
+    def similar_items(self, items, k=10, metric="cosine"):
+        """evaluate.similar_items: the k items nearest to each of `items` in the
+        item table ('cosine', 'dot' or 'euclid'): (ids [n, k], scores [n, k])
+        numpy arrays; never the item itself, never the padding row."""
+        from .evaluate import similar_items
+        return similar_items(self, items, k=k, metric=metric)
+
+    def similar_users(self, users, k=10, metric="cosine", rows=None):
+        """evaluate.similar_users: the k users nearest to each of `users`; with
+        rows (a FoldIn or a [m, d] tensor) the queries are those rows instead."""
+        from .evaluate import similar_users
+        return similar_users(self, users, k=k, metric=metric, rows=rows)
+
     def evaluate_multi(self, plan, cutoffs=(10, 50, 100), raw=False):
         """evaluate.evaluate_multi: recall / ndcg / map / ... @K, mrr and auc against
         several held-out items per user (plan: evaluate.init_eval_multi)."""

@@ -425,6 +425,14 @@ class NeuMF:
         _, items, scores = self._context(1).rank_all(users, int(k), self.iNum - 1, off, ex)
         return items.cpu().numpy(), scores.cpu().numpy()
 
+    def similar_items(self, items, k=10, metric="cosine"):
+        raise NotImplementedError("NeuMF has two item tables (the GMF and the MLP embeddings) that only the "
+                                  "network combines, so there is no single similarity between two items.")
+
+    def similar_users(self, users, k=10, metric="cosine", rows=None):
+        raise NotImplementedError("NeuMF has two user tables (the GMF and the MLP embeddings) that only the "
+                                  "network combines, so there is no single similarity between two users.")
+
     def positions_all(self, users, test_items, train):
         """Per user the number of candidates scoring >= the user's test item, the
         candidates being every item except 0, the user's train items and the test

@@ -743,6 +743,82 @@ def recommend_topk(P, Q, users, k: int, num_candidates: int | None = None, excl_
     return items, scores
 
 
+NEIGHBOR_METRICS = {"dot": 0, "cosine": 1, "euclid": 2}  # NBR_DOT, NBR_COS, NBR_EUC
+
+
+def _neighbor_k(k):
+    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f"k must be an int in [1, {TOPK_MAX_K}], got {k!r}")
+
+
+def neighbors_topk_workspace(n_queries: int, num_candidates: int, k: int) -> int:
+    """Bytes of device workspace acf_neighbors_topk needs (a host-only query): a
+    16-byte head, the strips' partial lists and the num_candidates floats of
+    candidate norms the cosine metric uses."""
+    _neighbor_k(k)
+    size = ctypes.c_size_t()
+    call("acf_neighbors_topk_workspace", int(n_queries), int(num_candidates), int(k), ctypes.byref(size))
+    return int(size.value)
+
+
+def neighbors_topk(T, queries, k: int, metric: str = "cosine", X=None, num_candidates: int | None = None,
+                   exclude_self: bool = True, excl_off=None, excl_items=None, check: bool = True):
+    """The k nearest rows of T per query: (items int32 [n, k], scores float32
+    [n, k]).  Query j is row queries[j] of X (default: T itself); its candidates
+    are rows [0, num_candidates) of T (default: every row) minus the set of
+    excl_items[excl_off[j]:excl_off[j+1]] (unsorted, repeated and out-of-range
+    entries are fine; no exclusion arguments: nothing is excluded) and, with
+    exclude_self, minus the row whose id equals queries[j].  metric: 'dot'
+    (recommend_topk's score bit for bit), 'cosine' (s / (|a| |b|), +0.0 for a
+    zero row) or 'euclid' (minus the squared distance: larger is nearer), in
+    fp32 as include/acf_apr.h states; ordered by score descending, ties to the
+    lower id, -1 / -inf past the last candidate.  Exact and bit-identical run
+    to run; no [n, num_candidates] array and no normalised copy of T is formed.
+    Bad shapes, k and metric raise ValueError / TypeError before any native
+    call; with check, a query outside X raises NativeIndexError (one sync),
+    without it such a query is read as row 0."""
+    _neighbor_k(k)
+    if metric not in NEIGHBOR_METRICS:
+        raise ValueError(f"metric must be one of {sorted(NEIGHBOR_METRICS)}, got {metric!r}")
+    _require(T, "T", torch.float32, None, 2)
+    dev = T.device
+    if X is None:
+        X = T
+    else:
+        _require(X, "X", torch.float32, dev, 2)
+        if X.shape[1] != T.shape[1]:
+            raise ValueError("T and X dims differ")
+    settle_tables()
+    q = _idx(queries, "queries", dev)
+    n = q.numel()
+    if num_candidates is None:
+        num_candidates = T.shape[0]
+    num_candidates = int(num_candidates)
+    if not 0 <= num_candidates <= T.shape[0]:
+        raise ValueError("num_candidates must lie in [0, table rows]")
+    if (excl_off is None) != (excl_items is None):
+        raise ValueError("excl_off and excl_items go together")
+    off = ex = None
+    if excl_off is not None:
+        off = torch.as_tensor(excl_off).to(device=dev, dtype=torch.int64).contiguous()
+        ex = (_idx(excl_items, "excl_items", dev) if len(excl_items)
+              else torch.zeros(1, dtype=torch.int32, device=dev))
+        if off.numel() != n + 1:
+            raise ValueError("excl_off must have len(queries) + 1 entries")
+    items = torch.empty((n, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+    if n == 0:
+        return items, scores
+    nbytes = neighbors_topk_workspace(n, num_candidates, k)
+    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    with _on(dev):
+        call("acf_neighbors_topk", T.data_ptr(), T.shape[0], T.shape[1], X.data_ptr(), X.shape[0], q.data_ptr(), n,
+             num_candidates, NEIGHBOR_METRICS[metric], int(bool(exclude_self)),
+             off.data_ptr() if off is not None else None, ex.data_ptr() if ex is not None else None, k,
+             items.data_ptr(), scores.data_ptr(), work.data_ptr(), nbytes, int(bool(check)), _stream_ptr(dev))
+    return items, scores
+
+
 RANK_MAX_CUTOFFS, RANK_MAX_K = 8, 1024          # EVX_MAX_CUT, EVX_MAX_K
 RANK_CUT_METRICS = ("hit", "recall", "precision", "ndcg", "map")
 RANK_FREE_METRICS = ("mrr", "auc")

@@ -46,6 +46,26 @@ class Recommender(ABC):
     def get_train_instances(self, train):
         pass
 
+    # -- nearest neighbours (not in the reference; MF-shaped recommenders) --------
+    def neighbor_tables(self):
+        """What evaluate.similar_items / similar_users take: an object with
+        embedding_P, embedding_Q, num_users and num_items.  A recommender with one
+        user table and one item table in the same space overrides this."""
+        raise NotImplementedError(f"{type(self).__name__} has no single user / item table to compare rows of")
+
+    def similar_items(self, items, k=10, metric="cosine"):
+        """evaluate.similar_items on the recommender's item table: the k items
+        nearest to each of `items` ('cosine', 'dot' or 'euclid'), never the item
+        itself: (ids [n, k] int32, scores [n, k] float32) numpy arrays."""
+        from .evaluate import similar_items
+        return similar_items(self.neighbor_tables(), items, k=k, metric=metric)
+
+    def similar_users(self, users, k=10, metric="cosine", rows=None):
+        """evaluate.similar_users on the recommender's user table; with rows (a
+        FoldIn or a [m, d] tensor) the queries are those rows instead."""
+        from .evaluate import similar_users
+        return similar_users(self.neighbor_tables(), users, k=k, metric=metric, rows=rows)
+
 
 class APR(Recommender):
     """BPR-MF (adver=False) or APR (adver=True) behind the Recommender API."""
@@ -126,6 +146,11 @@ class APR(Recommender):
     def rank(self, users, items):
         self._ensure()
         return self.model.scores(np.asarray(users).reshape(-1), np.asarray(items).reshape(-1))
+
+    def neighbor_tables(self):
+        """The model: tables of uNum + 1 / iNum + 1 rows, the last one padding."""
+        self._ensure()
+        return self.model
 
     def recommend(self, users, k, train=None):
         """The k best items of each user among [0, iNum): (items [n, k] int32,

@@ -375,6 +375,57 @@ int acf_recommend_topk(const float* P, const float* Q, int64_t num_user_rows, in
                        int32_t* out_items, float* out_scores, void* workspace, size_t workspace_bytes,
                        int32_t kernel, void* stream);
 
+/* ---- nearest-neighbour lists: similar items, similar users -----------------
+ * (no reference counterpart.)  Query r is row queries[r] of the query table X
+ * [num_query_rows, dim] (any order, repeats allowed; X may be T itself); its
+ * candidates are the rows [0, num_candidates) of T [num_rows, dim] minus the SET
+ * of excl_items[excl_off[r] .. excl_off[r+1]) -- unsorted, repeated and
+ * out-of-range entries (-1 included) are ignored; excl_off = excl_items = NULL
+ * excludes nothing -- and, with exclude_self != 0, minus the candidate whose id
+ * equals queries[r] (the query itself when X == T; for another X just that id).
+ * Self-exclusion is decided inside the kernel: no per-query list is built.
+ * With a = X[queries[r]], b = T[c] and s = the evaluation's sequential
+ * round-then-add dot product of a and b (acf_recommend_topk's score):
+ *   metric 0 (dot):       score = s.  With X == T, exclude_self = 0 and no
+ *     lists the output equals acf_recommend_topk(T, T, ...) bit for bit.
+ *   metric 1 (cosine):    na = sqrtf(s(a, a)), nb = sqrtf(s(b, b)), den = na *
+ *     nb; score = den > 0 ? (s / den) + 0.0f : +0.0f.  A zero row scores +0.0
+ *     against everything.
+ *   metric 2 (Euclidean): score = 0.0f - D2, D2 = the sum over k ascending from
+ *     +0.0 of round((a[k] - b[k])^2), acf_eval_positions_worst's chain: a larger
+ *     score is a nearer row, identical rows give +0.0.
+ * All of it fp32, every operation rounded on its own, the square roots and the
+ * division correctly rounded.  No score is ever -0.0, which the 64-bit
+ * (score, id) key of the selection relies on: s never is (the chain starts at
+ * +0.0); a quotient that underflows on the negative side is -0.0 and the
+ * "+ 0.0f" makes it +0.0 while changing no other value; D2 >= +0.0, so
+ * 0.0f - D2 is +0.0 exactly for D2 = +0.0, the only case in which that
+ * subtraction yields a zero.
+ * The order is score descending by float comparison, ties to the ascending id;
+ * out_items / out_scores [n_queries, k] receive the first k candidates in that
+ * order, -1 / -inf past the last candidate.  1 <= k <= 128.  A query's list
+ * depends only on that query's inputs.  Exact and deterministic: identical bits
+ * run to run, no float atomics; no [n_queries, num_candidates] array and no
+ * normalised copy of T is formed.  `workspace`: device memory, 8-byte aligned:
+ * a 16-byte head, the strips' partial lists (n_queries * S * k * 8 bytes, as
+ * for acf_recommend_topk's VALU sweep) and, used by metric 1 only,
+ * num_candidates floats of candidate norms computed once per call.
+ * acf_neighbors_topk_workspace reports all three together -- a host-only query
+ * that touches no device and has no metric argument; metrics 0 and 2 accept a
+ * workspace without the norms.  A smaller workspace, a metric outside 0..2 and
+ * k outside [1, 128] are ACF_E_INVALID before any launch.  0 <= num_candidates
+ * <= num_rows; n_queries = 0 does nothing.  A query outside [0, num_query_rows)
+ * is read as row 0 (and is id 0 for exclude_self); with check != 0 the call
+ * then synchronises once, after its launches, and returns ACF_E_RANGE
+ * (check == 0: no error, no sync).  Tables are assumed finite: with a NaN
+ * score the order is unspecified. */
+int acf_neighbors_topk_workspace(int32_t n_queries, int32_t num_candidates, int32_t k, size_t* bytes);
+int acf_neighbors_topk(const float* T, int64_t num_rows, int32_t dim, const float* X, int64_t num_query_rows,
+                       const int32_t* queries, int32_t n_queries, int32_t num_candidates, int32_t metric,
+                       int32_t exclude_self, const int64_t* excl_off, const int32_t* excl_items, int32_t k,
+                       int32_t* out_items, float* out_scores, void* workspace, size_t workspace_bytes,
+                       int32_t check, void* stream);
+
 /* ---- evaluation against several held-out items per user --------------------
  * (no reference counterpart: the reference holds out one item per user.)
  * Entry r (row users[r] of P; any order, repeats allowed) has the test list
