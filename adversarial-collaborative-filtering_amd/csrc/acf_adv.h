@@ -1,5 +1,5 @@
 // Whole-stream adversarial direction kernels of libacf_apr.so (k_adv_*): included
-// by acf_apr.hip after acf_topk.h (seq_dot, bpr_term, random_delta, the row
+// by acf_rank.hip after acf_topk.h (seq_dot; bpr_term, random_delta and the row
 // helpers); one translation unit.  DESIGN.md §4c.
 //
 // acf_adv_direction, grad mode: the clean-loss gradient of ALL n triplets as one

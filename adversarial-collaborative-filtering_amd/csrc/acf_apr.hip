@@ -53,13 +53,14 @@
 #include <vector>
 
 #include "acf_apr.h"
+#include "acf_host.h"  // HIP_TRY, ACF_CHECK, ACF_RET, grid_for, geometry, DISPATCH_GEOM, check_dim
 
 // ---------------------------------------------------------------------------
-// error plumbing
+// error plumbing: the library's one thread-local message (every translation unit: acf_host.h)
 // ---------------------------------------------------------------------------
 static thread_local std::string g_last_error;
 
-static int set_error(int code, const char* fmt, ...) {
+int acf_set_error(int code, const char* fmt, ...) {
   char buf[1024];
   va_list ap;
   va_start(ap, fmt);
@@ -68,29 +69,6 @@ static int set_error(int code, const char* fmt, ...) {
   g_last_error = buf;
   return code;
 }
-
-// for the other translation units of the library (acf_ops.hip)
-int acf_set_error(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_last_error = buf;
-  return code;
-}
-
-#define HIP_TRY(expr)                                                          \
-  do {                                                                         \
-    hipError_t e_ = (expr);                                                    \
-    if (e_ != hipSuccess)                                                      \
-      return set_error(ACF_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
-
-#define ACF_CHECK(cond, code, ...)                                             \
-  do {                                                                         \
-    if (!(cond)) return set_error((code), __VA_ARGS__);                        \
-  } while (0)
 
 // ---------------------------------------------------------------------------
 // device helpers (row groups, the TF-order dot product, BPR term, RNG)
@@ -1653,29 +1631,6 @@ struct Geo {
     tl = lane - leader;
   }
 };
-
-// "random" delta: l2_normalize(truncated_normal(0, 0.01)) * eps, redrawn every
-// run (APR.py:180-191, adv == "random").  Out of line: the gradient mode never
-// runs it and it would otherwise bloat every step kernel's instruction stream.
-template <int LPR, int NV>
-__device__ __noinline__ RowV<NV> random_delta(uint64_t seed, uint32_t call, int32_t t, int32_t d, float eps,
-                                              int is_item, int32_t row, int l) {
-  RowV<NV> z;
-  const uint64_t rk = mix64(seed ^ mix64(((uint64_t)call << 33) ^ (((uint64_t)t << 1) | (is_item ? 1 : 0)))) ^
-                      mix64((uint64_t)row * 0x100000001B3ull);
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    const int c = l + LPR * v;
-    float e4[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      e4[e] = (c * 4 + e < d) ? trunc_normal(rk ^ mix64((uint64_t)(c * 4 + e)), 0.01f) : 0.f;
-    z.v[v] = make_float4(e4[0], e4[1], e4[2], e4[3]);
-  }
-  const float ss = dot_row<LPR, NV>(z, z);
-  const float inv = __builtin_amdgcn_rsqf(fmaxf(ss, 1e-12f));
-  return scale_row(scale_row(z, inv), eps);
-}
 
 // delta of one row from its batch-summed clean gradient G (APR.py:180-191)
 template <int LPR, int NV>
@@ -3577,14 +3532,6 @@ __global__ void __launch_bounds__(256) k_forward(const float* __restrict__ P,
   }
 }
 
-#include "acf_sweep.h"  // seq_dot and the score sweep the ranking kernels share: DESIGN.md §4
-#include "acf_eval.h"  // all-items evaluation (k_eval_*): DESIGN.md §4
-#include "acf_topk.h"  // top-K recommendation lists (k_topk_*): DESIGN.md §4b
-#include "acf_neighbors.h"  // nearest-neighbour lists (k_nbr_*): DESIGN.md §4h
-#include "acf_adv.h"   // whole-stream adversarial direction (k_adv_*): DESIGN.md §4c
-#include "acf_eval_multi.h"  // multi-item evaluation and rank metrics (k_evx_*): DESIGN.md §4f
-#include "acf_eval_worst.h"  // certified worst-case positions (k_evw_*): DESIGN.md §4g
-
 // ---------------------------------------------------------------------------
 // sampler (shuffle / _get_train_batch, APR.py:39-81)
 // ---------------------------------------------------------------------------
@@ -3842,55 +3789,10 @@ static int dalloc(acf_apr_ctx* c, T** p, size_t n) {
   void* q = nullptr;
   if (hipMalloc(&q, n * sizeof(T) + 16) != hipSuccess) {
     (void)hipGetLastError();
-    return set_error(ACF_E_NOMEM, "hipMalloc of %zu bytes failed", n * sizeof(T));
+    return acf_set_error(ACF_E_NOMEM, "hipMalloc of %zu bytes failed", n * sizeof(T));
   }
   c->allocs.push_back(q);
   *p = static_cast<T*>(q);
-  return ACF_OK;
-}
-
-#define ACF_RET(x)                  \
-  do {                              \
-    int r_ = (x);                   \
-    if (r_ != ACF_OK) return r_;    \
-  } while (0)
-
-static inline unsigned grid_for(int64_t n, int bs = 256) {
-  return (unsigned)((n + bs - 1) / bs);
-}
-
-// Row-group geometry for a given dim: LPR lanes per row, NV float4 per lane.
-static void geometry(int d, int* lpr, int* nv) {
-  int d4 = d / 4;
-  int l = 1;
-  while (l < d4 && l < 64) l <<= 1;
-  *lpr = l;
-  *nv = (d4 + l - 1) / l;
-}
-
-#define DISPATCH_GEOM(d, KFN, ...)                                                    \
-  [&]() -> int {                                                                    \
-    int lpr_, nv_;                                                                  \
-    geometry((d), &lpr_, &nv_);                                                     \
-    switch (lpr_ * 100 + nv_) {                                                     \
-      case 101: KFN<1, 1>(__VA_ARGS__); break;                                      \
-      case 201: KFN<2, 1>(__VA_ARGS__); break;                                      \
-      case 401: KFN<4, 1>(__VA_ARGS__); break;                                      \
-      case 801: KFN<8, 1>(__VA_ARGS__); break;                                      \
-      case 1601: KFN<16, 1>(__VA_ARGS__); break;                                    \
-      case 3201: KFN<32, 1>(__VA_ARGS__); break;                                    \
-      case 6401: KFN<64, 1>(__VA_ARGS__); break;                                    \
-      case 6402: KFN<64, 2>(__VA_ARGS__); break;                                    \
-      case 6403: KFN<64, 3>(__VA_ARGS__); break;                                    \
-      case 6404: KFN<64, 4>(__VA_ARGS__); break;                                    \
-      default: return set_error(ACF_E_INVALID, "unsupported dim %d", (int)(d));     \
-    }                                                                               \
-    return ACF_OK;                                                                  \
-  }()
-
-static int check_dim(int d) {
-  ACF_CHECK(d >= 4 && d <= 1024 && d % 4 == 0, ACF_E_INVALID,
-            "dim must be a multiple of 4 in [4, 1024], got %d", d);
   return ACF_OK;
 }
 
@@ -3984,14 +3886,14 @@ extern "C" int acf_apr_create(acf_apr_ctx** out, int64_t U1, int64_t I1, int32_t
       rocprim::inclusive_scan(nullptr, b4, c->key_in, c->key_out, (size_t)(3 * maxE),
                               rocprim::plus<uint64_t>()) != hipSuccess) {
     acf_apr_destroy(c);
-    return set_error(ACF_E_HIP, "rocprim temporary-storage query failed");
+    return acf_set_error(ACF_E_HIP, "rocprim temporary-storage query failed");
   }
   c->tmp_bytes = std::max(std::max(b1, b4), std::max(b2, b3));
   r = dalloc(c, reinterpret_cast<char**>(&c->tmp), c->tmp_bytes);
   if (r != ACF_OK) { acf_apr_destroy(c); return r; }
   if (hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking) != hipSuccess) {
     acf_apr_destroy(c);
-    return set_error(ACF_E_HIP, "hipStreamCreate failed");
+    return acf_set_error(ACF_E_HIP, "hipStreamCreate failed");
   }
   // generation 0 never matches a plan: zeroed inline / fused-triplet records read as absent;
   // the epoch (version tag and call counter) starts at 1: zeroed version granules never match
@@ -4004,7 +3906,7 @@ extern "C" int acf_apr_create(acf_apr_ctx** out, int64_t U1, int64_t I1, int32_t
       hipMemcpy(c->epoch, &kOne, sizeof(kOne), hipMemcpyHostToDevice) != hipSuccess || hipMemset(c->nextt, 0, 3 * maxE * sizeof(int32_t)) != hipSuccess ||
       hipDeviceSynchronize() != hipSuccess) {
     acf_apr_destroy(c);
-    return set_error(ACF_E_HIP, "hipMemset failed");
+    return acf_set_error(ACF_E_HIP, "hipMemset failed");
   }
 #ifdef ACF_DIAG  // the tail's stamps (tools/tail_diag.py): diagnostic builds only
   if (const char* e = getenv("ACF_TAIL_DIAG"))
@@ -4015,7 +3917,7 @@ extern "C" int acf_apr_create(acf_apr_ctx** out, int64_t U1, int64_t I1, int32_t
       hipDeviceSynchronize() != hipSuccess) {
     (void)hipGetLastError();
     acf_apr_destroy(c);
-    return set_error(ACF_E_NOMEM, "failure-gate allocation failed");
+    return acf_set_error(ACF_E_NOMEM, "failure-gate allocation failed");
   }
   *out = c;
   return ACF_OK;
@@ -4050,9 +3952,9 @@ static int wait_decided(const Pending& p, bool* failed) {
     const hipError_t q = hipStreamQuery(p.s);
     if (q == hipSuccess) {
       if (decided(p, failed)) return ACF_OK;
-      return set_error(ACF_E_STATE, "streamed call %u reported no outcome", p.seq);
+      return acf_set_error(ACF_E_STATE, "streamed call %u reported no outcome", p.seq);
     }
-    if (q != hipErrorNotReady) return set_error(ACF_E_HIP, "hipStreamQuery: %s", hipGetErrorString(q));
+    if (q != hipErrorNotReady) return acf_set_error(ACF_E_HIP, "hipStreamQuery: %s", hipGetErrorString(q));
     std::this_thread::yield();
   }
 }
@@ -4751,7 +4653,7 @@ static int launch(void* fn, const StepArgs& a, int waves, hipStream_t s, hipEven
                   hipEvent_t e1 = nullptr) {
   const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
   // waves past slot_waves run fused triplets: only when fusion is on
-  if (!a.use_single && a.slot_waves + a.hot_waves < waves) return set_error(ACF_E_STATE, "bad step geometry");
+  if (!a.use_single && a.slot_waves + a.hot_waves < waves) return acf_set_error(ACF_E_STATE, "bad step geometry");
   if (e0)
     hipExtLaunchKernelGGL(reinterpret_cast<StepKernel>(fn), grid, block, 0, s, e0, e1, 0, a);
   else
@@ -5126,11 +5028,11 @@ extern "C" int acf_apr_train_planned(acf_apr_ctx* c, const acf_apr_tables* tb,
     int r = run_loop(c, tb, hp, first, n, c->cap_stream, nullptr, nullptr);
     hipError_t ec = hipStreamEndCapture(c->cap_stream, &g);
     if (r != ACF_OK) { if (g) (void)hipGraphDestroy(g); return r; }
-    if (ec != hipSuccess) return set_error(ACF_E_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ec));
+    if (ec != hipSuccess) return acf_set_error(ACF_E_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ec));
     hipGraphExec_t ex = nullptr;
     hipError_t ei = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
-    if (ei != hipSuccess) return set_error(ACF_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ei));
+    if (ei != hipSuccess) return acf_set_error(ACF_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ei));
     if (c->graphs.size() >= 16) {  // bounded cache
       (void)hipGraphExecDestroy(c->graphs.begin()->second);
       c->graphs.erase(c->graphs.begin());
@@ -5162,13 +5064,13 @@ static int time_kernels(acf_apr_ctx* c, const acf_apr_tables* tb, const acf_apr_
   std::vector<int> kinds(nl, -1);
   for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
   int r = run_loop(c, tb, hp, first, n, s, ev.data(), kinds.data(), nkinds > 4 ? 2 : (nkinds > 3 ? 1 : 0));
-  if (r == ACF_OK && hipStreamSynchronize(s) != hipSuccess) r = set_error(ACF_E_HIP, "sync failed");
+  if (r == ACF_OK && hipStreamSynchronize(s) != hipSuccess) r = acf_set_error(ACF_E_HIP, "sync failed");
   for (int k = 0; k < nkinds; ++k) { ms_out[k] = 0.0; launches_out[k] = 0; }
   for (int x = 0; r == ACF_OK && x < nl; ++x) {
     if (kinds[x] < 0 || kinds[x] >= nkinds) continue;
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, ev[2 * x], ev[2 * x + 1]) != hipSuccess) {
-      r = set_error(ACF_E_HIP, "hipEventElapsedTime failed");
+      r = acf_set_error(ACF_E_HIP, "hipEventElapsedTime failed");
       break;
     }
     ms_out[kinds[x]] += ms;
@@ -5575,496 +5477,6 @@ extern "C" int acf_bpr_forward(const float* P, const float* Q, int64_t U1, int64
   ACF_CHECK(B > 0 && nb > 0 && U1 > 0 && I1 > 0, ACF_E_INVALID, "empty problem");
   hipStream_t s = static_cast<hipStream_t>(stream_);
   ACF_RET(DISPATCH_GEOM(d, launch_forward, P, Q, d, u, i, j, B, nb, lo, hi, bl, bc, op, on, s));
-  HIP_TRY(hipGetLastError());
-  return ACF_OK;
-}
-
-// kernel: 0 auto (ACF_EVAL_AUTO_VALU_PAIRS), 1 the fused MFMA sweep, 2 the VALU
-// sweep k_eval_all (A/B and tests); positions are identical.
-#define ACF_EVAL_VALU_PAIRS 0  // auto: the VALU sweep below this many user x candidate pairs
-
-static int eval_positions_all(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
-                              const int32_t* users, const int32_t* tests, int32_t n_users, int32_t num_cand,
-                              const int64_t* excl_off, const int32_t* excl, int32_t* positions, int32_t kernel,
-                              void* stream_) {
-  ACF_RET(check_dim(d));
-  ACF_CHECK(P && Q && users && tests && excl_off && positions, ACF_E_INVALID, "NULL argument");
-  ACF_CHECK(num_cand >= 0 && num_cand <= I1, ACF_E_INVALID, "num_candidates %d > item rows", num_cand);
-  ACF_CHECK(kernel >= 0 && kernel <= 2, ACF_E_INVALID, "kernel must be 0 (auto), 1 (MFMA) or 2 (VALU), got %d",
-            kernel);
-  if (n_users <= 0) return ACF_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream_);
-  if (kernel == 0) kernel = (int64_t)n_users * num_cand < ACF_EVAL_VALU_PAIRS ? 2 : 1;
-  if (kernel == 2) {
-    const size_t lds = (size_t)EVAL_UB * d * sizeof(float);
-    k_eval_all<<<(n_users + EVAL_UB - 1) / EVAL_UB, 256, lds, s>>>(P, Q, d, users, tests, n_users,
-                                                                    num_cand, excl_off, excl, positions);
-    HIP_TRY(hipGetLastError());
-    return ACF_OK;
-  }
-  float* tscore = nullptr;
-  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&tscore), (size_t)n_users * sizeof(float), s));
-  k_eval_tscore<<<grid_for(n_users), 256, 0, s>>>(P, Q, d, users, tests, n_users, tscore, positions);
-  if (num_cand > 0) {
-    float eb, floor_e;
-    mfma_err_band(d, &eb, &floor_e);
-    const dim3 grid((unsigned)((num_cand + EVM_C - 1) / EVM_C), (unsigned)((n_users + EVM_U - 1) / EVM_U));
-    k_eval_fused<<<grid, 256, 0, s>>>(P, Q, d, users, tscore, n_users, num_cand, excl_off, excl, eb, floor_e,
-                                      positions);
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipFreeAsync(tscore, s));
-  return ACF_OK;
-}
-
-extern "C" int acf_eval_positions_all(const float* P, const float* Q, int64_t U1, int64_t I1,
-                                      int32_t d, const int32_t* users, const int32_t* tests,
-                                      int32_t n_users, int32_t num_cand, const int64_t* excl_off,
-                                      const int32_t* excl, int32_t* positions, void* stream_) {
-  return eval_positions_all(P, Q, U1, I1, d, users, tests, n_users, num_cand, excl_off, excl, positions, 0,
-                            stream_);
-}
-
-extern "C" int acf_eval_positions_all_kernel(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
-                                             const int32_t* users, const int32_t* tests, int32_t n_users,
-                                             int32_t num_cand, const int64_t* excl_off, const int32_t* excl,
-                                             int32_t* positions, int32_t kernel, void* stream_) {
-  return eval_positions_all(P, Q, U1, I1, d, users, tests, n_users, num_cand, excl_off, excl, positions, kernel,
-                            stream_);
-}
-
-// kernel: 0 auto, 1 the MFMA sweep k_topk_mfma, 2 the VALU sweep k_topk_valu;
-// identical outputs.  auto: the VALU sweep below ACF_TOPK_VALU_PAIRS user x candidate pairs.
-// Measured at K = 100, d = 64 the VALU sweep is 5-6x faster than the MFMA
-// sweep at ml-1m (22M pairs) and pinterest-20 (547M pairs) alike, so no measured size
-// crosses over: auto is the VALU sweep.
-#define ACF_TOPK_VALU_PAIRS INT64_MAX
-static int topk_kernel(int32_t n_users, int32_t num_cand, int32_t kernel) {
-  if (kernel == 0) return (int64_t)n_users * num_cand < ACF_TOPK_VALU_PAIRS ? 2 : 1;
-  return kernel;
-}
-
-static int topk_check(int32_t n_users, int32_t num_cand, int32_t k, int32_t kernel) {
-  ACF_CHECK(k >= 1 && k <= TOPK_MAX_K, ACF_E_INVALID, "k must be in [1, %d], got %d", TOPK_MAX_K, k);
-  ACF_CHECK(kernel >= 0 && kernel <= 2, ACF_E_INVALID, "kernel must be 0 (auto), 1 (MFMA) or 2 (VALU), got %d",
-            kernel);
-  ACF_CHECK(n_users >= 0 && num_cand >= 0, ACF_E_INVALID, "negative size");
-  return ACF_OK;
-}
-
-extern "C" int acf_recommend_topk_workspace(int32_t n_users, int32_t num_cand, int32_t k, int32_t kernel,
-                                            size_t* bytes) {
-  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
-  ACF_RET(topk_check(n_users, num_cand, k, kernel));
-  int wper = 0, S = 0;
-  topk_strips(n_users, num_cand, k, topk_kernel(n_users, num_cand, kernel), &wper, &S);
-  *bytes = (size_t)std::max(n_users, 1) * S * k * sizeof(uint64_t);
-  return ACF_OK;
-}
-
-// the sweeps' dynamic LDS (MFMA: up to 96 KB of keys; VALU: 32 KB of keys + 8 rows) is above the 64 KB default
-// (set per call: the attribute belongs to the current device's copy of the kernel)
-static int topk_lds_optin(int kernel) {
-  if (kernel == 1)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_topk_mfma),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(EVM_U * TKM_CAP_MAX * sizeof(uint64_t))));
-  else
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_topk_valu),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(TKV_UB * TKV_CAP * sizeof(uint64_t) + TKV_UB * 1024 * sizeof(float))));
-  return ACF_OK;
-}
-
-extern "C" int acf_recommend_topk(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
-                                  const int32_t* users, int32_t n_users, int32_t num_cand,
-                                  const int64_t* excl_off, const int32_t* excl, int32_t k, int32_t* out_items,
-                                  float* out_scores, void* workspace, size_t workspace_bytes, int32_t kernel,
-                                  void* stream_) {
-  ACF_RET(check_dim(d));
-  ACF_RET(topk_check(n_users, num_cand, k, kernel));
-  ACF_CHECK(P && Q && users && excl_off && excl && out_items && out_scores && workspace, ACF_E_INVALID,
-            "NULL argument");
-  ACF_CHECK(num_cand <= I1, ACF_E_INVALID, "num_candidates %d > item rows", num_cand);
-  ACF_CHECK(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, ACF_E_INVALID, "workspace must be 8-byte aligned");
-  kernel = topk_kernel(n_users, num_cand, kernel);
-  int wper = 0, S = 0;
-  topk_strips(n_users, num_cand, k, kernel, &wper, &S);
-  const size_t need = (size_t)std::max(n_users, 1) * S * k * sizeof(uint64_t);
-  ACF_CHECK(workspace_bytes >= need, ACF_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
-  if (n_users == 0) return ACF_OK;
-  ACF_RET(topk_lds_optin(kernel));
-  hipStream_t s = static_cast<hipStream_t>(stream_);
-  uint64_t* ws = static_cast<uint64_t*>(workspace);
-  if (kernel == 2) {
-    const size_t lds = (size_t)TKV_UB * TKV_CAP * sizeof(uint64_t) + (size_t)TKV_UB * d * sizeof(float);
-    const dim3 grid((unsigned)((n_users + TKV_UB - 1) / TKV_UB), (unsigned)S);
-    k_topk_valu<<<grid, 256, lds, s>>>(P, Q, d, users, n_users, num_cand, excl_off, excl, k, wper, S, ws);
-  } else {
-    float eb, floor_e;
-    mfma_err_band(d, &eb, &floor_e);
-    const int cap = topk_mfma_cap(k);
-    const dim3 grid((unsigned)((n_users + EVM_U - 1) / EVM_U), (unsigned)S);
-    k_topk_mfma<<<grid, 256, (size_t)EVM_U * cap * sizeof(uint64_t), s>>>(P, Q, d, users, n_users, num_cand,
-                                                                         excl_off, excl, eb, floor_e, k, cap, wper,
-                                                                         S, ws);
-  }
-  HIP_TRY(hipGetLastError());
-  k_topk_merge<<<(unsigned)n_users, 256, 0, s>>>(ws, S, k, out_items, out_scores);
-  HIP_TRY(hipGetLastError());
-  return ACF_OK;
-}
-
-// ---- nearest-neighbour lists (acf_neighbors.h) ---------------------------------
-static int nbr_check(int32_t n_q, int32_t num_cand, int32_t k) {
-  ACF_CHECK(k >= 1 && k <= TOPK_MAX_K, ACF_E_INVALID, "k must be in [1, %d], got %d", TOPK_MAX_K, k);
-  ACF_CHECK(n_q >= 0 && num_cand >= 0, ACF_E_INVALID, "negative size");
-  return ACF_OK;
-}
-
-extern "C" int acf_neighbors_topk_workspace(int32_t n_q, int32_t num_cand, int32_t k, size_t* bytes) {
-  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
-  ACF_RET(nbr_check(n_q, num_cand, k));
-  *bytes = nbr_workspace(n_q, num_cand, k, true);
-  return ACF_OK;
-}
-
-template <int METRIC>
-static int launch_nbr(const float* T, const float* X, int d, int64_t XR, const int32_t* queries, int n_q,
-                      int num_cand, int exclude_self, const int64_t* excl_off, const int32_t* excl,
-                      const float* cnorm, int K, int wper, int S, uint64_t* lists, int32_t* err, hipStream_t s) {
-  // 32 KB of keys + 8 rows: above the 64 KB default from d = 1024 (set per call, as topk_lds_optin)
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nbr_valu<METRIC>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(TKV_UB * TKV_CAP * sizeof(uint64_t) + TKV_UB * 1024 * sizeof(float))));
-  const size_t lds = (size_t)TKV_UB * TKV_CAP * sizeof(uint64_t) + (size_t)TKV_UB * d * sizeof(float);
-  const dim3 grid((unsigned)((n_q + TKV_UB - 1) / TKV_UB), (unsigned)S);
-  k_nbr_valu<METRIC><<<grid, 256, lds, s>>>(T, X, d, XR, queries, n_q, num_cand, exclude_self, excl_off, excl, cnorm,
-                                            K, wper, S, lists, err);
-  HIP_TRY(hipGetLastError());
-  return ACF_OK;
-}
-
-extern "C" int acf_neighbors_topk(const float* T, int64_t TR, int32_t d, const float* X, int64_t XR,
-                                  const int32_t* queries, int32_t n_q, int32_t num_cand, int32_t metric,
-                                  int32_t exclude_self, const int64_t* excl_off, const int32_t* excl, int32_t k,
-                                  int32_t* out_items, float* out_scores, void* workspace, size_t workspace_bytes,
-                                  int32_t check, void* stream_) {
-  ACF_RET(check_dim(d));
-  ACF_RET(nbr_check(n_q, num_cand, k));
-  ACF_CHECK(metric >= NBR_DOT && metric <= NBR_EUC, ACF_E_INVALID,
-            "metric must be 0 (dot), 1 (cosine) or 2 (Euclidean), got %d", metric);
-  ACF_CHECK(TR > 0 && XR > 0, ACF_E_INVALID, "empty table");
-  ACF_CHECK(num_cand <= TR, ACF_E_INVALID, "num_candidates %d > table rows", num_cand);
-  ACF_CHECK(T && X && queries && out_items && out_scores && workspace, ACF_E_INVALID, "NULL argument");
-  ACF_CHECK((excl_off == nullptr) == (excl == nullptr), ACF_E_INVALID, "excl_off and excl_items go together");
-  ACF_CHECK(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, ACF_E_INVALID, "workspace must be 8-byte aligned");
-  int wper = 0, S = 0;
-  const size_t lists_bytes = nbr_lists_bytes(n_q, num_cand, k, &wper, &S);
-  const size_t need = nbr_workspace(n_q, num_cand, k, metric == NBR_COS);
-  ACF_CHECK(workspace_bytes >= need, ACF_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
-  if (n_q == 0) return ACF_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream_);
-  int32_t* err = static_cast<int32_t*>(workspace);
-  uint64_t* lists = reinterpret_cast<uint64_t*>(static_cast<char*>(workspace) + NBR_WS_HEAD);
-  float* cnorm = reinterpret_cast<float*>(static_cast<char*>(workspace) + NBR_WS_HEAD + lists_bytes);
-  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
-  if (metric == NBR_COS && num_cand > 0) {
-    k_nbr_norms<<<grid_for(num_cand), 256, 0, s>>>(T, d, num_cand, cnorm);
-    HIP_TRY(hipGetLastError());
-  }
-  const auto launch = metric == NBR_DOT ? &launch_nbr<NBR_DOT> : metric == NBR_COS ? &launch_nbr<NBR_COS>
-                                                                                   : &launch_nbr<NBR_EUC>;
-  ACF_RET(launch(T, X, d, XR, queries, n_q, num_cand, exclude_self != 0, excl_off, excl, cnorm, k, wper, S, lists,
-                 err, s));
-  k_topk_merge<<<(unsigned)n_q, 256, 0, s>>>(lists, S, k, out_items, out_scores);
-  HIP_TRY(hipGetLastError());
-  if (check) {
-    int32_t herr = 0;
-    HIP_TRY(hipMemcpyAsync(&herr, err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    ACF_CHECK(herr == 0, ACF_E_RANGE, "index out of range (query >= num_query_rows)");
-  }
-  return ACF_OK;
-}
-
-// ---- multi-item evaluation (acf_eval_multi.h) ---------------------------------
-static int evx_check(int32_t n_users, int64_t n_tests, int32_t num_cand) {
-  ACF_CHECK(n_users >= 0 && n_tests >= 0, ACF_E_INVALID, "negative count");
-  ACF_CHECK(n_tests < ((int64_t)1 << 31), ACF_E_INVALID, "more than 2^31 - 1 test items");
-  ACF_CHECK(num_cand >= 1, ACF_E_INVALID, "num_candidates must be >= 1, got %d", num_cand);
-  return ACF_OK;
-}
-
-extern "C" int acf_eval_positions_multi_workspace(int32_t n_users, int64_t n_tests, int32_t num_cand,
-                                                  size_t* bytes) {
-  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
-  ACF_RET(evx_check(n_users, n_tests, num_cand));
-  *bytes = evx_workspace(n_users, n_tests, num_cand);
-  return ACF_OK;
-}
-
-extern "C" int acf_eval_positions_multi(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
-                                        const int32_t* users, const int64_t* test_off, const int32_t* test_items,
-                                        int32_t n_users, int64_t n_tests, int32_t num_cand, const int64_t* excl_off,
-                                        const int32_t* excl, int32_t* positions, void* workspace,
-                                        size_t workspace_bytes, int32_t check, void* stream_) {
-  ACF_RET(check_dim(d));
-  ACF_RET(evx_check(n_users, n_tests, num_cand));
-  ACF_CHECK(U1 > 0 && I1 > 0, ACF_E_INVALID, "empty table");
-  ACF_CHECK(num_cand <= I1, ACF_E_INVALID, "num_candidates %d > item rows", num_cand);
-  ACF_CHECK(P && Q && users && test_off && test_items && positions && workspace, ACF_E_INVALID, "NULL argument");
-  ACF_CHECK((excl_off == nullptr) == (excl == nullptr), ACF_E_INVALID, "excl_off and excl_items go together");
-  ACF_CHECK(reinterpret_cast<uintptr_t>(workspace) % 4 == 0, ACF_E_INVALID, "workspace must be 4-byte aligned");
-  const size_t need = evx_workspace(n_users, n_tests, num_cand);
-  ACF_CHECK(workspace_bytes >= need, ACF_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
-  if (n_users == 0 || n_tests == 0) return ACF_OK;
-  int wper = 0, S = 0;
-  evx_strips(n_users, n_tests, num_cand, &wper, &S);
-  hipStream_t s = static_cast<hipStream_t>(stream_);
-  int32_t* err = static_cast<int32_t*>(workspace);
-  int32_t* part = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + EVX_WS_HEAD);
-  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
-  const dim3 grid((unsigned)((n_users + EVX_UB - 1) / EVX_UB), (unsigned)S);
-  k_evx_sweep<<<grid, 256, (size_t)EVX_UB * d * sizeof(float), s>>>(P, Q, d, U1, I1, users, test_off, test_items,
-                                                                     n_users, n_tests, num_cand, excl_off, excl, wper,
-                                                                     S > 1 ? part : positions, err);
-  HIP_TRY(hipGetLastError());
-  if (S > 1) {
-    k_evx_sum<<<grid_for(n_tests), 256, 0, s>>>(part, S, n_tests, positions);
-    HIP_TRY(hipGetLastError());
-  }
-  if (check) {
-    int32_t herr = 0;
-    HIP_TRY(hipMemcpyAsync(&herr, err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    ACF_CHECK(herr == 0, ACF_E_RANGE, "index out of range (%s%s)", (herr & 1) ? "user >= num_user_rows " : "",
-              (herr & 2) ? "test item >= num_item_rows" : "");
-  }
-  return ACF_OK;
-}
-
-// ---- certified worst-case positions (acf_eval_worst.h) -------------------------
-static int evw_check(int32_t n_users, int32_t num_cand, int32_t n_eps) {
-  ACF_CHECK(n_users >= 0, ACF_E_INVALID, "negative count");
-  ACF_CHECK(num_cand >= 1, ACF_E_INVALID, "num_candidates must be >= 1, got %d", num_cand);
-  ACF_CHECK(n_eps >= 1 && n_eps <= EVW_MAX_EPS, ACF_E_INVALID, "n_eps %d outside [1, %d]", n_eps, EVW_MAX_EPS);
-  return ACF_OK;
-}
-
-extern "C" int acf_eval_positions_worst_workspace(int32_t n_users, int32_t num_cand, int32_t n_eps, size_t* bytes) {
-  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
-  ACF_RET(evw_check(n_users, num_cand, n_eps));
-  *bytes = evw_workspace(n_users, num_cand, n_eps);
-  return ACF_OK;
-}
-
-template <int UB, bool USER>
-static void launch_evw(const float* P, const float* Q, int d, int64_t U1, int64_t I1, const int32_t* users,
-                       const int32_t* tests, int n_users, int num_cand, const int64_t* excl_off, const int32_t* excl,
-                       const EvwEps& eps, int wper, int S, int32_t* out, int32_t* err, hipStream_t s) {
-  const dim3 grid((unsigned)((n_users + UB - 1) / UB), (unsigned)S);
-  const size_t lds = (size_t)(USER ? 2 : 1) * UB * d * sizeof(float);
-  k_evw_sweep<UB, USER><<<grid, 256, lds, s>>>(P, Q, d, U1, I1, users, tests, n_users, num_cand, excl_off, excl, eps,
-                                               wper, out, err);
-}
-
-extern "C" int acf_eval_positions_worst(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
-                                        const int32_t* users, const int32_t* test_items, int32_t n_users,
-                                        int32_t num_cand, const int64_t* excl_off, const int32_t* excl,
-                                        const float* eps, int32_t n_eps, int32_t side, int32_t* worst,
-                                        void* workspace, size_t workspace_bytes, int32_t check, void* stream_) {
-  ACF_RET(check_dim(d));
-  ACF_RET(evw_check(n_users, num_cand, n_eps));
-  ACF_CHECK(side == 0 || side == 1, ACF_E_INVALID, "side must be 0 (user) or 1 (item), got %d", side);
-  ACF_CHECK(eps, ACF_E_INVALID, "NULL argument");
-  EvwEps ev{};
-  ev.n = n_eps;
-  for (int e = 0; e < EVW_MAX_EPS; ++e) {
-    const float v = eps[std::min(e, n_eps - 1)];  // the unused slots repeat the last one
-    ACF_CHECK(std::isfinite(v) && v >= 0.f, ACF_E_INVALID, "eps must be finite and >= 0, got %g", (double)v);
-    ev.e[e] = v;
-  }
-  ACF_CHECK(U1 > 0 && I1 > 0, ACF_E_INVALID, "empty table");
-  ACF_CHECK(num_cand <= I1, ACF_E_INVALID, "num_candidates %d > item rows", num_cand);
-  ACF_CHECK(P && Q && users && test_items && worst && workspace, ACF_E_INVALID, "NULL argument");
-  ACF_CHECK((excl_off == nullptr) == (excl == nullptr), ACF_E_INVALID, "excl_off and excl_items go together");
-  ACF_CHECK(reinterpret_cast<uintptr_t>(workspace) % 4 == 0, ACF_E_INVALID, "workspace must be 4-byte aligned");
-  const size_t need = evw_workspace(n_users, num_cand, n_eps);
-  ACF_CHECK(workspace_bytes >= need, ACF_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
-  if (n_users == 0) return ACF_OK;
-  int wper = 0, S = 0;
-  evw_strips(n_users, num_cand, n_eps, &wper, &S);
-  hipStream_t s = static_cast<hipStream_t>(stream_);
-  int32_t* err = static_cast<int32_t*>(workspace);
-  int32_t* part = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + EVW_WS_HEAD);
-  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
-  int32_t* out = S > 1 ? part : worst;
-  const bool wide = d <= EVW_D_SPLIT;  // 8 entries per workgroup, 4 above: the rows stay within 32 KB of LDS
-  const auto launch = side == 0 ? (wide ? &launch_evw<EVW_UB, true> : &launch_evw<EVW_UB / 2, true>)
-                                : (wide ? &launch_evw<EVW_UB, false> : &launch_evw<EVW_UB / 2, false>);
-  launch(P, Q, d, U1, I1, users, test_items, n_users, num_cand, excl_off, excl, ev, wper, S, out, err, s);
-  HIP_TRY(hipGetLastError());
-  if (S > 1) {
-    const int64_t n_out = (int64_t)n_eps * n_users;
-    k_evx_sum<<<grid_for(n_out), 256, 0, s>>>(part, S, n_out, worst);
-    HIP_TRY(hipGetLastError());
-  }
-  if (check) {
-    int32_t herr = 0;
-    HIP_TRY(hipMemcpyAsync(&herr, err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    ACF_CHECK(herr == 0, ACF_E_RANGE, "index out of range (%s%s)", (herr & 1) ? "user >= num_user_rows " : "",
-              (herr & 2) ? "test item >= num_item_rows" : "");
-  }
-  return ACF_OK;
-}
-
-extern "C" int acf_eval_rank_metrics(const int32_t* positions, const int64_t* test_off, int32_t n_users,
-                                     const int32_t* n_neg, const int32_t* cutoffs, int32_t n_cutoffs,
-                                     double* per_user, double* per_user_free, double* mean_cut, double* mean_free,
-                                     int64_t* n_scored, void* stream_) {
-  ACF_CHECK(n_users >= 0, ACF_E_INVALID, "negative count");
-  ACF_CHECK(n_cutoffs >= 0 && n_cutoffs <= EVX_MAX_CUT, ACF_E_INVALID, "n_cutoffs %d outside [0, %d]", n_cutoffs,
-            EVX_MAX_CUT);
-  ACF_CHECK(cutoffs || n_cutoffs == 0, ACF_E_INVALID, "NULL argument");
-  EvxCuts cuts{};
-  cuts.n = n_cutoffs;
-  for (int c = 0; c < n_cutoffs; ++c) {
-    ACF_CHECK(cutoffs[c] >= 1 && cutoffs[c] <= EVX_MAX_K, ACF_E_INVALID, "cutoff %d outside [1, %d]", cutoffs[c],
-              EVX_MAX_K);
-    cuts.k[c] = cutoffs[c];
-  }
-  ACF_CHECK(test_off && mean_free && n_scored && (mean_cut || n_cutoffs == 0), ACF_E_INVALID, "NULL argument");
-  ACF_CHECK(n_users == 0 || (positions && n_neg && per_user_free && (per_user || n_cutoffs == 0)), ACF_E_INVALID,
-            "NULL argument");
-  hipStream_t s = static_cast<hipStream_t>(stream_);
-  if (n_users > 0) {
-    k_evx_metrics<<<(unsigned)n_users, 256, 0, s>>>(positions, test_off, n_neg, cuts, per_user, per_user_free);
-    HIP_TRY(hipGetLastError());
-  }
-  const int ncol = n_cutoffs * EVX_NM;
-  k_evx_means<<<(unsigned)(ncol + 2), 256, 0, s>>>(per_user, per_user_free, test_off, n_users, ncol, mean_cut,
-                                                   mean_free, n_scored);
-  HIP_TRY(hipGetLastError());
-  return ACF_OK;
-}
-
-// ---- whole-stream adversarial direction (acf_adv.h) -------------------------
-static int adv_check(int64_t n, int64_t U1, int64_t I1, int32_t d) {
-  ACF_RET(check_dim(d));
-  ACF_CHECK(U1 > 0 && I1 > 0, ACF_E_INVALID, "empty table");
-  ACF_CHECK(U1 + I1 < ((int64_t)1 << 31), ACF_E_INVALID, "more than 2^31 - 1 table rows");
-  ACF_CHECK(n >= 0 && n < ((int64_t)1 << 29), ACF_E_INVALID, "n must lie in [0, 2^29), got %lld", (long long)n);
-  return ACF_OK;
-}
-
-extern "C" int acf_adv_direction_workspace(int64_t n, int64_t U1, int64_t I1, int32_t d, size_t* bytes) {
-  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
-  ACF_RET(adv_check(n, U1, I1, d));
-  *bytes = adv_layout(n, U1, I1, d).total;
-  return ACF_OK;
-}
-
-template <int LPR, int NV>
-static void launch_adv_random(uint64_t seed, uint32_t call, int32_t t, int d, int64_t U1, int64_t R, float* nP,
-                              float* nQ, hipStream_t s) {
-  k_adv_random<LPR, NV><<<grid_for(R * LPR), 256, 0, s>>>(seed, call, t, d, U1, R, nP, nQ);
-}
-
-template <int LPR, int NV>
-static void launch_adv_sum(const float* P, const float* Q, int d, int64_t U1, int64_t R, const int32_t* off,
-                           const int2* rec, float* part, float* nP, float* nQ, int64_t units, hipStream_t s) {
-  k_adv_chunks<LPR, NV><<<grid_for(units * LPR), 256, 0, s>>>(P, Q, d, U1, R, off, rec, part, nP, nQ, units);
-  k_adv_combine<LPR, NV><<<grid_for(R * LPR), 256, 0, s>>>(d, U1, R, off, part, nP, nQ);
-}
-
-extern "C" int acf_adv_direction(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
-                                 const int32_t* user, const int32_t* ipos, const int32_t* ineg, int64_t n,
-                                 float clip_lo, float clip_hi, int32_t adv_mode, uint64_t seed, uint32_t call,
-                                 int32_t t, float* nP, float* nQ, void* workspace, size_t workspace_bytes,
-                                 int32_t check, void* stream_) {
-  ACF_RET(adv_check(n, U1, I1, d));
-  ACF_CHECK(adv_mode == 0 || adv_mode == 1, ACF_E_INVALID, "adv_mode must be 0 (grad) or 1 (random), got %d",
-            adv_mode);
-  ACF_CHECK(P && Q && nP && nQ, ACF_E_INVALID, "NULL argument");
-  hipStream_t s = static_cast<hipStream_t>(stream_);
-  const int64_t R = U1 + I1;
-  if (adv_mode == 1) {  // the triplets are not read
-    ACF_RET(DISPATCH_GEOM(d, launch_adv_random, seed, call, t, d, U1, R, nP, nQ, s));
-    HIP_TRY(hipGetLastError());
-    return ACF_OK;
-  }
-  if (n == 0) {
-    HIP_TRY(hipMemsetAsync(nP, 0, (size_t)U1 * d * sizeof(float), s));
-    HIP_TRY(hipMemsetAsync(nQ, 0, (size_t)I1 * d * sizeof(float), s));
-    return ACF_OK;
-  }
-  ACF_CHECK(user && ipos && ineg && workspace, ACF_E_INVALID, "NULL argument");
-  ACF_CHECK(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, ACF_E_INVALID, "workspace must be 16-byte aligned");
-  const AdvLayout L = adv_layout(n, U1, I1, d);
-  ACF_CHECK(workspace_bytes >= L.total, ACF_E_INVALID, "workspace too small: %zu < %zu bytes", workspace_bytes,
-            L.total);
-  char* ws = static_cast<char*>(workspace);
-  float* coef = reinterpret_cast<float*>(ws + L.coef);
-  uint32_t* kb[2] = {reinterpret_cast<uint32_t*>(ws + L.k0), reinterpret_cast<uint32_t*>(ws + L.k1)};
-  uint32_t* vb[2] = {reinterpret_cast<uint32_t*>(ws + L.v0), reinterpret_cast<uint32_t*>(ws + L.v1)};
-  uint32_t* counts = reinterpret_cast<uint32_t*>(ws + L.counts);
-  uint32_t* tsum = reinterpret_cast<uint32_t*>(ws + L.tsum);
-  int32_t* off = reinterpret_cast<int32_t*>(ws + L.off);
-  float* part = reinterpret_cast<float*>(ws + L.part);
-  int32_t* err = reinterpret_cast<int32_t*>(ws + L.err);
-  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
-  k_adv_stage<<<grid_for(n), 256, 0, s>>>(P, Q, d, user, ipos, ineg, n, U1, I1, clip_lo, clip_hi, coef, kb[0], vb[0],
-                                           err);
-  HIP_TRY(hipGetLastError());
-  if (check) {  // before anything is built on the indices
-    int32_t herr = 0;
-    HIP_TRY(hipMemcpyAsync(&herr, err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    ACF_CHECK(herr == 0, ACF_E_RANGE, "triplet index out of range (%s%s)",
-              (herr & 1) ? "user >= num_user_rows " : "", (herr & 2) ? "item >= num_item_rows" : "");
-  }
-  int cur = 0;
-  for (int p = 0; p < L.passes; ++p, cur ^= 1) {
-    k_adv_hist<<<(unsigned)L.ntiles, ADV_SORT_BS, 0, s>>>(kb[cur], L.N, 8 * p, L.ntiles, counts);
-    k_adv_scan1<<<(unsigned)L.T, 256, 0, s>>>(counts, L.M, tsum);
-    k_adv_scan2<<<1, 1024, 0, s>>>(tsum, L.T);
-    k_adv_scan3<<<(unsigned)L.T, 256, 0, s>>>(counts, L.M, tsum);
-    k_adv_reorder<<<(unsigned)L.ntiles, ADV_SORT_BS, 0, s>>>(kb[cur], vb[cur], kb[cur ^ 1], vb[cur ^ 1], L.N, 8 * p,
-                                                            L.ntiles, counts);
-    HIP_TRY(hipGetLastError());
-  }
-  int2* rec = reinterpret_cast<int2*>(kb[cur ^ 1]);  // the free (keys, values) pair: N * 8 bytes
-  k_adv_offsets<<<grid_for(R + 1), 256, 0, s>>>(kb[cur], L.N, R, off);
-  k_adv_records<<<grid_for(L.N), 256, 0, s>>>(vb[cur], L.N, n, user, ipos, ineg, U1, I1, coef, rec);
-  HIP_TRY(hipGetLastError());
-  const int64_t units = L.N / ADV_CHUNK + R + 1;
-  ACF_RET(DISPATCH_GEOM(d, launch_adv_sum, P, Q, d, U1, R, off, rec, part, nP, nQ, units, s));
-  HIP_TRY(hipGetLastError());
-  return ACF_OK;
-}
-
-extern "C" int acf_adv_apply(const float* W, const float* N, int64_t rows, int32_t d, float eps, float* delta_out,
-                             float* sum_out, void* stream_) {
-  ACF_CHECK(rows >= 0 && d > 0, ACF_E_INVALID, "negative size");
-  ACF_CHECK(N && (W || !sum_out), ACF_E_INVALID, "NULL argument");
-  const int64_t count = rows * (int64_t)d;
-  if (count == 0 || (!delta_out && !sum_out)) return ACF_OK;
-  k_adv_apply<<<grid_for(count), 256, 0, static_cast<hipStream_t>(stream_)>>>(W, N, count, eps, delta_out, sum_out);
-  HIP_TRY(hipGetLastError());
-  return ACF_OK;
-}
-
-extern "C" int acf_eval_positions_list(const float* P, const float* Q, int64_t U1, int64_t I1,
-                                       int32_t d, const int32_t* users, const int32_t* tests,
-                                       int32_t n_users, const int64_t* cand_off,
-                                       const int32_t* cand, int32_t* positions, void* stream_) {
-  ACF_RET(check_dim(d));
-  ACF_CHECK(P && Q && users && tests && cand_off && positions, ACF_E_INVALID, "NULL argument");
-  if (n_users <= 0) return ACF_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream_);
-  k_eval_list<<<n_users, 256, d * sizeof(float), s>>>(P, Q, d, users, tests, cand_off, cand, positions);
   HIP_TRY(hipGetLastError());
   return ACF_OK;
 }

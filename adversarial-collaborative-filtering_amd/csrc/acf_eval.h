@@ -1,5 +1,5 @@
 // All-items evaluation kernels of libacf_apr.so (k_eval_*): included by
-// acf_apr.hip after acf_sweep.h (seq_dot and the shared sweep pieces); one
+// acf_rank.hip after acf_sweep.h (seq_dot and the shared sweep pieces); one
 // translation unit.
 #pragma once
 

@@ -1,5 +1,5 @@
 // Multi-item all-items evaluation kernels of libacf_apr.so (k_evx_*): included by
-// acf_apr.hip after acf_sweep.h (seq_dot, the shared sweep pieces); one
+// acf_rank.hip after acf_sweep.h (seq_dot, the shared sweep pieces); one
 // translation unit.  DESIGN.md §4f.
 #pragma once
 

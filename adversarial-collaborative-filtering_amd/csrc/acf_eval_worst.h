@@ -1,5 +1,5 @@
 // Certified worst-case positions under an eps attack (k_evw_*): included by
-// acf_apr.hip after acf_eval_multi.h (acf_sweep.h's pieces, k_evx_sum); one
+// acf_rank.hip after acf_eval_multi.h (acf_sweep.h's pieces, k_evx_sum); one
 // translation unit.  DESIGN.md §4g.
 #pragma once
 

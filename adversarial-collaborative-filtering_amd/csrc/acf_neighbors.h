@@ -1,4 +1,4 @@
-// Nearest-neighbour lists of libacf_apr.so (k_nbr_*): included by acf_apr.hip
+// Nearest-neighbour lists of libacf_apr.so (k_nbr_*): included by acf_rank.hip
 // after acf_topk.h (acf_sweep.h's pieces, the key, topk_prune, k_topk_merge, the
 // strip cut); one translation unit.  DESIGN.md §4h.
 #pragma once

@@ -1,0 +1,525 @@
+// acf_rank.hip — the ranking family of libacf_apr.so: read-only kernels over the trained
+// tables (the headers included below) and their C-ABI entry points; nothing here touches a
+// training context (acf_apr.hip).  Every entry point follows one frame: argument checks,
+// workspace size and alignment, zero the error word, launch, sum the strips, read the error
+// word back when `check` is set; its repeated pieces are the first section's functions.
+// Build: one hipcc line with acf_apr.hip and acf_ops.hip, same flags.
+
+#include <hip/hip_runtime.h>
+#include <rocprim/block/block_radix_sort.hpp>
+#include <rocprim/block/block_scan.hpp>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+
+#include "acf_apr.h"
+#include "acf_host.h"
+#include "acf_rows.h"
+
+#include "acf_sweep.h"  // seq_dot and the score sweep the ranking kernels share: DESIGN.md §4
+#include "acf_eval.h"  // all-items evaluation (k_eval_*): DESIGN.md §4
+#include "acf_topk.h"  // top-K recommendation lists (k_topk_*): DESIGN.md §4b
+#include "acf_neighbors.h"  // nearest-neighbour lists (k_nbr_*): DESIGN.md §4h
+#include "acf_adv.h"   // whole-stream adversarial direction (k_adv_*): DESIGN.md §4c
+#include "acf_eval_multi.h"  // multi-item evaluation and rank metrics (k_evx_*): DESIGN.md §4f
+#include "acf_eval_worst.h"  // certified worst-case positions (k_evw_*): DESIGN.md §4g
+
+// ---- the host frame's shared pieces --------------------------------------------
+static int check_kernel(int32_t kernel) {
+  ACF_CHECK(kernel >= 0 && kernel <= 2, ACF_E_INVALID, "kernel must be 0 (auto), 1 (MFMA) or 2 (VALU), got %d",
+            kernel);
+  return ACF_OK;
+}
+
+static int check_excl_pair(const int64_t* excl_off, const int32_t* excl) {
+  ACF_CHECK((excl_off == nullptr) == (excl == nullptr), ACF_E_INVALID, "excl_off and excl_items go together");
+  return ACF_OK;
+}
+
+// The workspace precondition: aligned to `align` bytes, at least `need` bytes.  (NULL is
+// refused with the entry point's other pointers, as before: callers see the order of checks.)
+static int check_workspace(const void* workspace, size_t bytes, size_t need, int align) {
+  ACF_CHECK(reinterpret_cast<uintptr_t>(workspace) % align == 0, ACF_E_INVALID, "workspace must be %d-byte aligned",
+            align);
+  ACF_CHECK(bytes >= need, ACF_E_INVALID, "workspace too small: %zu < %zu bytes", bytes, need);
+  return ACF_OK;
+}
+
+// The kernels' error word on the host (one sync); the caller words what its bits mean.
+static int read_error_word(const int32_t* err, hipStream_t s, int32_t* word) {
+  int32_t herr = 0;
+  HIP_TRY(hipMemcpyAsync(&herr, err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *word = herr;
+  return ACF_OK;
+}
+
+// ... for the evaluation sweeps: bit 0 a user, bit 1 a test item outside its table
+static int check_eval_range(const int32_t* err, hipStream_t s) {
+  int32_t herr = 0;
+  ACF_RET(read_error_word(err, s, &herr));
+  ACF_CHECK(herr == 0, ACF_E_RANGE, "index out of range (%s%s)", (herr & 1) ? "user >= num_user_rows " : "",
+            (herr & 2) ? "test item >= num_item_rows" : "");
+  return ACF_OK;
+}
+
+// S > 1 strips write their counts to `part`, summed into `out` afterwards; one strip writes `out`.
+static int32_t* strip_target(int32_t* part, int S, int32_t* out) { return S > 1 ? part : out; }
+
+static int sum_strips(const int32_t* part, int S, int64_t n_out, int32_t* out, hipStream_t s) {
+  if (S > 1) {
+    k_evx_sum<<<grid_for(n_out), 256, 0, s>>>(part, S, n_out, out);
+    HIP_TRY(hipGetLastError());
+  }
+  return ACF_OK;
+}
+
+// Dynamic LDS of the VALU top-K sweeps (k_topk_valu, k_nbr_valu): 32 KB of keys + 8 rows, at d = 1024 above the
+// 64 KB default: they opt in to the largest (per call: the attribute belongs to the current device's copy).
+constexpr size_t tkv_lds(int d) { return (size_t)TKV_UB * (TKV_CAP * sizeof(uint64_t) + d * sizeof(float)); }
+constexpr int TKV_LDS_MAX = (int)tkv_lds(1024);
+
+// ---- all-items evaluation (acf_eval.h) ------------------------------------------
+// kernel: 0 auto, 1 the fused MFMA sweep, 2 the VALU sweep k_eval_all (A/B and
+// tests); positions are identical.  auto is the MFMA sweep.
+static int eval_positions_all(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
+                              const int32_t* users, const int32_t* tests, int32_t n_users, int32_t num_cand,
+                              const int64_t* excl_off, const int32_t* excl, int32_t* positions, int32_t kernel,
+                              void* stream_) {
+  ACF_RET(check_dim(d));
+  ACF_CHECK(P && Q && users && tests && excl_off && positions, ACF_E_INVALID, "NULL argument");
+  ACF_CHECK(num_cand >= 0 && num_cand <= I1, ACF_E_INVALID, "num_candidates %d > item rows", num_cand);
+  ACF_RET(check_kernel(kernel));
+  if (n_users <= 0) return ACF_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  if (kernel == 2) {
+    const size_t lds = (size_t)EVAL_UB * d * sizeof(float);
+    k_eval_all<<<(n_users + EVAL_UB - 1) / EVAL_UB, 256, lds, s>>>(P, Q, d, users, tests, n_users, num_cand, excl_off,
+                                                                    excl, positions);
+    HIP_TRY(hipGetLastError());
+    return ACF_OK;
+  }
+  float* tscore = nullptr;
+  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&tscore), (size_t)n_users * sizeof(float), s));
+  k_eval_tscore<<<grid_for(n_users), 256, 0, s>>>(P, Q, d, users, tests, n_users, tscore, positions);
+  if (num_cand > 0) {
+    float eb, floor_e;
+    mfma_err_band(d, &eb, &floor_e);
+    const dim3 grid((unsigned)((num_cand + EVM_C - 1) / EVM_C), (unsigned)((n_users + EVM_U - 1) / EVM_U));
+    k_eval_fused<<<grid, 256, 0, s>>>(P, Q, d, users, tscore, n_users, num_cand, excl_off, excl, eb, floor_e,
+                                      positions);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipFreeAsync(tscore, s));
+  return ACF_OK;
+}
+
+extern "C" int acf_eval_positions_all(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
+                                      const int32_t* users, const int32_t* tests, int32_t n_users, int32_t num_cand,
+                                      const int64_t* excl_off, const int32_t* excl, int32_t* positions,
+                                      void* stream_) {
+  return eval_positions_all(P, Q, U1, I1, d, users, tests, n_users, num_cand, excl_off, excl, positions, 0, stream_);
+}
+
+extern "C" int acf_eval_positions_all_kernel(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
+                                             const int32_t* users, const int32_t* tests, int32_t n_users,
+                                             int32_t num_cand, const int64_t* excl_off, const int32_t* excl,
+                                             int32_t* positions, int32_t kernel, void* stream_) {
+  return eval_positions_all(P, Q, U1, I1, d, users, tests, n_users, num_cand, excl_off, excl, positions, kernel,
+                            stream_);
+}
+
+extern "C" int acf_eval_positions_list(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
+                                       const int32_t* users, const int32_t* tests, int32_t n_users,
+                                       const int64_t* cand_off, const int32_t* cand, int32_t* positions,
+                                       void* stream_) {
+  ACF_RET(check_dim(d));
+  ACF_CHECK(P && Q && users && tests && cand_off && positions, ACF_E_INVALID, "NULL argument");
+  if (n_users <= 0) return ACF_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  k_eval_list<<<n_users, 256, d * sizeof(float), s>>>(P, Q, d, users, tests, cand_off, cand, positions);
+  HIP_TRY(hipGetLastError());
+  return ACF_OK;
+}
+
+// ---- top-K recommendation lists (acf_topk.h) --------------------------------------
+// kernel: 0 auto, 1 the MFMA sweep k_topk_mfma, 2 the VALU sweep k_topk_valu;
+// identical outputs.  Measured at K = 100, d = 64 the VALU sweep is
+// 5-6x faster than the MFMA sweep at ml-1m (22M pairs) and pinterest-20 (547M pairs)
+// alike, so no measured size crosses over: auto is the VALU sweep.
+static int topk_kernel(int32_t kernel) { return kernel == 0 ? 2 : kernel; }
+
+static int topk_check(int32_t n_users, int32_t num_cand, int32_t k, int32_t kernel) {
+  ACF_CHECK(k >= 1 && k <= TOPK_MAX_K, ACF_E_INVALID, "k must be in [1, %d], got %d", TOPK_MAX_K, k);
+  ACF_RET(check_kernel(kernel));
+  ACF_CHECK(n_users >= 0 && num_cand >= 0, ACF_E_INVALID, "negative size");
+  return ACF_OK;
+}
+
+extern "C" int acf_recommend_topk_workspace(int32_t n_users, int32_t num_cand, int32_t k, int32_t kernel,
+                                            size_t* bytes) {
+  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
+  ACF_RET(topk_check(n_users, num_cand, k, kernel));
+  int wper = 0, S = 0;
+  topk_strips(n_users, num_cand, k, topk_kernel(kernel), &wper, &S);
+  *bytes = (size_t)std::max(n_users, 1) * S * k * sizeof(uint64_t);
+  return ACF_OK;
+}
+
+// the MFMA sweep's dynamic LDS (up to 96 KB of keys) is above the 64 KB default too (see tkv_lds)
+static int topk_lds_optin(int kernel) {
+  if (kernel == 1)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_topk_mfma),
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(EVM_U * TKM_CAP_MAX * sizeof(uint64_t))));
+  else
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_topk_valu),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, TKV_LDS_MAX));
+  return ACF_OK;
+}
+
+extern "C" int acf_recommend_topk(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
+                                  const int32_t* users, int32_t n_users, int32_t num_cand,
+                                  const int64_t* excl_off, const int32_t* excl, int32_t k, int32_t* out_items,
+                                  float* out_scores, void* workspace, size_t workspace_bytes, int32_t kernel,
+                                  void* stream_) {
+  ACF_RET(check_dim(d));
+  ACF_RET(topk_check(n_users, num_cand, k, kernel));
+  ACF_CHECK(P && Q && users && excl_off && excl && out_items && out_scores && workspace, ACF_E_INVALID,
+            "NULL argument");
+  ACF_CHECK(num_cand <= I1, ACF_E_INVALID, "num_candidates %d > item rows", num_cand);
+  kernel = topk_kernel(kernel);
+  int wper = 0, S = 0;
+  topk_strips(n_users, num_cand, k, kernel, &wper, &S);
+  ACF_RET(check_workspace(workspace, workspace_bytes, (size_t)std::max(n_users, 1) * S * k * sizeof(uint64_t), 8));
+  if (n_users == 0) return ACF_OK;
+  ACF_RET(topk_lds_optin(kernel));
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  uint64_t* ws = static_cast<uint64_t*>(workspace);
+  if (kernel == 2) {
+    const dim3 grid((unsigned)((n_users + TKV_UB - 1) / TKV_UB), (unsigned)S);
+    k_topk_valu<<<grid, 256, tkv_lds(d), s>>>(P, Q, d, users, n_users, num_cand, excl_off, excl, k, wper, S, ws);
+  } else {
+    float eb, floor_e;
+    mfma_err_band(d, &eb, &floor_e);
+    const int cap = topk_mfma_cap(k);
+    const dim3 grid((unsigned)((n_users + EVM_U - 1) / EVM_U), (unsigned)S);
+    k_topk_mfma<<<grid, 256, (size_t)EVM_U * cap * sizeof(uint64_t), s>>>(P, Q, d, users, n_users, num_cand,
+                                                                         excl_off, excl, eb, floor_e, k, cap, wper,
+                                                                         S, ws);
+  }
+  HIP_TRY(hipGetLastError());
+  k_topk_merge<<<(unsigned)n_users, 256, 0, s>>>(ws, S, k, out_items, out_scores);
+  HIP_TRY(hipGetLastError());
+  return ACF_OK;
+}
+
+// ---- nearest-neighbour lists (acf_neighbors.h) ---------------------------------
+static int nbr_check(int32_t n_q, int32_t num_cand, int32_t k) {
+  ACF_CHECK(k >= 1 && k <= TOPK_MAX_K, ACF_E_INVALID, "k must be in [1, %d], got %d", TOPK_MAX_K, k);
+  ACF_CHECK(n_q >= 0 && num_cand >= 0, ACF_E_INVALID, "negative size");
+  return ACF_OK;
+}
+
+extern "C" int acf_neighbors_topk_workspace(int32_t n_q, int32_t num_cand, int32_t k, size_t* bytes) {
+  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
+  ACF_RET(nbr_check(n_q, num_cand, k));
+  *bytes = nbr_workspace(n_q, num_cand, k, true);
+  return ACF_OK;
+}
+
+template <int METRIC>
+static int launch_nbr(const float* T, const float* X, int d, int64_t XR, const int32_t* queries, int n_q,
+                      int num_cand, int exclude_self, const int64_t* excl_off, const int32_t* excl,
+                      const float* cnorm, int K, int wper, int S, uint64_t* lists, int32_t* err, hipStream_t s) {
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nbr_valu<METRIC>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, TKV_LDS_MAX));
+  const dim3 grid((unsigned)((n_q + TKV_UB - 1) / TKV_UB), (unsigned)S);
+  k_nbr_valu<METRIC><<<grid, 256, tkv_lds(d), s>>>(T, X, d, XR, queries, n_q, num_cand, exclude_self, excl_off, excl,
+                                                   cnorm, K, wper, S, lists, err);
+  HIP_TRY(hipGetLastError());
+  return ACF_OK;
+}
+
+extern "C" int acf_neighbors_topk(const float* T, int64_t TR, int32_t d, const float* X, int64_t XR,
+                                  const int32_t* queries, int32_t n_q, int32_t num_cand, int32_t metric,
+                                  int32_t exclude_self, const int64_t* excl_off, const int32_t* excl, int32_t k,
+                                  int32_t* out_items, float* out_scores, void* workspace, size_t workspace_bytes,
+                                  int32_t check, void* stream_) {
+  ACF_RET(check_dim(d));
+  ACF_RET(nbr_check(n_q, num_cand, k));
+  ACF_CHECK(metric >= NBR_DOT && metric <= NBR_EUC, ACF_E_INVALID,
+            "metric must be 0 (dot), 1 (cosine) or 2 (Euclidean), got %d", metric);
+  ACF_CHECK(TR > 0 && XR > 0, ACF_E_INVALID, "empty table");
+  ACF_CHECK(num_cand <= TR, ACF_E_INVALID, "num_candidates %d > table rows", num_cand);
+  ACF_CHECK(T && X && queries && out_items && out_scores && workspace, ACF_E_INVALID, "NULL argument");
+  ACF_RET(check_excl_pair(excl_off, excl));
+  int wper = 0, S = 0;
+  const size_t lists_bytes = nbr_lists_bytes(n_q, num_cand, k, &wper, &S);
+  ACF_RET(check_workspace(workspace, workspace_bytes, nbr_workspace(n_q, num_cand, k, metric == NBR_COS), 8));
+  if (n_q == 0) return ACF_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  int32_t* err = static_cast<int32_t*>(workspace);
+  uint64_t* lists = reinterpret_cast<uint64_t*>(static_cast<char*>(workspace) + NBR_WS_HEAD);
+  float* cnorm = reinterpret_cast<float*>(static_cast<char*>(workspace) + NBR_WS_HEAD + lists_bytes);
+  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+  if (metric == NBR_COS && num_cand > 0) {
+    k_nbr_norms<<<grid_for(num_cand), 256, 0, s>>>(T, d, num_cand, cnorm);
+    HIP_TRY(hipGetLastError());
+  }
+  const auto launch = metric == NBR_DOT ? &launch_nbr<NBR_DOT> : metric == NBR_COS ? &launch_nbr<NBR_COS>
+                                                                                   : &launch_nbr<NBR_EUC>;
+  ACF_RET(launch(T, X, d, XR, queries, n_q, num_cand, exclude_self != 0, excl_off, excl, cnorm, k, wper, S, lists,
+                 err, s));
+  k_topk_merge<<<(unsigned)n_q, 256, 0, s>>>(lists, S, k, out_items, out_scores);
+  HIP_TRY(hipGetLastError());
+  if (check) {
+    int32_t herr = 0;
+    ACF_RET(read_error_word(err, s, &herr));
+    ACF_CHECK(herr == 0, ACF_E_RANGE, "index out of range (query >= num_query_rows)");
+  }
+  return ACF_OK;
+}
+
+// ---- multi-item evaluation (acf_eval_multi.h) ---------------------------------
+static int evx_check(int32_t n_users, int64_t n_tests, int32_t num_cand) {
+  ACF_CHECK(n_users >= 0 && n_tests >= 0, ACF_E_INVALID, "negative count");
+  ACF_CHECK(n_tests < ((int64_t)1 << 31), ACF_E_INVALID, "more than 2^31 - 1 test items");
+  ACF_CHECK(num_cand >= 1, ACF_E_INVALID, "num_candidates must be >= 1, got %d", num_cand);
+  return ACF_OK;
+}
+
+extern "C" int acf_eval_positions_multi_workspace(int32_t n_users, int64_t n_tests, int32_t num_cand,
+                                                  size_t* bytes) {
+  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
+  ACF_RET(evx_check(n_users, n_tests, num_cand));
+  *bytes = evx_workspace(n_users, n_tests, num_cand);
+  return ACF_OK;
+}
+
+extern "C" int acf_eval_positions_multi(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
+                                        const int32_t* users, const int64_t* test_off, const int32_t* test_items,
+                                        int32_t n_users, int64_t n_tests, int32_t num_cand, const int64_t* excl_off,
+                                        const int32_t* excl, int32_t* positions, void* workspace,
+                                        size_t workspace_bytes, int32_t check, void* stream_) {
+  ACF_RET(check_dim(d));
+  ACF_RET(evx_check(n_users, n_tests, num_cand));
+  ACF_CHECK(U1 > 0 && I1 > 0, ACF_E_INVALID, "empty table");
+  ACF_CHECK(num_cand <= I1, ACF_E_INVALID, "num_candidates %d > item rows", num_cand);
+  ACF_CHECK(P && Q && users && test_off && test_items && positions && workspace, ACF_E_INVALID, "NULL argument");
+  ACF_RET(check_excl_pair(excl_off, excl));
+  ACF_RET(check_workspace(workspace, workspace_bytes, evx_workspace(n_users, n_tests, num_cand), 4));
+  if (n_users == 0 || n_tests == 0) return ACF_OK;
+  int wper = 0, S = 0;
+  evx_strips(n_users, n_tests, num_cand, &wper, &S);
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  int32_t* err = static_cast<int32_t*>(workspace);
+  int32_t* part = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + EVX_WS_HEAD);
+  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+  const dim3 grid((unsigned)((n_users + EVX_UB - 1) / EVX_UB), (unsigned)S);
+  k_evx_sweep<<<grid, 256, (size_t)EVX_UB * d * sizeof(float), s>>>(P, Q, d, U1, I1, users, test_off, test_items,
+                                                                     n_users, n_tests, num_cand, excl_off, excl, wper,
+                                                                     strip_target(part, S, positions), err);
+  HIP_TRY(hipGetLastError());
+  ACF_RET(sum_strips(part, S, n_tests, positions, s));
+  if (check) ACF_RET(check_eval_range(err, s));
+  return ACF_OK;
+}
+
+extern "C" int acf_eval_rank_metrics(const int32_t* positions, const int64_t* test_off, int32_t n_users,
+                                     const int32_t* n_neg, const int32_t* cutoffs, int32_t n_cutoffs,
+                                     double* per_user, double* per_user_free, double* mean_cut, double* mean_free,
+                                     int64_t* n_scored, void* stream_) {
+  ACF_CHECK(n_users >= 0, ACF_E_INVALID, "negative count");
+  ACF_CHECK(n_cutoffs >= 0 && n_cutoffs <= EVX_MAX_CUT, ACF_E_INVALID, "n_cutoffs %d outside [0, %d]", n_cutoffs,
+            EVX_MAX_CUT);
+  ACF_CHECK(cutoffs || n_cutoffs == 0, ACF_E_INVALID, "NULL argument");
+  EvxCuts cuts{};
+  cuts.n = n_cutoffs;
+  for (int c = 0; c < n_cutoffs; ++c) {
+    ACF_CHECK(cutoffs[c] >= 1 && cutoffs[c] <= EVX_MAX_K, ACF_E_INVALID, "cutoff %d outside [1, %d]", cutoffs[c],
+              EVX_MAX_K);
+    cuts.k[c] = cutoffs[c];
+  }
+  ACF_CHECK(test_off && mean_free && n_scored && (mean_cut || n_cutoffs == 0), ACF_E_INVALID, "NULL argument");
+  ACF_CHECK(n_users == 0 || (positions && n_neg && per_user_free && (per_user || n_cutoffs == 0)), ACF_E_INVALID,
+            "NULL argument");
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  if (n_users > 0) {
+    k_evx_metrics<<<(unsigned)n_users, 256, 0, s>>>(positions, test_off, n_neg, cuts, per_user, per_user_free);
+    HIP_TRY(hipGetLastError());
+  }
+  const int ncol = n_cutoffs * EVX_NM;
+  k_evx_means<<<(unsigned)(ncol + 2), 256, 0, s>>>(per_user, per_user_free, test_off, n_users, ncol, mean_cut,
+                                                   mean_free, n_scored);
+  HIP_TRY(hipGetLastError());
+  return ACF_OK;
+}
+
+// ---- certified worst-case positions (acf_eval_worst.h) -------------------------
+static int evw_check(int32_t n_users, int32_t num_cand, int32_t n_eps) {
+  ACF_CHECK(n_users >= 0, ACF_E_INVALID, "negative count");
+  ACF_CHECK(num_cand >= 1, ACF_E_INVALID, "num_candidates must be >= 1, got %d", num_cand);
+  ACF_CHECK(n_eps >= 1 && n_eps <= EVW_MAX_EPS, ACF_E_INVALID, "n_eps %d outside [1, %d]", n_eps, EVW_MAX_EPS);
+  return ACF_OK;
+}
+
+extern "C" int acf_eval_positions_worst_workspace(int32_t n_users, int32_t num_cand, int32_t n_eps, size_t* bytes) {
+  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
+  ACF_RET(evw_check(n_users, num_cand, n_eps));
+  *bytes = evw_workspace(n_users, num_cand, n_eps);
+  return ACF_OK;
+}
+
+template <int UB, bool USER>
+static void launch_evw(const float* P, const float* Q, int d, int64_t U1, int64_t I1, const int32_t* users,
+                       const int32_t* tests, int n_users, int num_cand, const int64_t* excl_off, const int32_t* excl,
+                       const EvwEps& eps, int wper, int S, int32_t* out, int32_t* err, hipStream_t s) {
+  const dim3 grid((unsigned)((n_users + UB - 1) / UB), (unsigned)S);
+  const size_t lds = (size_t)(USER ? 2 : 1) * UB * d * sizeof(float);
+  k_evw_sweep<UB, USER><<<grid, 256, lds, s>>>(P, Q, d, U1, I1, users, tests, n_users, num_cand, excl_off, excl, eps,
+                                               wper, out, err);
+}
+
+extern "C" int acf_eval_positions_worst(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
+                                        const int32_t* users, const int32_t* test_items, int32_t n_users,
+                                        int32_t num_cand, const int64_t* excl_off, const int32_t* excl,
+                                        const float* eps, int32_t n_eps, int32_t side, int32_t* worst,
+                                        void* workspace, size_t workspace_bytes, int32_t check, void* stream_) {
+  ACF_RET(check_dim(d));
+  ACF_RET(evw_check(n_users, num_cand, n_eps));
+  ACF_CHECK(side == 0 || side == 1, ACF_E_INVALID, "side must be 0 (user) or 1 (item), got %d", side);
+  ACF_CHECK(eps, ACF_E_INVALID, "NULL argument");
+  EvwEps ev{};
+  ev.n = n_eps;
+  for (int e = 0; e < EVW_MAX_EPS; ++e) {
+    const float v = eps[std::min(e, n_eps - 1)];  // the unused slots repeat the last one
+    ACF_CHECK(std::isfinite(v) && v >= 0.f, ACF_E_INVALID, "eps must be finite and >= 0, got %g", (double)v);
+    ev.e[e] = v;
+  }
+  ACF_CHECK(U1 > 0 && I1 > 0, ACF_E_INVALID, "empty table");
+  ACF_CHECK(num_cand <= I1, ACF_E_INVALID, "num_candidates %d > item rows", num_cand);
+  ACF_CHECK(P && Q && users && test_items && worst && workspace, ACF_E_INVALID, "NULL argument");
+  ACF_RET(check_excl_pair(excl_off, excl));
+  ACF_RET(check_workspace(workspace, workspace_bytes, evw_workspace(n_users, num_cand, n_eps), 4));
+  if (n_users == 0) return ACF_OK;
+  int wper = 0, S = 0;
+  evw_strips(n_users, num_cand, n_eps, &wper, &S);
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  int32_t* err = static_cast<int32_t*>(workspace);
+  int32_t* part = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + EVW_WS_HEAD);
+  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+  const bool wide = d <= EVW_D_SPLIT;  // 8 entries per workgroup, 4 above: the rows stay within 32 KB of LDS
+  const auto launch = side == 0 ? (wide ? &launch_evw<EVW_UB, true> : &launch_evw<EVW_UB / 2, true>)
+                                : (wide ? &launch_evw<EVW_UB, false> : &launch_evw<EVW_UB / 2, false>);
+  launch(P, Q, d, U1, I1, users, test_items, n_users, num_cand, excl_off, excl, ev, wper, S,
+         strip_target(part, S, worst), err, s);
+  HIP_TRY(hipGetLastError());
+  ACF_RET(sum_strips(part, S, (int64_t)n_eps * n_users, worst, s));
+  if (check) ACF_RET(check_eval_range(err, s));
+  return ACF_OK;
+}
+
+// ---- whole-stream adversarial direction (acf_adv.h) -------------------------
+static int adv_check(int64_t n, int64_t U1, int64_t I1, int32_t d) {
+  ACF_RET(check_dim(d));
+  ACF_CHECK(U1 > 0 && I1 > 0, ACF_E_INVALID, "empty table");
+  ACF_CHECK(U1 + I1 < ((int64_t)1 << 31), ACF_E_INVALID, "more than 2^31 - 1 table rows");
+  ACF_CHECK(n >= 0 && n < ((int64_t)1 << 29), ACF_E_INVALID, "n must lie in [0, 2^29), got %lld", (long long)n);
+  return ACF_OK;
+}
+
+extern "C" int acf_adv_direction_workspace(int64_t n, int64_t U1, int64_t I1, int32_t d, size_t* bytes) {
+  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
+  ACF_RET(adv_check(n, U1, I1, d));
+  *bytes = adv_layout(n, U1, I1, d).total;
+  return ACF_OK;
+}
+
+template <int LPR, int NV>
+static void launch_adv_random(uint64_t seed, uint32_t call, int32_t t, int d, int64_t U1, int64_t R, float* nP,
+                              float* nQ, hipStream_t s) {
+  k_adv_random<LPR, NV><<<grid_for(R * LPR), 256, 0, s>>>(seed, call, t, d, U1, R, nP, nQ);
+}
+
+template <int LPR, int NV>
+static void launch_adv_sum(const float* P, const float* Q, int d, int64_t U1, int64_t R, const int32_t* off,
+                           const int2* rec, float* part, float* nP, float* nQ, int64_t units, hipStream_t s) {
+  k_adv_chunks<LPR, NV><<<grid_for(units * LPR), 256, 0, s>>>(P, Q, d, U1, R, off, rec, part, nP, nQ, units);
+  k_adv_combine<LPR, NV><<<grid_for(R * LPR), 256, 0, s>>>(d, U1, R, off, part, nP, nQ);
+}
+
+extern "C" int acf_adv_direction(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
+                                 const int32_t* user, const int32_t* ipos, const int32_t* ineg, int64_t n,
+                                 float clip_lo, float clip_hi, int32_t adv_mode, uint64_t seed, uint32_t call,
+                                 int32_t t, float* nP, float* nQ, void* workspace, size_t workspace_bytes,
+                                 int32_t check, void* stream_) {
+  ACF_RET(adv_check(n, U1, I1, d));
+  ACF_CHECK(adv_mode == 0 || adv_mode == 1, ACF_E_INVALID, "adv_mode must be 0 (grad) or 1 (random), got %d",
+            adv_mode);
+  ACF_CHECK(P && Q && nP && nQ, ACF_E_INVALID, "NULL argument");
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  const int64_t R = U1 + I1;
+  if (adv_mode == 1) {  // the triplets are not read
+    ACF_RET(DISPATCH_GEOM(d, launch_adv_random, seed, call, t, d, U1, R, nP, nQ, s));
+    HIP_TRY(hipGetLastError());
+    return ACF_OK;
+  }
+  if (n == 0) {
+    HIP_TRY(hipMemsetAsync(nP, 0, (size_t)U1 * d * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(nQ, 0, (size_t)I1 * d * sizeof(float), s));
+    return ACF_OK;
+  }
+  ACF_CHECK(user && ipos && ineg && workspace, ACF_E_INVALID, "NULL argument");
+  const AdvLayout L = adv_layout(n, U1, I1, d);
+  ACF_RET(check_workspace(workspace, workspace_bytes, L.total, 16));
+  char* ws = static_cast<char*>(workspace);
+  float* coef = reinterpret_cast<float*>(ws + L.coef);
+  uint32_t* kb[2] = {reinterpret_cast<uint32_t*>(ws + L.k0), reinterpret_cast<uint32_t*>(ws + L.k1)};
+  uint32_t* vb[2] = {reinterpret_cast<uint32_t*>(ws + L.v0), reinterpret_cast<uint32_t*>(ws + L.v1)};
+  uint32_t* counts = reinterpret_cast<uint32_t*>(ws + L.counts);
+  uint32_t* tsum = reinterpret_cast<uint32_t*>(ws + L.tsum);
+  int32_t* off = reinterpret_cast<int32_t*>(ws + L.off);
+  float* part = reinterpret_cast<float*>(ws + L.part);
+  int32_t* err = reinterpret_cast<int32_t*>(ws + L.err);
+  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+  k_adv_stage<<<grid_for(n), 256, 0, s>>>(P, Q, d, user, ipos, ineg, n, U1, I1, clip_lo, clip_hi, coef, kb[0], vb[0],
+                                           err);
+  HIP_TRY(hipGetLastError());
+  if (check) {  // before anything is built on the indices
+    int32_t herr = 0;
+    ACF_RET(read_error_word(err, s, &herr));
+    ACF_CHECK(herr == 0, ACF_E_RANGE, "triplet index out of range (%s%s)",
+              (herr & 1) ? "user >= num_user_rows " : "", (herr & 2) ? "item >= num_item_rows" : "");
+  }
+  int cur = 0;
+  for (int p = 0; p < L.passes; ++p, cur ^= 1) {
+    k_adv_hist<<<(unsigned)L.ntiles, ADV_SORT_BS, 0, s>>>(kb[cur], L.N, 8 * p, L.ntiles, counts);
+    k_adv_scan1<<<(unsigned)L.T, 256, 0, s>>>(counts, L.M, tsum);
+    k_adv_scan2<<<1, 1024, 0, s>>>(tsum, L.T);
+    k_adv_scan3<<<(unsigned)L.T, 256, 0, s>>>(counts, L.M, tsum);
+    k_adv_reorder<<<(unsigned)L.ntiles, ADV_SORT_BS, 0, s>>>(kb[cur], vb[cur], kb[cur ^ 1], vb[cur ^ 1], L.N, 8 * p,
+                                                            L.ntiles, counts);
+    HIP_TRY(hipGetLastError());
+  }
+  int2* rec = reinterpret_cast<int2*>(kb[cur ^ 1]);  // the free (keys, values) pair: N * 8 bytes
+  k_adv_offsets<<<grid_for(R + 1), 256, 0, s>>>(kb[cur], L.N, R, off);
+  k_adv_records<<<grid_for(L.N), 256, 0, s>>>(vb[cur], L.N, n, user, ipos, ineg, U1, I1, coef, rec);
+  HIP_TRY(hipGetLastError());
+  const int64_t units = L.N / ADV_CHUNK + R + 1;
+  ACF_RET(DISPATCH_GEOM(d, launch_adv_sum, P, Q, d, U1, R, off, rec, part, nP, nQ, units, s));
+  HIP_TRY(hipGetLastError());
+  return ACF_OK;
+}
+
+extern "C" int acf_adv_apply(const float* W, const float* N, int64_t rows, int32_t d, float eps, float* delta_out,
+                             float* sum_out, void* stream_) {
+  ACF_CHECK(rows >= 0 && d > 0, ACF_E_INVALID, "negative size");
+  ACF_CHECK(N && (W || !sum_out), ACF_E_INVALID, "NULL argument");
+  const int64_t count = rows * (int64_t)d;
+  if (count == 0 || (!delta_out && !sum_out)) return ACF_OK;
+  k_adv_apply<<<grid_for(count), 256, 0, static_cast<hipStream_t>(stream_)>>>(W, N, count, eps, delta_out, sum_out);
+  HIP_TRY(hipGetLastError());
+  return ACF_OK;
+}

@@ -1,6 +1,7 @@
-// acf_rows.h — device row helpers shared by the APR step kernels (acf_apr.hip)
-// and the decomposed per-op kernels (acf_ops.hip): row-group loads/stores, the
-// TF-order dot product, the BPR term, and the counter-based RNG.
+// acf_rows.h — device row helpers shared by the APR step kernels (acf_apr.hip),
+// the ranking kernels (acf_rank.hip) and the decomposed per-op kernels
+// (acf_ops.hip): row-group loads/stores, the TF-order dot product, the BPR term,
+// the counter-based RNG and the random delta drawn from it.
 #ifndef ACF_ROWS_H
 #define ACF_ROWS_H
 
@@ -184,6 +185,29 @@ __device__ __forceinline__ float trunc_normal(uint64_t key, float stddev) {
     float z = r * cosf(6.283185307179586f * u01(h2));
     if (fabsf(z) <= 2.0f || a > 64) return z * stddev;
   }
+}
+
+// "random" delta: l2_normalize(truncated_normal(0, 0.01)) * eps, redrawn every
+// run (APR.py:180-191, adv == "random").  Out of line: the gradient mode never
+// runs it and it would otherwise bloat every step kernel's instruction stream.
+template <int LPR, int NV>
+__device__ __noinline__ RowV<NV> random_delta(uint64_t seed, uint32_t call, int32_t t, int32_t d, float eps,
+                                              int is_item, int32_t row, int l) {
+  RowV<NV> z;
+  const uint64_t rk = mix64(seed ^ mix64(((uint64_t)call << 33) ^ (((uint64_t)t << 1) | (is_item ? 1 : 0)))) ^
+                      mix64((uint64_t)row * 0x100000001B3ull);
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    const int c = l + LPR * v;
+    float e4[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      e4[e] = (c * 4 + e < d) ? trunc_normal(rk ^ mix64((uint64_t)(c * 4 + e)), 0.01f) : 0.f;
+    z.v[v] = make_float4(e4[0], e4[1], e4[2], e4[3]);
+  }
+  const float ss = dot_row<LPR, NV>(z, z);
+  const float inv = __builtin_amdgcn_rsqf(fmaxf(ss, 1e-12f));
+  return scale_row(scale_row(z, inv), eps);
 }
 
 #endif  // ACF_ROWS_H

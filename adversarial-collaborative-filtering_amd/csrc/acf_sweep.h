@@ -1,5 +1,5 @@
 // What the VALU score sweeps of libacf_apr.so share (k_eval_all, k_topk_valu,
-// k_evx_sweep; seq_dot: every ranking kernel): included by acf_apr.hip before
+// k_evx_sweep; seq_dot: every ranking kernel): included by acf_rank.hip before
 // acf_eval.h; one translation unit.  __device__ __forceinline__ pieces and two
 // host helpers, no kernels.  DESIGN.md §4.
 #pragma once

@@ -1,5 +1,5 @@
 // Top-K recommendation kernels of libacf_apr.so (k_topk_*): included by
-// acf_apr.hip after acf_sweep.h and acf_eval.h (seq_dot, the shared sweep pieces,
+// acf_rank.hip after acf_sweep.h and acf_eval.h (seq_dot, the shared sweep pieces,
 // the EVM_* tiling); one translation unit.
 #pragma once
 

@@ -644,6 +644,89 @@ def _unique_exclusions(off: torch.Tensor, ex: torch.Tensor, n_users: int) -> tor
     return torch.where(dup, torch.full_like(ex, -1), ex)
 
 
+# ---- what the ranking calls below share: argument checks, exclusion lists, workspace ----
+TOPK_MAX_K = 128
+
+
+def _check_k(k) -> None:
+    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f"k must be an int in [1, {TOPK_MAX_K}], got {k!r}")
+
+
+def _kernel_id(kernel) -> int:
+    if kernel not in EVAL_KERNELS:
+        raise ValueError(f"kernel must be one of {sorted(EVAL_KERNELS)}, got {kernel!r}")
+    return EVAL_KERNELS[kernel]
+
+
+def _check_num_candidates(num_candidates) -> None:
+    if isinstance(num_candidates, bool) or not isinstance(num_candidates, int) or num_candidates < 1:
+        raise ValueError(f"num_candidates must be an int >= 1, got {num_candidates!r}")
+
+
+def _table_types(A, B, a: str = "embedding_P", b: str = "embedding_Q") -> None:
+    """TypeError unless both tables are 2-D float32 tensors, ValueError if their
+    dims differ.  Looks at no device: a caller checks its host arguments between
+    this and _table_pair, so that tables on the CPU are what fails last."""
+    for tab, name in ((A, a), (B, b)):
+        if not isinstance(tab, torch.Tensor) or tab.dtype != torch.float32 or tab.dim() != 2:
+            raise TypeError(f"{name} must be a 2-D torch.float32 tensor")
+    if A.shape[1] != B.shape[1]:
+        raise ValueError(f"{a} and {b} dims differ")
+
+
+def _table_pair(A, B, a: str = "embedding_P", b: str = "embedding_Q") -> torch.device:
+    """The device of a pair of tables: both 2-D float32 and contiguous, B on A's
+    HIP device, equal dims (TypeError / ValueError)."""
+    _require(A, a, torch.float32, None, 2)
+    _require(B, b, torch.float32, A.device, 2)
+    _table_types(A, B, a, b)  # (only the dims are left to differ)
+    return A.device
+
+
+def _to_i32(t: torch.Tensor, dev) -> torch.Tensor:
+    return t.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def _exclusions(excl_off, excl_items, n: int, dev, rows: str | None = None):
+    """Per-row exclusion lists as (off int64 [n + 1], items int32) on `dev`, or
+    (None, None) without them; an empty item array becomes a one-element
+    placeholder (its pointer must not be NULL).  rows=None: a strict CSR
+    (_csr_items, _csr_offsets; checked on the host before anything moves).
+    rows="users" | "queries": whatever _idx takes, the offsets checked for their
+    length only, the message naming `rows`."""
+    if (excl_off is None) != (excl_items is None):
+        raise ValueError("excl_off and excl_items go together")
+    if excl_off is None:
+        return None, None
+    if rows is None:
+        ex = _csr_items(excl_items, "excl_items")
+        off = _csr_offsets(excl_off, n, ex.numel(), "excl_off").to(device=dev, dtype=torch.int64).contiguous()
+        ex = _to_i32(ex, dev) if ex.numel() else None
+    else:
+        off = torch.as_tensor(excl_off).to(device=dev, dtype=torch.int64).contiguous()
+        ex = _idx(excl_items, "excl_items", dev) if len(excl_items) else None
+        if off.numel() != n + 1:
+            raise ValueError(f"excl_off must have len({rows}) + 1 entries")
+    return off, ex if ex is not None else torch.zeros(1, dtype=torch.int32, device=dev)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _workspace_bytes(symbol: str, *sizes) -> int:
+    """A host-only acf_*_workspace query: ints in, bytes out."""
+    size = ctypes.c_size_t()
+    call(symbol, *(int(v) for v in sizes), ctypes.byref(size))
+    return int(size.value)
+
+
+def _workspace(nbytes: int, align: int, dev) -> torch.Tensor:
+    """At least nbytes of uninitialised device memory in units of `align` (4 or 8) bytes."""
+    return torch.empty((nbytes + align - 1) // align, dtype=torch.int64 if align == 8 else torch.int32, device=dev)
+
+
 def eval_positions_all(P, Q, users, test_items, num_candidates: int, excl_off, excl_items, kernel: str = "auto",
                        unique_lists: bool = False):
     """_eval_by_user positions over all items minus the exclusion lists.  kernel:
@@ -656,12 +739,8 @@ def eval_positions_all(P, Q, users, test_items, num_candidates: int, excl_off, e
     _require(P, "embedding_P", torch.float32, None, 2)
     _require(Q, "embedding_Q", torch.float32, dev, 2)
     u, t = _idx(users, "users", dev), _idx(test_items, "test_items", dev)
-    off = torch.as_tensor(excl_off).to(device=dev, dtype=torch.int64).contiguous()
-    ex = _idx(excl_items, "excl_items", dev) if len(excl_items) else torch.zeros(1, dtype=torch.int32, device=dev)
-    if off.numel() != u.numel() + 1:
-        raise ValueError("excl_off must have len(users) + 1 entries")
-    if kernel not in EVAL_KERNELS:
-        raise ValueError(f"kernel must be one of {sorted(EVAL_KERNELS)}, got {kernel!r}")
+    off, ex = _exclusions(excl_off, excl_items, u.numel(), dev, "users")
+    kernel = _kernel_id(kernel)
     _check_range(u, P.shape[0], "user")
     _check_range(t, Q.shape[0], "test item")
     if num_candidates > Q.shape[0]:
@@ -672,23 +751,16 @@ def eval_positions_all(P, Q, users, test_items, num_candidates: int, excl_off, e
     with _on(dev):
         call("acf_eval_positions_all_kernel", P.data_ptr(), Q.data_ptr(), P.shape[0], Q.shape[0], P.shape[1],
              u.data_ptr(), t.data_ptr(), u.numel(), int(num_candidates), off.data_ptr(), ex.data_ptr(),
-             pos.data_ptr(), EVAL_KERNELS[kernel], _stream_ptr(dev))
+             pos.data_ptr(), kernel, _stream_ptr(dev))
     return pos
-
-
-TOPK_MAX_K = 128
 
 
 def recommend_topk_workspace(n_users: int, num_candidates: int, k: int, kernel: str = "auto") -> int:
     """Bytes of device workspace acf_recommend_topk needs (a host-only query)."""
-    if kernel not in EVAL_KERNELS:
-        raise ValueError(f"kernel must be one of {sorted(EVAL_KERNELS)}, got {kernel!r}")
+    kernel = _kernel_id(kernel)
     if not 1 <= int(k) <= TOPK_MAX_K:
         raise ValueError(f"k must be in [1, {TOPK_MAX_K}], got {k}")
-    size = ctypes.c_size_t()
-    call("acf_recommend_topk_workspace", int(n_users), int(num_candidates), int(k), EVAL_KERNELS[kernel],
-         ctypes.byref(size))
-    return int(size.value)
+    return _workspace_bytes("acf_recommend_topk_workspace", n_users, num_candidates, k, kernel)
 
 
 def recommend_topk(P, Q, users, k: int, num_candidates: int | None = None, excl_off=None, excl_items=None,
@@ -701,15 +773,9 @@ def recommend_topk(P, Q, users, k: int, num_candidates: int | None = None, excl_
     score descending, ties to the lower item id; a user with fewer than k
     candidates gets -1 / -inf in the tail.  kernel: 'auto' | 'mfma' | 'valu'
     (identical outputs).  No [n, num_candidates] score array is formed."""
-    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= TOPK_MAX_K:
-        raise ValueError(f"k must be an int in [1, {TOPK_MAX_K}], got {k!r}")
-    if kernel not in EVAL_KERNELS:
-        raise ValueError(f"kernel must be one of {sorted(EVAL_KERNELS)}, got {kernel!r}")
-    _require(P, "embedding_P", torch.float32, None, 2)
-    dev = P.device
-    _require(Q, "embedding_Q", torch.float32, dev, 2)
-    if P.shape[1] != Q.shape[1]:
-        raise ValueError("embedding_P and embedding_Q dims differ")
+    _check_k(k)
+    kernel_id = _kernel_id(kernel)
+    dev = _table_pair(P, Q)
     settle_tables()
     u = _idx(users, "users", dev)
     n = u.numel()
@@ -718,47 +784,33 @@ def recommend_topk(P, Q, users, k: int, num_candidates: int | None = None, excl_
     num_candidates = int(num_candidates)
     if not 0 <= num_candidates <= Q.shape[0]:
         raise ValueError("num_candidates must lie in [0, item rows]")
-    if (excl_off is None) != (excl_items is None):
-        raise ValueError("excl_off and excl_items go together")
-    if excl_off is None:
+    off, ex = _exclusions(excl_off, excl_items, n, dev, "users")
+    if off is None:  # the C side takes no NULL here: an empty list per user
         off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
         ex = torch.zeros(1, dtype=torch.int32, device=dev)
-    else:
-        off = torch.as_tensor(excl_off).to(device=dev, dtype=torch.int64).contiguous()
-        ex = (_idx(excl_items, "excl_items", dev) if len(excl_items)
-              else torch.zeros(1, dtype=torch.int32, device=dev))
-        if off.numel() != n + 1:
-            raise ValueError("excl_off must have len(users) + 1 entries")
     _check_range(u, P.shape[0], "user")
     items = torch.empty((n, k), dtype=torch.int32, device=dev)
     scores = torch.empty((n, k), dtype=torch.float32, device=dev)
     if n == 0:
         return items, scores
     nbytes = recommend_topk_workspace(n, num_candidates, k, kernel)
-    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    work = _workspace(nbytes, 8, dev)
     with _on(dev):
         call("acf_recommend_topk", P.data_ptr(), Q.data_ptr(), P.shape[0], Q.shape[0], P.shape[1], u.data_ptr(),
              n, num_candidates, off.data_ptr(), ex.data_ptr(), k, items.data_ptr(), scores.data_ptr(),
-             work.data_ptr(), nbytes, EVAL_KERNELS[kernel], _stream_ptr(dev))
+             work.data_ptr(), nbytes, kernel_id, _stream_ptr(dev))
     return items, scores
 
 
 NEIGHBOR_METRICS = {"dot": 0, "cosine": 1, "euclid": 2}  # NBR_DOT, NBR_COS, NBR_EUC
 
 
-def _neighbor_k(k):
-    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= TOPK_MAX_K:
-        raise ValueError(f"k must be an int in [1, {TOPK_MAX_K}], got {k!r}")
-
-
 def neighbors_topk_workspace(n_queries: int, num_candidates: int, k: int) -> int:
     """Bytes of device workspace acf_neighbors_topk needs (a host-only query): a
     16-byte head, the strips' partial lists and the num_candidates floats of
     candidate norms the cosine metric uses."""
-    _neighbor_k(k)
-    size = ctypes.c_size_t()
-    call("acf_neighbors_topk_workspace", int(n_queries), int(num_candidates), int(k), ctypes.byref(size))
-    return int(size.value)
+    _check_k(k)
+    return _workspace_bytes("acf_neighbors_topk_workspace", n_queries, num_candidates, k)
 
 
 def neighbors_topk(T, queries, k: int, metric: str = "cosine", X=None, num_candidates: int | None = None,
@@ -777,17 +829,12 @@ def neighbors_topk(T, queries, k: int, metric: str = "cosine", X=None, num_candi
     Bad shapes, k and metric raise ValueError / TypeError before any native
     call; with check, a query outside X raises NativeIndexError (one sync),
     without it such a query is read as row 0."""
-    _neighbor_k(k)
+    _check_k(k)
     if metric not in NEIGHBOR_METRICS:
         raise ValueError(f"metric must be one of {sorted(NEIGHBOR_METRICS)}, got {metric!r}")
-    _require(T, "T", torch.float32, None, 2)
-    dev = T.device
     if X is None:
         X = T
-    else:
-        _require(X, "X", torch.float32, dev, 2)
-        if X.shape[1] != T.shape[1]:
-            raise ValueError("T and X dims differ")
+    dev = _table_pair(T, X, "T", "X")
     settle_tables()
     q = _idx(queries, "queries", dev)
     n = q.numel()
@@ -796,25 +843,16 @@ def neighbors_topk(T, queries, k: int, metric: str = "cosine", X=None, num_candi
     num_candidates = int(num_candidates)
     if not 0 <= num_candidates <= T.shape[0]:
         raise ValueError("num_candidates must lie in [0, table rows]")
-    if (excl_off is None) != (excl_items is None):
-        raise ValueError("excl_off and excl_items go together")
-    off = ex = None
-    if excl_off is not None:
-        off = torch.as_tensor(excl_off).to(device=dev, dtype=torch.int64).contiguous()
-        ex = (_idx(excl_items, "excl_items", dev) if len(excl_items)
-              else torch.zeros(1, dtype=torch.int32, device=dev))
-        if off.numel() != n + 1:
-            raise ValueError("excl_off must have len(queries) + 1 entries")
+    off, ex = _exclusions(excl_off, excl_items, n, dev, "queries")
     items = torch.empty((n, k), dtype=torch.int32, device=dev)
     scores = torch.empty((n, k), dtype=torch.float32, device=dev)
     if n == 0:
         return items, scores
     nbytes = neighbors_topk_workspace(n, num_candidates, k)
-    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    work = _workspace(nbytes, 8, dev)
     with _on(dev):
         call("acf_neighbors_topk", T.data_ptr(), T.shape[0], T.shape[1], X.data_ptr(), X.shape[0], q.data_ptr(), n,
-             num_candidates, NEIGHBOR_METRICS[metric], int(bool(exclude_self)),
-             off.data_ptr() if off is not None else None, ex.data_ptr() if ex is not None else None, k,
+             num_candidates, NEIGHBOR_METRICS[metric], int(bool(exclude_self)), _ptr(off), _ptr(ex), k,
              items.data_ptr(), scores.data_ptr(), work.data_ptr(), nbytes, int(bool(check)), _stream_ptr(dev))
     return items, scores
 
@@ -872,9 +910,7 @@ def _csr_items(t, name: str) -> torch.Tensor:
 
 def eval_positions_multi_workspace(n_users: int, n_tests: int, num_candidates: int) -> int:
     """Bytes of device workspace acf_eval_positions_multi needs (a host-only query)."""
-    size = ctypes.c_size_t()
-    call("acf_eval_positions_multi_workspace", int(n_users), int(n_tests), int(num_candidates), ctypes.byref(size))
-    return int(size.value)
+    return _workspace_bytes("acf_eval_positions_multi_workspace", n_users, n_tests, num_candidates)
 
 
 def eval_positions_multi(P, Q, users, test_off, test_items, num_candidates: int, excl_off=None, excl_items=None,
@@ -895,40 +931,24 @@ def eval_positions_multi(P, Q, users, test_off, test_items, num_candidates: int,
     ti = _csr_items(test_items, "test_items")
     us = _csr_items(users, "users")
     n, T = us.numel(), ti.numel()
-    if (excl_off is None) != (excl_items is None):
-        raise ValueError("excl_off and excl_items go together")
-    ex = None if excl_items is None else _csr_items(excl_items, "excl_items")
-    if isinstance(num_candidates, bool) or not isinstance(num_candidates, int) or num_candidates < 1:
-        raise ValueError(f"num_candidates must be an int >= 1, got {num_candidates!r}")
-    for tab, name in ((P, "embedding_P"), (Q, "embedding_Q")):
-        if not isinstance(tab, torch.Tensor) or tab.dtype != torch.float32 or tab.dim() != 2:
-            raise TypeError(f"{name} must be a 2-D torch.float32 tensor")
-    if P.shape[1] != Q.shape[1]:
-        raise ValueError("embedding_P and embedding_Q dims differ")
+    _check_num_candidates(num_candidates)
+    _table_types(P, Q)
     if num_candidates > Q.shape[0]:
         raise ValueError("num_candidates exceeds item rows")
     toff = _csr_offsets(test_off, n, T, "test_off")
-    eoff = None if ex is None else _csr_offsets(excl_off, n, ex.numel(), "excl_off")
-    _require(P, "embedding_P", torch.float32, None, 2)
-    dev = P.device
-    _require(Q, "embedding_Q", torch.float32, dev, 2)
+    eoff, ex = _exclusions(excl_off, excl_items, n, P.device)
+    dev = _table_pair(P, Q)
     toff = toff.to(device=dev, dtype=torch.int64).contiguous()
-    eoff = None if eoff is None else eoff.to(device=dev, dtype=torch.int64).contiguous()
     settle_tables()
-    u = us.to(device=dev, dtype=torch.int32).contiguous()
-    t = ti.to(device=dev, dtype=torch.int32).contiguous()
-    if ex is not None:
-        ex = (ex.to(device=dev, dtype=torch.int32).contiguous() if ex.numel()
-              else torch.zeros(1, dtype=torch.int32, device=dev))
+    u, t = _to_i32(us, dev), _to_i32(ti, dev)
     pos = torch.empty(T, dtype=torch.int32, device=dev)
     if n == 0 or T == 0:
         return pos
     nbytes = eval_positions_multi_workspace(n, T, num_candidates)
-    work = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+    work = _workspace(nbytes, 4, dev)
     with _on(dev):
         call("acf_eval_positions_multi", P.data_ptr(), Q.data_ptr(), P.shape[0], Q.shape[0], P.shape[1],
-             u.data_ptr(), toff.data_ptr(), t.data_ptr(), n, T, num_candidates,
-             eoff.data_ptr() if eoff is not None else None, ex.data_ptr() if ex is not None else None,
+             u.data_ptr(), toff.data_ptr(), t.data_ptr(), n, T, num_candidates, _ptr(eoff), _ptr(ex),
              pos.data_ptr(), work.data_ptr(), nbytes, int(bool(check)), _stream_ptr(dev))
     return pos
 
@@ -1009,9 +1029,7 @@ def _worst_eps(eps) -> tuple:
 
 def eval_positions_worst_workspace(n_users: int, num_candidates: int, n_eps: int) -> int:
     """Bytes of device workspace acf_eval_positions_worst needs (a host-only query)."""
-    size = ctypes.c_size_t()
-    call("acf_eval_positions_worst_workspace", int(n_users), int(num_candidates), int(n_eps), ctypes.byref(size))
-    return int(size.value)
+    return _workspace_bytes("acf_eval_positions_worst_workspace", n_users, num_candidates, n_eps)
 
 
 def eval_positions_worst(P, Q, users, test_items, num_candidates: int, excl_off=None, excl_items=None,
@@ -1039,41 +1057,24 @@ def eval_positions_worst(P, Q, users, test_items, num_candidates: int, excl_off=
     n = us.numel()
     if ti.numel() != n:
         raise ValueError(f"test_items must have one entry per user: {ti.numel()} for {n}")
-    if (excl_off is None) != (excl_items is None):
-        raise ValueError("excl_off and excl_items go together")
-    ex = None if excl_items is None else _csr_items(excl_items, "excl_items")
-    if isinstance(num_candidates, bool) or not isinstance(num_candidates, int) or num_candidates < 1:
-        raise ValueError(f"num_candidates must be an int >= 1, got {num_candidates!r}")
-    for tab, name in ((P, "embedding_P"), (Q, "embedding_Q")):
-        if not isinstance(tab, torch.Tensor) or tab.dtype != torch.float32 or tab.dim() != 2:
-            raise TypeError(f"{name} must be a 2-D torch.float32 tensor")
-    if P.shape[1] != Q.shape[1]:
-        raise ValueError("embedding_P and embedding_Q dims differ")
+    _check_num_candidates(num_candidates)
+    _table_types(P, Q)
     if num_candidates > Q.shape[0]:
         raise ValueError("num_candidates exceeds item rows")
-    eoff = None if ex is None else _csr_offsets(excl_off, n, ex.numel(), "excl_off")
-    _require(P, "embedding_P", torch.float32, None, 2)
-    dev = P.device
-    _require(Q, "embedding_Q", torch.float32, dev, 2)
-    eoff = None if eoff is None else eoff.to(device=dev, dtype=torch.int64).contiguous()
+    eoff, ex = _exclusions(excl_off, excl_items, n, P.device)
+    dev = _table_pair(P, Q)
     settle_tables()
-    u = us.to(device=dev, dtype=torch.int32).contiguous()
-    t = ti.to(device=dev, dtype=torch.int32).contiguous()
-    if ex is not None:
-        ex = (ex.to(device=dev, dtype=torch.int32).contiguous() if ex.numel()
-              else torch.zeros(1, dtype=torch.int32, device=dev))
+    u, t = _to_i32(us, dev), _to_i32(ti, dev)
     worst = torch.empty((len(es), n), dtype=torch.int32, device=dev)
     if n == 0:
         return worst
     nbytes = eval_positions_worst_workspace(n, num_candidates, len(es))
-    work = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+    work = _workspace(nbytes, 4, dev)
     ceps = (ctypes.c_float * len(es))(*es)
     with _on(dev):
         call("acf_eval_positions_worst", P.data_ptr(), Q.data_ptr(), P.shape[0], Q.shape[0], P.shape[1],
-             u.data_ptr(), t.data_ptr(), n, num_candidates,
-             eoff.data_ptr() if eoff is not None else None, ex.data_ptr() if ex is not None else None,
-             ceps, len(es), WORST_SIDES[side], worst.data_ptr(), work.data_ptr(), nbytes, int(bool(check)),
-             _stream_ptr(dev))
+             u.data_ptr(), t.data_ptr(), n, num_candidates, _ptr(eoff), _ptr(ex), ceps, len(es), WORST_SIDES[side],
+             worst.data_ptr(), work.data_ptr(), nbytes, int(bool(check)), _stream_ptr(dev))
     return worst
 
 
@@ -1085,10 +1086,7 @@ def adv_direction_workspace(n: int, num_user_rows: int, num_item_rows: int, dim:
     """Bytes of device workspace acf_adv_direction needs for n triplets (a host-only query)."""
     if not 0 <= int(n) <= ADV_MAX_TRIPLETS:
         raise ValueError(f"n must lie in [0, {ADV_MAX_TRIPLETS}], got {n}")
-    size = ctypes.c_size_t()
-    call("acf_adv_direction_workspace", int(n), int(num_user_rows), int(num_item_rows), int(dim),
-         ctypes.byref(size))
-    return int(size.value)
+    return _workspace_bytes("acf_adv_direction_workspace", n, num_user_rows, num_item_rows, dim)
 
 
 def adv_direction(P, Q, user, item_pos, item_neg, adv: str = "grad", seed: int = 0, call: int = 1, t: int = 0,
@@ -1110,11 +1108,7 @@ def adv_direction(P, Q, user, item_pos, item_neg, adv: str = "grad", seed: int =
         raise ValueError("user, item_pos and item_neg must have equal lengths")
     if n > ADV_MAX_TRIPLETS:
         raise ValueError(f"at most {ADV_MAX_TRIPLETS} triplets, got {n}")
-    _require(P, "embedding_P", torch.float32, None, 2)
-    dev = P.device
-    _require(Q, "embedding_Q", torch.float32, dev, 2)
-    if P.shape[1] != Q.shape[1]:
-        raise ValueError("embedding_P and embedding_Q dims differ")
+    dev = _table_pair(P, Q)
     u, i, j = (_idx(x, nm, dev) for x, nm in ((user, "user"), (item_pos, "item_pos"), (item_neg, "item_neg")))
     if not (u.numel() == i.numel() == j.numel() == n):
         raise ValueError("user, item_pos and item_neg must have equal lengths")
@@ -1124,13 +1118,12 @@ def adv_direction(P, Q, user, item_pos, item_neg, adv: str = "grad", seed: int =
     nQ = torch.empty((I1, d), dtype=torch.float32, device=dev)
     grad = adv == "grad"
     nbytes = adv_direction_workspace(n, U1, I1, d) if grad and n else 0
-    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev) if nbytes else None
+    work = _workspace(nbytes, 8, dev) if nbytes else None  # (the allocator aligns far above the 16 bytes asked for)
     with _on(dev):
         _native.call("acf_adv_direction", P.data_ptr(), Q.data_ptr(), U1, I1, d, u.data_ptr() if n else None,
                      i.data_ptr() if n else None, j.data_ptr() if n else None, n, clip_lo, clip_hi, ADV_MODES[adv],
                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF, int(t),
-                     nP.data_ptr(), nQ.data_ptr(), work.data_ptr() if work is not None else None, nbytes,
-                     int(bool(check)), _stream_ptr(dev))
+                     nP.data_ptr(), nQ.data_ptr(), _ptr(work), nbytes, int(bool(check)), _stream_ptr(dev))
     return nP, nQ
 
 
@@ -1147,7 +1140,7 @@ def adv_apply(W, N, eps: float, want_delta: bool = False):
     delta = torch.empty_like(W) if want_delta else None
     with _on(dev):
         _native.call("acf_adv_apply", W.data_ptr(), N.data_ptr(), W.shape[0], W.shape[1], float(eps),
-                     delta.data_ptr() if want_delta else None, out.data_ptr(), _stream_ptr(dev))
+                     _ptr(delta), out.data_ptr(), _stream_ptr(dev))
     return (out, delta) if want_delta else out
 
 

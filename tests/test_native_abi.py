@@ -56,6 +56,23 @@ def test_errors_surface_as_exceptions(native):
         native.call("acf_apr_create", ctypes.byref(p), 10, 10, 6, 4, 1)  # dim 6 unsupported
 
 
+def test_translation_units_share_one_error_string(native):
+    """An entry point of acf_rank.hip and one of acf_apr.hip, both called wrongly
+    on this thread: each leaves its own message in the library's one thread-local
+    string (acf_apr_last_error), overwriting the other's."""
+    import ctypes
+    lib = native.load()
+    size = ctypes.c_size_t(0)
+    last = lambda: lib.acf_apr_last_error().decode()  # noqa: E731
+    rank = lambda: lib.acf_eval_positions_worst_workspace(3, 0, 1, ctypes.byref(size))  # noqa: E731
+    engine = lambda: lib.acf_apr_set_slot_mapping(None, 7)  # noqa: E731
+    for first, second in ((rank, engine), (engine, rank)):
+        for fn in (first, second, first):
+            assert fn() == native.ACF_E_INVALID
+            want = "num_candidates must be >= 1, got 0" if fn is rank else "ctx is NULL"
+            assert last() == want
+
+
 def test_no_cpu_path(acf):
     ops = importlib.import_module(PKG + ".ops")
     P = torch.zeros(4, 8)

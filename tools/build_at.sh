@@ -10,7 +10,11 @@ git show $rev:include/acf_apr.h > $tmp/include/acf_apr.h
 for f in $(git ls-tree --name-only $rev adversarial-collaborative-filtering_amd/csrc/); do
   case $f in *.hip|*.h) git show $rev:$f > $tmp/csrc/$(basename $f);; esac
 done
+srcs=
+for s in acf_apr acf_rank acf_ops; do  # the library's sources that exist at $rev (acf_rank.hip: not before the split)
+  [ -f $tmp/csrc/$s.hip ] && srcs="$srcs $tmp/csrc/$s.hip"
+done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -I $tmp/include \
-  $tmp/csrc/acf_apr.hip $tmp/csrc/acf_ops.hip -o tools/libacf_apr_$rev.so
+  $srcs -o tools/libacf_apr_$rev.so
 rm -rf $tmp
 echo tools/libacf_apr_$rev.so
