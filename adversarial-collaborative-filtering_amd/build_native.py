@@ -37,8 +37,9 @@ LIBS = {
                         f"{PKG}/csrc/acf_eval_multi.h", f"{PKG}/csrc/acf_sweep.h",
                         f"{PKG}/csrc/acf_eval_worst.h", f"{PKG}/csrc/acf_neighbors.h"]},
     "neumf": {"lib": f"{PKG}/lib/libacf_neumf.so",
-              "srcs": [f"{PKG}/csrc/acf_neumf.hip"],
-              "headers": ["include/acf_apr.h", "include/acf_neumf.h", f"{PKG}/csrc/acf_topk_select.h"]},
+              "srcs": [f"{PKG}/csrc/acf_neumf.hip", f"{PKG}/csrc/acf_keras_mf.hip"],
+              "headers": ["include/acf_apr.h", "include/acf_neumf.h", f"{PKG}/csrc/acf_host.h",
+                          f"{PKG}/csrc/acf_neumf_adam.h", f"{PKG}/csrc/acf_topk_select.h"]},
     "torch": {"lib": f"{PKG}/lib/libacf_torch.so",
               "srcs": [f"{PKG}/csrc/acf_torch.cpp"],
               "headers": ["include/acf_apr.h"]},

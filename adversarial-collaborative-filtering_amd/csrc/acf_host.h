@@ -1,9 +1,12 @@
-// acf_host.h — host plumbing of the entry points in acf_apr.hip (training engine) and acf_rank.hip
-// (ranking family): error macros, launch grid, row geometry, dim check.  After hip_runtime.h, acf_apr.h.
+// acf_host.h — host plumbing of the entry points of both libraries: libacf_apr.so (acf_apr.hip, training
+// engine; acf_rank.hip, ranking family) and libacf_neumf.so (acf_neumf.hip, acf_keras_mf.hip): error macros,
+// launch grid, row geometry, dim check, the kernels' range bits.  After hip_runtime.h, acf_apr.h.
 #pragma once
 
-// The library's one thread-local error string and this function's one definition are in acf_apr.hip.
-int acf_set_error(int code, const char* fmt, ...);
+// Each library has one thread-local error string and one definition of this function (acf_apr.hip,
+// acf_neumf.hip).  Hidden: both libraries can be in one process, and an interposable symbol would send
+// one library's messages to the string of whichever was loaded first; so each binds to its own copy.
+__attribute__((visibility("hidden"))) int acf_set_error(int code, const char* fmt, ...);
 
 #define HIP_TRY(expr)                                                          \
   do {                                                                         \
@@ -55,6 +58,40 @@ static inline void geometry(int d, int* lpr, int* nv) {
     }                                                                               \
     return ACF_OK;                                                                  \
   }()
+
+// One float4 per lane (d <= 256): KFN<LPR> for the smallest power of two LPR with 4 LPR >= d.
+#define DISPATCH_LPR(d, KFN, ...)                                                     \
+  [&]() -> int {                                                                    \
+    int lpr_ = 1;                                                                   \
+    while (lpr_ * 4 < (d)) lpr_ <<= 1;                                              \
+    switch (lpr_) {                                                                 \
+      case 1: KFN<1>(__VA_ARGS__); break;                                           \
+      case 2: KFN<2>(__VA_ARGS__); break;                                           \
+      case 4: KFN<4>(__VA_ARGS__); break;                                           \
+      case 8: KFN<8>(__VA_ARGS__); break;                                           \
+      case 16: KFN<16>(__VA_ARGS__); break;                                         \
+      case 32: KFN<32>(__VA_ARGS__); break;                                         \
+      case 64: KFN<64>(__VA_ARGS__); break;                                         \
+      default: return acf_set_error(ACF_E_INVALID, "unsupported dim %d", (int)(d)); \
+    }                                                                               \
+    return ACF_OK;                                                                  \
+  }()
+
+// The error word the kernels of libacf_neumf.so set: bit 1 a user index, bit 2 an item index outside its
+// table (the kernel used row 0 instead).
+static inline int range_err(int32_t herr) {
+  ACF_CHECK(herr == 0, ACF_E_RANGE, "index out of range (%s%s)", (herr & 1) ? "user >= num_user_rows " : "",
+            (herr & 2) ? "item >= num_item_rows" : "");
+  return ACF_OK;
+}
+
+// ... read back from the device once stream s has run dry
+static inline int read_range_err(const int32_t* err, hipStream_t s) {
+  int32_t herr = 0;
+  HIP_TRY(hipMemcpyAsync(&herr, err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return range_err(herr);
+}
 
 static inline int check_dim(int d) {
   ACF_CHECK(d >= 4 && d <= 1024 && d % 4 == 0, ACF_E_INVALID,

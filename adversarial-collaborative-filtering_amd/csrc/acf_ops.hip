@@ -22,7 +22,8 @@
 #include "acf_apr.h"
 #include "acf_rows.h"
 
-int acf_set_error(int code, const char* fmt, ...);  // acf_apr.hip (thread-local message)
+// acf_apr.hip (thread-local message); hidden as in acf_host.h
+__attribute__((visibility("hidden"))) int acf_set_error(int code, const char* fmt, ...);
 
 #define OPS_TRY(expr)                                                               \
   do {                                                                              \

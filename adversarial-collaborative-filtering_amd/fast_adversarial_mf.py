@@ -30,8 +30,8 @@ import torch
 
 from . import _native
 from .neumf import mf_train_instances
-from .ops import _idx, _stream_ptr
-from .recommender import Recommender
+from .ops import _stream_ptr
+from .recommender import FlatMF, _npz
 
 
 def popularity_split(x, pop_percent):
@@ -47,24 +47,16 @@ def popularity_split(x, pop_percent):
     return ranked[:k], ranked[k:]
 
 
-class FastAdversarialMF(Recommender):
+class FastAdversarialMF(FlatMF):
+    _prefix = "acf_amf_"
+
     def __init__(self, uNum, iNum, dim, weight=1.0, pop_percent=0.2, lr=0.001, seed=None, device=None):
         if not torch.cuda.is_available() and device is None:
             raise RuntimeError("FastAdversarialMF needs a HIP device: there is no CPU path")
-        self.uNum, self.iNum, self.dim = int(uNum), int(iNum), int(dim)
         self.weight, self.pop_percent = float(weight), float(pop_percent)
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.hp = _native.NeuMFHParams(lr, 0.9, 0.999, 1e-7, 0.0, 0.0, 0, 0)
-        n = self.param_count(self.uNum, self.iNum, self.dim)
-        self.params = torch.as_tensor(self.keras_init(self.uNum, self.iNum, self.dim, seed)).to(self.device)
-        f = dict(dtype=torch.float32, device=self.device)
-        self.grad = torch.zeros(n, **f)
-        self.m = torch.zeros(n, **f)
-        self.v = torch.zeros(n, **f)
-        self.t = 0
-        self._rng = np.random.RandomState(seed)
+        self._init_flat(uNum, iNum, dim, self.keras_init(int(uNum), int(iNum), int(dim), seed),
+                        (lr, 0.9, 0.999, 1e-7), seed, device)
         self.popular_user_x = self.rare_user_x = self.popular_item_x = self.rare_item_x = None
-        self._ctx, self._ctx_batch = ctypes.c_void_p(), 0
 
     # -- layout --------------------------------------------------------------------
     @staticmethod
@@ -89,20 +81,6 @@ class FastAdversarialMF(Recommender):
             o += cls.disc_block(d)
         return buf
 
-    @property
-    def uEmb(self) -> torch.Tensor:
-        return self.params[: self.uNum * self.dim].view(self.uNum, self.dim)
-
-    @property
-    def iEmb(self) -> torch.Tensor:
-        return self.params[self.uNum * self.dim: (self.uNum + self.iNum) * self.dim].view(self.iNum, self.dim)
-
-    def neighbor_tables(self):
-        """uEmb / iEmb as evaluate.similar_items / similar_users take them (no padding rows)."""
-        from types import SimpleNamespace
-        return SimpleNamespace(embedding_P=self.uEmb, embedding_Q=self.iEmb, num_users=self.uNum,
-                               num_items=self.iNum)
-
     def discriminator(self, which: str) -> dict:
         """Views of D_u ("user") / D_i ("item"): W1 [d, d], b1 [d], W2 [d], b2 [1]."""
         d = self.dim
@@ -110,24 +88,6 @@ class FastAdversarialMF(Recommender):
         p = self.params
         return {"W1": p[o: o + d * d].view(d, d), "b1": p[o + d * d: o + d * d + d],
                 "W2": p[o + d * d + d: o + d * d + 2 * d], "b2": p[o + d * d + 2 * d: o + d * d + 2 * d + 1]}
-
-    def __del__(self):
-        try:
-            if self._ctx:
-                _native.load_neumf().acf_amf_destroy(self._ctx)
-        except Exception:
-            pass
-
-    def _context(self, batch):
-        if batch > self._ctx_batch:
-            if self._ctx:
-                _native.load_neumf().acf_amf_destroy(self._ctx)
-                self._ctx = ctypes.c_void_p()
-            with torch.cuda.device(self.device):
-                _native.call_neumf("acf_amf_create", ctypes.byref(self._ctx), self.uNum, self.iNum, self.dim,
-                                   int(batch))
-            self._ctx_batch = int(batch)
-        return self._ctx
 
     # -- Recommender API -----------------------------------------------------------
     def get_params(self):
@@ -203,16 +163,6 @@ class FastAdversarialMF(Recommender):
                                du.data_ptr(), di.data_ptr(), B, out.data_ptr(), _stream_ptr(self.device))
         return out
 
-    def rank(self, users, items):
-        u = _idx(users, "users", self.device)
-        it = _idx(items, "items", self.device)
-        out = torch.empty(u.numel(), dtype=torch.float32, device=self.device)
-        ctx = self._context(max(self._ctx_batch, 1))
-        with torch.cuda.device(self.device):
-            _native.call_neumf("acf_amf_predict", ctx, self.params.data_ptr(), u.data_ptr(), it.data_ptr(),
-                               u.numel(), out.data_ptr(), _stream_ptr(self.device))
-        return out.cpu().numpy().reshape(-1, 1)
-
     def save(self, path):
         """npz with the Keras layer names: the two embedding tables and the
         discriminators' Dense kernels / biases."""
@@ -221,10 +171,10 @@ class FastAdversarialMF(Recommender):
         for tag, D in (("disc_u", du), ("disc_i", di)):
             for k, t in D.items():
                 arrs[f"{tag}_{k}"] = t.cpu().numpy()
-        np.savez(path if path.endswith(".npz") else path + ".npz", **arrs)
+        np.savez(_npz(path), **arrs)
 
     def load_pre_train(self, pre):
-        with np.load(pre if pre.endswith(".npz") else pre + ".npz", allow_pickle=False) as z:
+        with np.load(_npz(pre), allow_pickle=False) as z:
             self.uEmb.copy_(torch.as_tensor(z["uEmb"]))
             self.iEmb.copy_(torch.as_tensor(z["iEmb"]))
             for tag, which in (("disc_u", "user"), ("disc_i", "item")):

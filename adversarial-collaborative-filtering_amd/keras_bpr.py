@@ -21,59 +21,18 @@ import numpy as np
 import torch
 
 from . import _native
-from .ops import _idx, _stream_ptr
-from .recommender import Recommender
+from .ops import _stream_ptr
+from .recommender import FlatMF, _npz
 
 
-class BPR(Recommender):
+class BPR(FlatMF):
+    _prefix = "acf_kbpr_"
+
     def __init__(self, uNum, iNum, dim, lr=0.001, beta1=0.9, beta2=0.999, adam_eps=1e-7, seed=None, device=None):
-        self.uNum, self.iNum, self.dim = int(uNum), int(iNum), int(dim)
         self.dns = 1
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.hp = _native.NeuMFHParams(lr, beta1, beta2, adam_eps, 0.0, 0.0, 0, 0)
-        f = dict(dtype=torch.float32, device=self.device)
-        n = (self.uNum + self.iNum) * self.dim
-        rng = np.random.default_rng(seed)
-        self.params = torch.as_tensor(rng.uniform(-0.05, 0.05, n).astype(np.float32)).to(self.device)
-        self.grad = torch.zeros(n, **f)
-        self.m = torch.zeros(n, **f)
-        self.v = torch.zeros(n, **f)
-        self.t = 0  # Adam iterations done
-        self._rng = np.random.RandomState(seed)
-        self._ctx, self._ctx_batch = ctypes.c_void_p(), 0
-
-    def __del__(self):
-        try:
-            if self._ctx:
-                _native.load_neumf().acf_kbpr_destroy(self._ctx)
-        except Exception:
-            pass
-
-    # -- Keras layer views -------------------------------------------------------
-    @property
-    def uEmb(self) -> torch.Tensor:
-        return self.params[: self.uNum * self.dim].view(self.uNum, self.dim)
-
-    @property
-    def iEmb(self) -> torch.Tensor:
-        return self.params[self.uNum * self.dim:].view(self.iNum, self.dim)
-
-    def neighbor_tables(self):
-        """uEmb / iEmb as evaluate.similar_items / similar_users take them (no padding rows)."""
-        from types import SimpleNamespace
-        return SimpleNamespace(embedding_P=self.uEmb, embedding_Q=self.iEmb, num_users=self.uNum,
-                               num_items=self.iNum)
-
-    def _context(self, batch):
-        if batch > self._ctx_batch:
-            if self._ctx:
-                _native.load_neumf().acf_kbpr_destroy(self._ctx)
-                self._ctx = ctypes.c_void_p()
-            with torch.cuda.device(self.device):
-                _native.call_neumf("acf_kbpr_create", ctypes.byref(self._ctx), self.uNum, self.iNum, self.dim,
-                                   int(batch))
-            self._ctx_batch = int(batch)
-        return self._ctx
+        n = (int(uNum) + int(iNum)) * int(dim)
+        init = np.random.default_rng(seed).uniform(-0.05, 0.05, n).astype(np.float32)
+        self._init_flat(uNum, iNum, dim, init, (lr, beta1, beta2, adam_eps), seed, device)
 
     # -- Recommender API -----------------------------------------------------------
     def get_params(self):
@@ -121,21 +80,11 @@ class BPR(Recommender):
         self.t += (n + batch_size - 1) // batch_size
         return float(losses.double().mean())
 
-    def rank(self, users, items):
-        u = _idx(users, "users", self.device)
-        it = _idx(items, "items", self.device)
-        out = torch.empty(u.numel(), dtype=torch.float32, device=self.device)
-        ctx = self._context(max(self._ctx_batch, 1))
-        with torch.cuda.device(self.device):
-            _native.call_neumf("acf_kbpr_predict", ctx, self.params.data_ptr(), u.data_ptr(), it.data_ptr(),
-                               u.numel(), out.data_ptr(), _stream_ptr(self.device))
-        return out.cpu().numpy().reshape(-1, 1)
-
     def save(self, path):
-        np.savez(path if path.endswith(".npz") else path + ".npz", uEmb=self.uEmb.cpu().numpy(),
+        np.savez(_npz(path), uEmb=self.uEmb.cpu().numpy(),
                  iEmb=self.iEmb.cpu().numpy())
 
     def load_pre_train(self, pre):
-        with np.load(pre if pre.endswith(".npz") else pre + ".npz", allow_pickle=False) as z:
+        with np.load(_npz(pre), allow_pickle=False) as z:
             self.uEmb.copy_(torch.as_tensor(z["uEmb"]))
             self.iEmb.copy_(torch.as_tensor(z["iEmb"]))

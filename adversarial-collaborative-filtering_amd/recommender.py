@@ -9,12 +9,14 @@ APR path.
 """
 from __future__ import annotations
 
+import ctypes
 from abc import ABC, abstractmethod
 from types import SimpleNamespace
 
 import numpy as np
+import torch
 
-from . import ops
+from . import _native, ops
 from .model import MF
 from .sampler import EpochTriplets
 
@@ -67,6 +69,72 @@ class Recommender(ABC):
         return similar_users(self.neighbor_tables(), users, k=k, metric=metric, rows=rows)
 
 
+def _npz(path):
+    return path if path.endswith(".npz") else path + ".npz"
+
+
+class FlatMF(Recommender):
+    """What keras_bpr.BPR and fast_adversarial_mf.FastAdversarialMF share: a dot-product
+    model of libacf_neumf.so whose parameters, gradient and Adam moments are four flat
+    float32 tensors in one layout that starts with [uEmb | iEmb], a native context
+    sized by the largest batch seen, and u . i scoring.  ``_prefix`` names the
+    engine's entry points (``<prefix>create / destroy / predict``)."""
+    _prefix = ""
+
+    def _init_flat(self, uNum, iNum, dim, init, adam, seed, device):
+        """init: the parameter buffer's initial values (numpy float32); adam: (lr, beta1, beta2, eps)."""
+        self.uNum, self.iNum, self.dim = int(uNum), int(iNum), int(dim)
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.hp = _native.NeuMFHParams(*adam, 0.0, 0.0, 0, 0)
+        self.params = torch.as_tensor(init).to(self.device)
+        self.grad, self.m, self.v = (torch.zeros_like(self.params) for _ in range(3))
+        self.t = 0  # Adam iterations done
+        self._rng = np.random.RandomState(seed)
+        self._ctx, self._ctx_batch = ctypes.c_void_p(), 0
+
+    def __del__(self):
+        try:
+            if self._ctx:
+                getattr(_native.load_neumf(), self._prefix + "destroy")(self._ctx)
+        except Exception:
+            pass
+
+    # -- Keras layer views -------------------------------------------------------
+    @property
+    def uEmb(self) -> torch.Tensor:
+        return self.params[: self.uNum * self.dim].view(self.uNum, self.dim)
+
+    @property
+    def iEmb(self) -> torch.Tensor:
+        return self.params[self.uNum * self.dim: (self.uNum + self.iNum) * self.dim].view(self.iNum, self.dim)
+
+    def neighbor_tables(self):
+        """uEmb / iEmb as evaluate.similar_items / similar_users take them (no padding rows)."""
+        return SimpleNamespace(embedding_P=self.uEmb, embedding_Q=self.iEmb, num_users=self.uNum,
+                               num_items=self.iNum)
+
+    def _context(self, batch):
+        if batch > self._ctx_batch:
+            if self._ctx:
+                getattr(_native.load_neumf(), self._prefix + "destroy")(self._ctx)
+                self._ctx = ctypes.c_void_p()
+            with torch.cuda.device(self.device):
+                _native.call_neumf(self._prefix + "create", ctypes.byref(self._ctx), self.uNum, self.iNum, self.dim,
+                                   int(batch))
+            self._ctx_batch = int(batch)
+        return self._ctx
+
+    def rank(self, users, items):
+        u = ops._idx(users, "users", self.device)
+        it = ops._idx(items, "items", self.device)
+        out = torch.empty(u.numel(), dtype=torch.float32, device=self.device)
+        ctx = self._context(max(self._ctx_batch, 1))
+        with torch.cuda.device(self.device):
+            _native.call_neumf(self._prefix + "predict", ctx, self.params.data_ptr(), u.data_ptr(), it.data_ptr(),
+                               u.numel(), out.data_ptr(), ops._stream_ptr(self.device))
+        return out.cpu().numpy().reshape(-1, 1)
+
+
 class APR(Recommender):
     """BPR-MF (adver=False) or APR (adver=True) behind the Recommender API."""
 
@@ -99,14 +167,13 @@ class APR(Recommender):
 
     def load_pre_train(self, pre):
         self._ensure()
-        with np.load(pre if pre.endswith(".npz") else pre + ".npz", allow_pickle=False) as z:
+        with np.load(_npz(pre), allow_pickle=False) as z:
             self.model.load_embeddings(z["embedding_P"], z["embedding_Q"])
 
     def save(self, path):
         self._ensure()
         ops.settle_tables()
-        np.savez(path if path.endswith(".npz") else path + ".npz",
-                 embedding_P=self.model.embedding_P.cpu().numpy(),
+        np.savez(_npz(path), embedding_P=self.model.embedding_P.cpu().numpy(),
                  embedding_Q=self.model.embedding_Q.cpu().numpy())
 
     def get_train_instances(self, train):
@@ -130,7 +197,6 @@ class APR(Recommender):
     def train(self, x_train, y_train, batch_size):
         """One pass over x_train in batches of batch_size (the trailing partial batch
         is dropped, as in APR.py:52); returns the mean clean loss per triplet."""
-        import torch
         from .train import training_batch, training_loss_acc
         self._ensure()
         m = self.model

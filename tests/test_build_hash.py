@@ -66,13 +66,19 @@ def test_load_refuses_library_after_header_edit(tmp_path):
 
 def test_load_neumf_refuses_library_after_source_edit(tmp_path):
     lib = _copy_tree(tmp_path, "neumf")
-    src = tmp_path / bn.LIBS["neumf"]["srcs"][0]
-    src.write_text(src.read_text() + "\n// edited\n")
+    srcs = bn.LIBS["neumf"]["srcs"]
+    assert [os.path.basename(s) for s in srcs] == ["acf_neumf.hip", "acf_keras_mf.hip"]
     saved = native._neumf
     native._neumf = None
     try:
-        with pytest.raises(ImportError, match="built from other sources"):
-            native.load_neumf(lib, str(tmp_path))
+        for rel in srcs:  # an edit to either unit, the other as built
+            src = tmp_path / rel
+            text = src.read_text()
+            src.write_text(text + "\n// edited\n")
+            with pytest.raises(ImportError, match="built from other sources"):
+                native.load_neumf(lib, str(tmp_path))
+            src.write_text(text)
+            bn.verify("neumf", lib, str(tmp_path))  # restored: accepted again
     finally:
         native._neumf = saved
 

@@ -38,7 +38,7 @@ def _model(uNum, iNum, d, dev, seed=1):
     return r, buf
 
 
-@pytest.mark.parametrize("d,B", [(8, 64), (64, 512), (32, 37)])
+@pytest.mark.parametrize("d,B", [(8, 64), (64, 512), (32, 37), (4, 16), (12, 37), (128, 32), (256, 16)])
 def test_batch_gradient_matches_oracle(dev, d, B):
     uNum, iNum = 50, 40
     r, buf = _model(uNum, iNum, d, dev)

@@ -14,11 +14,19 @@ from conftest import PKG
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("d,batch", [(32, 512), (64, 100), (8, 37)])
+# (d, batch) at tables of 400 x 300 rows and 2,300 triplets; the others, at 40 x 30 rows
+# and 150 triplets, make every lane-group width of the instance and predict kernels
+# (LPR = 1 .. 64) launch once, with a d that does not fill its lane group (12) and one
+# that spans several 64-lane sweeps of the row waves (132)
+_LARGE = [(32, 512), (64, 100), (8, 37)]
+_SMALL = [(4, 64), (12, 37), (128, 64), (132, 37), (256, 64)]
+
+
+@pytest.mark.parametrize("d,batch", _LARGE + _SMALL)
 def test_epoch_matches_oracle(dev, d, batch):
     from kbpr_oracle import kbpr_epoch
     KB = importlib.import_module(PKG + ".keras_bpr")
-    U1, I1, n = 400, 300, 2300
+    U1, I1, n = (400, 300, 2300) if (d, batch) in _LARGE else (40, 30, 150)
     rng = np.random.default_rng(d)
     u = rng.integers(1, U1, n).astype(np.int32)
     i = (rng.zipf(1.3, n) % (I1 - 1) + 1).astype(np.int32)  # hot items: many occurrences per batch
@@ -41,6 +49,31 @@ def test_epoch_matches_oracle(dev, d, batch):
     sc = r.rank(u[:50], i[:50]).reshape(-1)
     P, Q = got[: U1 * d].reshape(U1, d), got[U1 * d:].reshape(I1, d)
     np.testing.assert_allclose(sc, (P[u[:50]] * Q[i[:50]]).sum(1), rtol=1e-5, atol=1e-6)
+
+
+def test_out_of_range_raises(dev):
+    """An index one past its table: the kernels use row 0 and set the error word, and
+    train / rank raise NativeIndexError naming the table."""
+    KB = importlib.import_module(PKG + ".keras_bpr")
+    nat = importlib.import_module(PKG + "._native")
+    uNum, iNum, n = 20, 10, 16
+    rng = np.random.default_rng(0)
+    u = rng.integers(1, uNum, n).astype(np.int32)
+    i = rng.integers(1, iNum, n).astype(np.int32)
+    j = rng.integers(1, iNum, n).astype(np.int32)
+    r = KB.BPR(uNum, iNum, 8, seed=1, device=dev)
+    bad_u = u.copy()
+    bad_u[3] = uNum
+    only_user, only_item = r"\(user >= num_user_rows \)$", r"\(item >= num_item_rows\)$"
+    with pytest.raises(nat.NativeIndexError, match=only_user):
+        r.train([bad_u, i, j], np.ones(n), 8)
+    with pytest.raises(nat.NativeIndexError, match=only_user):
+        r.rank(bad_u, i)
+    bad_i = i.copy()
+    bad_i[5] = iNum
+    with pytest.raises(nat.NativeIndexError, match=only_item):
+        r.rank(u, bad_i)
+    assert np.isfinite(r.rank(u, i)).all()  # the context is usable afterwards
 
 
 def test_run_py_bpr_end_to_end(tmp_path, dev):

@@ -106,6 +106,63 @@ def test_neumf_library_exports_every_header_symbol(native):
     assert b"gfx950" in open(native.NEUMF_LIB_PATH, "rb").read()
 
 
+def test_neumf_translation_units_share_one_error_string(native):
+    """An entry point of acf_neumf.hip and one of acf_keras_mf.hip, both called wrongly
+    on this thread (rejected before any HIP call): each leaves its own message in
+    libacf_neumf.so's one thread-local string, overwriting the other's."""
+    import ctypes
+    lib = native.load_neumf()
+    ctx = ctypes.c_void_p()
+    last = lambda: lib.acf_neumf_last_error().decode()  # noqa: E731
+    neumf = lambda: lib.acf_neumf_adam(None, None, None, None, None, 1, None, None)  # noqa: E731
+    keras = lambda: lib.acf_kbpr_create(ctypes.byref(ctx), 10, 10, 6, 4)  # noqa: E731
+    for first, second in ((neumf, keras), (keras, neumf)):
+        for fn in (first, second, first):
+            assert fn() == native.ACF_E_INVALID
+            assert last() == ("NULL argument" if fn is neumf else "dim must be a multiple of 4 in [4, 256], got 6")
+    assert not ctx
+
+
+_TWO_LIBRARIES = r"""
+import ctypes, sys
+paths = {"apr": sys.argv[1], "neumf": sys.argv[2]}
+libs = {name: ctypes.CDLL(paths[name], mode=ctypes.RTLD_GLOBAL) for name in sys.argv[3:5]}
+apr, neumf = libs["apr"], libs["neumf"]
+apr.acf_apr_last_error.restype = neumf.acf_neumf_last_error.restype = ctypes.c_char_p
+apr.acf_apr_set_slot_mapping.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+neumf.acf_kbpr_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int64, ctypes.c_int64,
+                                  ctypes.c_int32, ctypes.c_int32]
+ctx = ctypes.c_void_p()
+fail = {"apr": lambda: apr.acf_apr_set_slot_mapping(None, 7),
+        "neumf": lambda: neumf.acf_kbpr_create(ctypes.byref(ctx), 10, 10, 6, 4)}
+last = {"apr": lambda: apr.acf_apr_last_error().decode(), "neumf": lambda: neumf.acf_neumf_last_error().decode()}
+want = {"apr": "ctx is NULL", "neumf": "dim must be a multiple of 4 in [4, 256], got 6"}
+for order in (("apr", "neumf"), ("neumf", "apr"), ("apr", "neumf")):
+    for name in order:
+        other = "neumf" if name == "apr" else "apr"
+        before = last[other]()
+        assert fail[name]() == 1, name
+        assert last[name]() == want[name], (name, last[name]())
+        assert last[other]() == before, (name, "wrote", other, last[other]())
+assert last["apr"]() == want["apr"] and last["neumf"]() == want["neumf"]
+print("ok")
+"""
+
+
+@pytest.mark.parametrize("order", [("apr", "neumf"), ("neumf", "apr")])
+def test_the_two_libraries_keep_their_own_error_strings(native, order):
+    """Both libraries define acf_set_error (csrc/acf_host.h).  Loaded into one fresh
+    process with RTLD_GLOBAL, in either order, a failing call in one sets that
+    library's *_last_error and leaves the other library's string alone."""
+    import subprocess
+    import sys
+    native.load_neumf()  # both built, and from these sources
+    assert native.ACF_E_INVALID == 1
+    r = subprocess.run([sys.executable, "-c", _TWO_LIBRARIES, native.LIB_PATH, native.NEUMF_LIB_PATH, *order],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+
+
 def test_neumf_layout_matches_keras_shapes(native):
     """The flat buffer holds the ten Keras tensors in order, 16-B aligned (host-only calls)."""
     import ctypes

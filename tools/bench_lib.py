@@ -1,7 +1,8 @@
 """bench.py over another build of libacf_apr.so (same-box A/Bs of the headline
 line): ACF_ALT_LIB=path loads that library in place of the package's, bypassing
-the build-hash check (as tools/large_line.py does); every other argument goes to
-bench.py unchanged.  Without ACF_ALT_LIB it is bench.py itself."""
+the build-hash check (as tools/large_line.py does); ACF_ALT_NEUMF_LIB=path does
+the same for libacf_neumf.so (the neumf line of --full); every other argument
+goes to bench.py unchanged.  With neither it is bench.py itself."""
 import ctypes
 import importlib
 import os
@@ -19,5 +20,13 @@ if alt:
             fn = getattr(lib, fname)
             fn.restype, fn.argtypes = res, args
     nat._lib = lib
+alt = os.environ.get("ACF_ALT_NEUMF_LIB")
+if alt:
+    nat = importlib.import_module(bench.PKG + "._native")
+    lib = ctypes.CDLL(alt)
+    for fname, (res, args) in nat.NEUMF_SIGNATURES.items():
+        fn = getattr(lib, fname)
+        fn.restype, fn.argtypes = res, args
+    nat._neumf = lib
 sys.argv = [bench.__file__] + sys.argv[1:]
 bench.main()
