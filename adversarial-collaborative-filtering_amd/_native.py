@@ -66,6 +66,8 @@ SIGNATURES = {
     "acf_apr_resolve": (ctypes.c_int, [_P]),
     "acf_apr_resolve_all": (ctypes.c_int, []),
     "acf_apr_share_failsafe": (ctypes.c_int, [_P, _P]),
+    "acf_plan_stream_create": (ctypes.c_int, [ctypes.POINTER(_P)]),
+    "acf_plan_stream_destroy": (ctypes.c_int, [_P]),
     "acf_apr_copy_losses": (ctypes.c_int, [_P, _P, _P, _P]),
     "acf_apr_delta_scatter": (ctypes.c_int, [_P, _P, _P, _P]),
     "acf_bpr_forward": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _P, _I32, _I32, _F, _F, _P, _P,

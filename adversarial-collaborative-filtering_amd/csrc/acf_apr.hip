@@ -714,6 +714,15 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// The plan of chunk c+1 runs beside chunk c's k_stream (PlanPipeline): a CU
+// that holds one k_stream workgroup (one wave of 240 VGPRs per SIMD) has 272
+// VGPRs per SIMD left, and a 1,024-thread plan workgroup puts 4 waves on each
+// SIMD, so it fits at <= 64 VGPRs per wave (allocated in eights).  The plan
+// kernels use 38 (sort) and 56 / 61 (build): they fit, and nothing pins that.
+// Capping them (__launch_bounds__(BS, 8): HIP's second argument is waves per
+// SIMD) also caps the SGPRs and spilled 33-52 of them in the build kernels, so
+// it was not taken; re-read the counts (tools/kernel_resources.py) after an
+// edit that costs registers.
 template <int BS, int IPT>
 __global__ void __launch_bounds__(BS) k_bplan_sort(BPlanArgs p) {
   constexpr int N = BS * IPT;
@@ -3725,6 +3734,11 @@ struct acf_apr_ctx {
   int32_t stream_depth = 2;  // ACF_STREAM_DEPTH: max waves per position (batches in flight)
   int32_t poll_sleep = 2;    // ACF_POLL_SLEEP: s_sleep between version polls (0-3; 4/5/6 = 8/16/32)
   int32_t spin_limit = ACF_SPIN_LIMIT;  // k_stream version polls before a give-up (acf_apr_set_spin_limit)
+  // a replay of a call of this context may still be reading the plan's records:
+  // replay_ev was recorded behind it on its stream, and the next plan waits on it
+  // (acf_apr_plan; the event, not the stream's handle, is what is kept)
+  hipEvent_t replay_ev = nullptr;
+  bool replay_dirty = false;
   int32_t failsafe = 1;      // verify every streamed call, replay a failed one (acf_apr_set_failsafe)
   unsigned long long* status = nullptr;      // host-mapped ring of 8: (seq << 2) | failed, per streamed launch
   unsigned long long* status_dev = nullptr;  // its device address
@@ -3819,6 +3833,7 @@ extern "C" int acf_apr_destroy(acf_apr_ctx* c) {
   c->graphs.clear();
   for (void* p : c->allocs) (void)hipFree(p);
   if (c->cap_stream) (void)hipStreamDestroy(c->cap_stream);
+  if (c->replay_ev) (void)hipEventDestroy(c->replay_ev);
   if (c->status) (void)hipHostFree(c->status);
   delete c;
   return r;
@@ -3993,6 +4008,9 @@ static int resolve(acf_apr_ctx* c, int mode) {
       prev = x.s;
       ACF_RET(run_loop(x.c, &x.tb, &x.hp, x.first, x.n, x.s, nullptr, nullptr, 0, 3));
       ++x.c->recoveries;
+      if (!x.c->replay_ev) HIP_TRY(hipEventCreateWithFlags(&x.c->replay_ev, hipEventDisableTiming));
+      HIP_TRY(hipEventRecord(x.c->replay_ev, x.s));
+      x.c->replay_dirty = true;
     }
   }
   return ACF_OK;
@@ -4348,6 +4366,13 @@ extern "C" int acf_apr_plan(acf_apr_ctx* c, const int32_t* user, const int32_t* 
   const uint32_t eb = std::max(eb_u, eb_i);  // item keys carry bit eb
   ACF_CHECK(eb < 64, ACF_E_INVALID, "plan key does not fit 64 bits");
   ACF_RET(resolve(c, 1));  // a queued streamed call of this context still needs its plan
+  if (c->replay_dirty) {
+    // a settling point replayed a call of this context on its own stream (the
+    // two-kernel schedule reads the records this plan overwrites): a plan on
+    // another stream -- PlanPipeline's side stream -- starts after that replay
+    c->replay_dirty = false;
+    HIP_TRY(hipStreamWaitEvent(s, c->replay_ev, 0));
+  }
   c->B = 0;
   c->nb = 0;
   c->last_delta_batch = -1;
@@ -5426,6 +5451,27 @@ extern "C" int acf_apr_set_spin_limit(acf_apr_ctx* c, int32_t polls) {
   ACF_RET(resolve(c, 2));  // settle queued streamed calls first (FailGroup)
   ACF_CHECK(polls >= 0, ACF_E_INVALID, "spin limit must be >= 0, got %d", polls);
   c->spin_limit = polls;
+  return ACF_OK;
+}
+
+// A stream of the device's LOWEST priority for work that runs beside the
+// persistent k_stream (PlanPipeline's next-chunk plan at small batches): where
+// both have workgroups to place, the step's go first, so a plan cannot keep a
+// k_stream launch from becoming resident.  (A framework stream cannot be made
+// lower than the default priority.)
+extern "C" int acf_plan_stream_create(void** out) {
+  ACF_CHECK(out, ACF_E_INVALID, "NULL argument");
+  int least = 0, greatest = 0;
+  HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+  hipStream_t s = nullptr;
+  HIP_TRY(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, least));
+  *out = s;
+  return ACF_OK;
+}
+
+extern "C" int acf_plan_stream_destroy(void* stream_) {
+  ACF_CHECK(stream_, ACF_E_INVALID, "NULL argument");
+  HIP_TRY(hipStreamDestroy(static_cast<hipStream_t>(stream_)));
   return ACF_OK;
 }
 

@@ -402,13 +402,19 @@ class PlanPipeline:
     are independent calls of train_planned (each ends with its flush), so the
     result is the one of planning and training the chunks in sequence.
 
-    overlap=False plans on the caller's stream instead.  overlap=None (default)
-    decides per run: concurrent planning for large batches (B >= 4,096: the
-    device-wide sort plan, ~40 us per batch); in line for smaller ones, whose
-    batch-local plan (two launches per chunk) costs less than the
-    events and stream hand-offs of planning beside the step, and never shares
-    the device with the persistent k_stream.  A run of a single chunk always
-    plans in line.
+    overlap=False plans on the caller's stream instead.  overlap=True (the
+    constructor's default) and overlap=None (the library's own choice, what
+    the benchmark and the model pass) now take the same schedule: concurrent
+    planning whenever the run has more than one chunk.  For large batches (B >= 4,096) that is the device-wide sort plan,
+    ~40 us per batch, on a side stream of the default priority.  For smaller
+    ones it is the batch-local plan (two launches per chunk)
+    beside the persistent k_stream: it goes to a stream of the lowest priority
+    (acf_plan_stream_create) and may start with the chunk it runs beside, so
+    the step's workgroups are placed first and the plan takes the slots
+    k_stream leaves free.  A run of a single chunk always plans in line: the
+    events and stream hand-offs cost more than a 20-batch plan.
+    ``overlapped`` tells which schedule the last run took.  The lowest-priority
+    stream belongs to the pipeline: ``close()`` (or a ``with`` block) destroys it.
     """
 
     def __init__(self, num_user_rows: int, num_item_rows: int, dim: int, batch_size: int,
@@ -424,7 +430,10 @@ class PlanPipeline:
         # (608M -> 313M triplets/s at d = 64, tools/large_prio.py, r03)
         # (the steps on a high-priority stream instead, the plan filling what they
         # leave idle, was 1.8x slower at configs[4]: 775M -> 424M triplets/s, r04)
-        self.side = torch.cuda.Stream(self.device)
+        # small batches plan beside the persistent k_stream: the lowest priority,
+        # which a torch stream cannot have (created at the first overlapped run)
+        self._low = None
+        self.side = torch.cuda.Stream(self.device) if self.batch_size >= 4096 else None
         self._free = [None, None]  # event: the last training on ctx[k] has been issued before it
         self._memo = None  # the last single-chunk call, validated (_repeat)
 
@@ -476,7 +485,45 @@ class PlanPipeline:
                        item_pos.data_ptr(), item_neg.data_ptr()),
                       _native.load().acf_apr_train, args, c, tb, h)
 
-    def _plan(self, k, u, i, j, b, n, check):
+    @property
+    def overlapped(self) -> bool:
+        """The last run planned chunk c+1 beside chunk c (False: in line)."""
+        return bool(self._ov)
+
+    def _side_stream(self):
+        if self.side is None:
+            h = ctypes.c_void_p()
+            with torch.cuda.device(self.device):
+                call("acf_plan_stream_create", ctypes.byref(h))
+            self._low = h.value
+            self.side = torch.cuda.ExternalStream(self._low, device=self.device)
+        return self.side
+
+    def close(self) -> None:
+        """Wait for the plan stream's work and destroy it (the lowest-priority
+        stream of small batches is this pipeline's own; a later overlapped run
+        makes a new one).  Errors surface here; __del__ calls it as a last
+        resort only."""
+        low, self._low = getattr(self, "_low", None), None
+        if low is None:
+            return
+        side, self.side = self.side, None
+        side.synchronize()
+        call("acf_plan_stream_destroy", low)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown: the process frees the stream
+            pass
+
+    def _plan(self, k, u, i, j, b, n, check, go=None):
         B, c = self.batch_size, self.ctx[k % 2]
         s = slice(b * B, (b + n) * B)
         if not self._ov:
@@ -485,6 +532,8 @@ class PlanPipeline:
         with torch.cuda.stream(self.side):
             if self._free[k % 2] is not None:
                 self.side.wait_event(self._free[k % 2])
+            if go is not None:  # not before the chunk it runs beside may start
+                self.side.wait_event(go)
             c.plan(u[s], i[s], j[s], B, check=check)
             ev = torch.cuda.Event()
             ev.record(self.side)
@@ -533,7 +582,7 @@ class PlanPipeline:
         main = torch.cuda.current_stream(self.device)
         chunks = [(b, min(self.chunk, first_batch + n_batches - b))
                   for b in range(first_batch, first_batch + n_batches, self.chunk)]
-        self._ov = (self.overlap if self.overlap is not None else B >= 4096) and len(chunks) > 1
+        self._ov = self.overlap is not False and len(chunks) > 1
         if not self._ov:  # plan + train per chunk in one C call each, on the caller's stream
             for k, (b, n) in enumerate(chunks):
                 self.ctx[k % 2].train_range(tables, hp, u, i, j, B, b, n, graph=graph, check=check, _checked=True)
@@ -543,17 +592,22 @@ class PlanPipeline:
             return
         ready = torch.cuda.Event()
         ready.record(main)  # triplets produced on the caller's stream
-        self.side.wait_event(ready)
+        self._side_stream().wait_event(ready)
         planned = self._plan(0, u, i, j, *chunks[0], check)
         for k, (b, n) in enumerate(chunks):
             if planned is not None:
                 main.wait_event(planned)
+            go = None
+            if self._low is not None and k + 1 < len(chunks):
+                # beside k_stream: the next plan may start with this chunk, not ahead of it
+                go = torch.cuda.Event()
+                go.record(main)
             self.ctx[k % 2].train_planned(tables, hp, 0, n, graph=graph)
             done = torch.cuda.Event()
             done.record(main)
             self._free[k % 2] = done
             if k + 1 < len(chunks):
-                planned = self._plan(k + 1, u, i, j, *chunks[k + 1], check)
+                planned = self._plan(k + 1, u, i, j, *chunks[k + 1], check, go)
         self._staged = (u, i, j)
 
 

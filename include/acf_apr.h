@@ -228,6 +228,13 @@ int acf_apr_resolve_all(void);
  * one stream (a PlanPipeline's contexts) must share one, so that a failed call
  * of either gates the later calls of both.  Settles both groups first. */
 int acf_apr_share_failsafe(acf_apr_ctx* ctx, acf_apr_ctx* peer);
+/* A non-blocking stream of the current device's lowest priority, for plans
+ * that run beside a streamed call (acf_apr_plan of the next chunk on it while
+ * k_stream trains this one on the caller's stream): where both have workgroups
+ * to place, the step's go first.  The caller orders the two streams with
+ * events and destroys the stream when its work has been waited for. */
+int acf_plan_stream_create(void** out);
+int acf_plan_stream_destroy(void* stream);
 
 /* ---- shard mode: users and items row-sharded over the ranks of one node ----
  * SURVEY §8(e) (no reference counterpart: the reference trains on one CPU
