@@ -96,6 +96,8 @@ SIGNATURES = {
     "acf_adv_apply": (ctypes.c_int, [_P, _P, _I64, _I32, _F, _P, _P, _P]),
     "acf_fold_in_users": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _P, _I64, _I32, _I32,
                                          ctypes.POINTER(HParams), _P, _P, _P, _P, _P, _I32, _P]),
+    "acf_fold_in_items": (ctypes.c_int, [_P, _I64, _P, _I64, _I32, _P, _I64, _P, _P, _I64, _I32, _I32,
+                                         ctypes.POINTER(HParams), _P, _P, _P, _P, _P, _I32, _P]),
     "acf_sample_epoch": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _U64, _I32, _I32, _P, _P,
                                         _P, _P]),
     "acf_gather_bpr_fwd_bwd": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _P, _I64, _F, _F, _P, _P, _P,

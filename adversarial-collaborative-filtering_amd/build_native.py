@@ -33,7 +33,7 @@ LIBS = {
             "headers": ["include/acf_apr.h", f"{PKG}/csrc/acf_host.h", f"{PKG}/csrc/acf_rows.h",
                         f"{PKG}/csrc/acf_hplan.h",
                         f"{PKG}/csrc/acf_eval.h", f"{PKG}/csrc/acf_topk.h", f"{PKG}/csrc/acf_adv.h",
-                        f"{PKG}/csrc/acf_fold.h", f"{PKG}/csrc/acf_topk_select.h",
+                        f"{PKG}/csrc/acf_fold.h", f"{PKG}/csrc/acf_fold_items.h", f"{PKG}/csrc/acf_topk_select.h",
                         f"{PKG}/csrc/acf_eval_multi.h", f"{PKG}/csrc/acf_sweep.h",
                         f"{PKG}/csrc/acf_eval_worst.h", f"{PKG}/csrc/acf_neighbors.h"]},
     "neumf": {"lib": f"{PKG}/lib/libacf_neumf.so",

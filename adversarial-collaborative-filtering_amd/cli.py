@@ -79,6 +79,12 @@ def parse_args(argv=None, flavor="ori"):
                         "uids are keys of new users, not rows of the user table) and write their --topk best "
                         "items to <out>/<runName>.foldin.topk (rows in ascending uid order) and the uids to "
                         "<out>/<runName>.foldin.users.  Needs --topk.")
+    p.add_argument("--fold_in_items", type=str, default=None, metavar="FILE",
+                   help="After training, fold in the new items of FILE (rating TSV: uid<TAB>item<TAB>...; its "
+                        "items are keys of new items, not rows of the item table; its uids are rows of the user "
+                        "table) and write the --topk best existing users of each to <out>/<runName>.folditems.topk "
+                        "(rows in ascending item key order, the item's own users excluded) and the keys to "
+                        "<out>/<runName>.folditems.items.  Needs --topk.")
     p.add_argument("--test_multi", type=str, default=None, metavar="FILE",
                    help="After training, evaluate against SEVERAL held-out items per user: the rows of FILE "
                         "(rating TSV: uid<TAB>item<TAB>...) are the users' test lists; writes "
@@ -95,6 +101,8 @@ def parse_args(argv=None, flavor="ori"):
     args = p.parse_args(argv)
     if args.fold_in is not None and args.topk <= 0:
         p.error("--fold_in needs --topk K (K > 0)")
+    if args.fold_in_items is not None and args.topk <= 0:
+        p.error("--fold_in_items needs --topk K (K > 0)")
     if args.similar is not None and args.topk <= 0:
         p.error("--similar needs --topk K (K > 0)")
     return args
@@ -224,6 +232,16 @@ def read_fold_file(file):
     return lists
 
 
+def read_fold_items_file(file):
+    """{item key: [uids]} of the same rating file read by its item column: the
+    users of every new item, in file order, repeats kept."""
+    lists = {}
+    for uid, items in read_fold_file(file).items():
+        for item in items:
+            lists.setdefault(item, []).append(uid)
+    return lists
+
+
 def read_id_file(file):
     """The ids of a file with one integer >= 0 per line (blank lines skipped)."""
     ids = []
@@ -333,6 +351,14 @@ def main(argv=None, flavor="ori"):
         items, _ = recommend_new(final, lists, args.topk, seed=args.seed, batch=min(args.batch_size, 512))
         write_topk(out, runName + ".foldin.topk", items)
         write_fold_users(out, runName + ".foldin.users", sorted(lists))
+    if args.fold_in_items is not None:
+        from .evaluate import audience_new
+        final = amf if args.model == "apr" else m
+        lists = read_fold_items_file(args.fold_in_items)
+        users, _ = audience_new(final, lists, args.topk, seed=args.seed, batch=min(args.batch_size, 512),
+                                dataset=dataset)
+        write_topk(out, runName + ".folditems.topk", users)
+        write_fold_users(out, runName + ".folditems.items", sorted(lists))
     if args.similar is not None:
         from .evaluate import similar_items
         final = amf if args.model == "apr" else m

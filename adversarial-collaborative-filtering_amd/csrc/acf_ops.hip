@@ -282,3 +282,4 @@ extern "C" int acf_sparse_adagrad_apply(float* W, float* acc, int64_t rows, int3
 }
 
 #include "acf_fold.h"
+#include "acf_fold_items.h"

@@ -18,6 +18,7 @@
 //   acf::adv_direction         adv_update's direction over a whole triplet stream (utils.py:145-154)
 //   acf::adv_apply             delta = N * eps and W + delta (APR.py:130-141,190)
 //   acf::fold_in_users         rows for new users against a frozen Q (no reference counterpart)
+//   acf::fold_in_items         rows for new items against frozen P and Q (no reference counterpart)
 //   acf::eval_positions_multi  positions of several held-out items per user, one sweep per user
 //   acf::rank_metrics          hit / recall / precision / ndcg / map @K, mrr, auc of such positions (fp64)
 //   acf::eval_positions_worst  certified worst-case positions under an eps attack on the user or the item rows
@@ -455,6 +456,56 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> fold_in_users(
   return {P_new, acc_new, loss};
 }
 
+// rows, accumulators and per-epoch losses of n new items fitted against frozen P and Q
+// (acf_fold_in_items, users and negatives range-checked by the call); init / acc_init: [n, d] or None
+std::tuple<at::Tensor, at::Tensor, at::Tensor> fold_in_items(
+    const at::Tensor& P, const at::Tensor& Q, const at::Tensor& item_off, const at::Tensor& user_pos_,
+    const at::Tensor& item_neg_, int64_t epochs, int64_t batch, const c10::optional<at::Tensor>& init,
+    const c10::optional<at::Tensor>& acc_init, double lr, double eps, double reg, double reg_adv, bool adver,
+    double clip_lo, double clip_hi) {
+  need_table(P, "embedding_P", P);
+  need_table(Q, "embedding_Q", P);
+  TORCH_CHECK(P.size(1) == Q.size(1), "embedding_P and embedding_Q differ in dim: ", P.size(1), " and ", Q.size(1));
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
+  need(item_off, "item_off", at::kLong, 1);
+  TORCH_CHECK(item_off.device() == Q.device(), "item_off must live on ", Q.device());
+  TORCH_CHECK(item_off.numel() >= 1, "item_off must have n + 1 entries");
+  TORCH_CHECK(epochs >= 0 && epochs < (1ll << 31), "epochs must be >= 0");
+  TORCH_CHECK(batch >= 1 && batch <= ACF_FOLD_MAX_BATCH, "batch must lie in [1, ", ACF_FOLD_MAX_BATCH, "], got ", batch);
+  at::Tensor up = idx32(user_pos_, "user_pos", Q);
+  const int64_t n = item_off.numel() - 1, T = up.numel(), d = Q.size(1);
+  TORCH_CHECK(item_neg_.dim() == 2 && item_neg_.size(0) == epochs && item_neg_.size(1) == T,
+              "item_neg must have shape (epochs, len(user_pos))");
+  at::Tensor in = idx32(item_neg_, "item_neg", Q);
+  const at::Tensor off = item_off.cpu();
+  const int64_t* o = off.data_ptr<int64_t>();
+  TORCH_CHECK(o[0] == 0 && o[n] == T, "item_off must start at 0 and end at len(user_pos)");
+  for (int64_t r = 0; r < n; ++r) TORCH_CHECK(o[r] <= o[r + 1], "item_off must be non-decreasing");
+  const float *ini = nullptr, *aci = nullptr;
+  if (init.has_value()) {
+    need(*init, "init", at::kFloat, 2);
+    TORCH_CHECK(init->device() == Q.device() && init->size(0) == n && init->size(1) == d, "init must be [n, dim] on ",
+                Q.device());
+    ini = init->data_ptr<float>();
+  }
+  if (acc_init.has_value()) {
+    need(*acc_init, "acc_init", at::kFloat, 2);
+    TORCH_CHECK(acc_init->device() == Q.device() && acc_init->size(0) == n && acc_init->size(1) == d,
+                "acc_init must be [n, dim] on ", Q.device());
+    aci = acc_init->data_ptr<float>();
+  }
+  const acf_apr_hparams hp = hparams(lr, eps, reg, reg_adv, adver, clip_lo, clip_hi);
+  at::Tensor Q_new = at::empty({n, d}, Q.options()), acc_new = at::empty({n, d}, Q.options());
+  at::Tensor loss = at::empty({epochs, n}, Q.options());
+  ok(acf_fold_in_items(P.data_ptr<float>(), P.size(0), Q.data_ptr<float>(), Q.size(0), (int32_t)d,
+                       item_off.data_ptr<int64_t>(), n, T ? up.data_ptr<int32_t>() : nullptr,
+                       T && epochs ? in.data_ptr<int32_t>() : nullptr, T, (int32_t)epochs, (int32_t)batch, &hp, ini,
+                       aci, n ? Q_new.data_ptr<float>() : nullptr, n ? acc_new.data_ptr<float>() : nullptr,
+                       n && epochs ? loss.data_ptr<float>() : nullptr, 1, stream_of(Q)),
+     "acf_fold_in_items");
+  return {Q_new, acc_new, loss};
+}
+
 // a CSR's offsets: int64 [n + 1] on `like`'s device, 0 = off[0] <= ... <= off[n] = total (read back once)
 void need_csr(const at::Tensor& off, const char* name, int64_t n, int64_t total, const at::Tensor& like) {
   need(off, name, at::kLong, 1);
@@ -612,6 +663,10 @@ TORCH_LIBRARY(acf, m) {
   m.def("fold_in_users(Tensor Q, Tensor user_off, Tensor item_pos, Tensor item_neg, int epochs, int batch=512, "
         "Tensor? init=None, Tensor? acc_init=None, float lr=0.05, float eps=0.5, float reg=0., float reg_adv=1., "
         "bool adver=True, float clip_lo=-80., float clip_hi=100000000.) -> (Tensor P_new, Tensor acc_new, Tensor loss)");
+  m.def("fold_in_items(Tensor P, Tensor Q, Tensor item_off, Tensor user_pos, Tensor item_neg, int epochs, "
+        "int batch=512, Tensor? init=None, Tensor? acc_init=None, float lr=0.05, float eps=0.5, float reg=0., "
+        "float reg_adv=1., bool adver=True, float clip_lo=-80., float clip_hi=100000000.) -> "
+        "(Tensor Q_new, Tensor acc_new, Tensor loss)");
   m.def("eval_positions_multi(Tensor P, Tensor Q, Tensor users, Tensor test_off, Tensor test_items, "
         "int num_candidates, Tensor excl_off, Tensor excl_items) -> Tensor");
   m.def("rank_metrics(Tensor positions, Tensor test_off, Tensor n_neg, int[] cutoffs) -> "
@@ -633,6 +688,7 @@ TORCH_LIBRARY_IMPL(acf, CUDA, m) {
   m.impl("adv_direction", &adv_direction);
   m.impl("adv_apply", &adv_apply);
   m.impl("fold_in_users", &fold_in_users);
+  m.impl("fold_in_items", &fold_in_items);
   m.impl("eval_positions_multi", &eval_positions_multi);
   m.impl("rank_metrics", &rank_metrics);
   m.impl("eval_positions_worst", &eval_positions_worst);

@@ -442,6 +442,137 @@ def recommend_new(model_or_tables, lists, k: int, **fold_args):
     return items.cpu().numpy(), scores.cpu().numpy()
 
 
+# ---- fold-in: rows for items that were not in the training set ----------------
+class FoldInItems:
+    """What fold_in_items returns: keys (the dict's keys ascending, or 0..n-1 for
+    a list of lists), the CSR (item_off int64 [n + 1], user_pos int32 [T], numpy)
+    of the sorted unique user lists, and the device tensors Q [n, d], acc [n, d]
+    (the fitted rows and their Adagrad accumulators) and loss [epochs, n]."""
+
+    def __init__(self, keys, item_off, user_pos, Q, acc, loss):
+        self.keys, self.item_off, self.user_pos = keys, item_off, user_pos
+        self.Q, self.acc, self.loss = Q, acc, loss
+
+    def __len__(self):
+        return len(self.keys)
+
+
+def fold_item_negatives(item_off, user_pos, num_items: int, epochs: int, seed: int = 0, excl_off=None, excl=None):
+    """item_neg int32 [epochs, T] for ops.fold_in_items: per position and epoch one
+    item uniform on [0, num_items).  With a train CSR of the existing users
+    (excl_off int64 [U + 1] / excl: the items of user u are
+    excl[excl_off[u]:excl_off[u+1]], what train_exclusions(dataset, arange(U))
+    returns) a draw that is a train item of that position's user is redrawn
+    (APR.py:76-77); without it the draws are plain uniform.  Reproducible from
+    `seed` (numpy RandomState).  ValueError: a user outside the CSR (or negative),
+    or a user whose train list holds every item."""
+    off = np.asarray(item_off, dtype=np.int64)
+    users = np.asarray(user_pos, dtype=np.int64).reshape(-1)
+    num_items, epochs, T = int(num_items), int(epochs), len(users)
+    if num_items <= 0:
+        raise ValueError("num_items must be positive")
+    if off.ndim != 1 or off.size < 1 or off[0] != 0 or off[-1] != T or (np.diff(off) < 0).any():
+        raise ValueError("item_off must be a CSR offset array over user_pos")
+    if T and users.min() < 0:
+        raise ValueError("a list holds a user outside the user table (negative)")
+    if (excl_off is None) != (excl is None):
+        raise ValueError("excl_off and excl go together")
+    rng = np.random.RandomState(int(seed) & 0xFFFFFFFF)
+    neg = rng.randint(num_items, size=epochs * T).astype(np.int64)
+    if excl_off is None or T == 0:
+        return neg.astype(np.int32).reshape(epochs, T)
+    eo = np.asarray(excl_off, dtype=np.int64).reshape(-1)
+    ex = np.asarray(excl, dtype=np.int64).reshape(-1)
+    n_users = len(eo) - 1
+    if users.max() >= n_users:
+        raise ValueError(f"a list holds a user outside [0, {n_users}), the users of the train CSR")
+    owner = np.repeat(np.arange(n_users, dtype=np.int64), np.diff(eo))
+    inside = (ex >= 0) & (ex < num_items)  # other entries can never be drawn
+    keys = np.unique(owner[inside] * num_items + ex[inside])
+    full = np.bincount(keys // num_items, minlength=n_users) >= num_items
+    if full[users].any():
+        raise ValueError("a user's train list holds every item: no admissible negative")
+    if len(keys) == 0:
+        return neg.astype(np.int32).reshape(epochs, T)
+    own = np.tile(users, epochs)
+    todo = np.arange(epochs * T)
+    while len(todo):
+        k = own[todo] * num_items + neg[todo]
+        at = np.minimum(np.searchsorted(keys, k), len(keys) - 1)
+        todo = todo[keys[at] == k]
+        neg[todo] = rng.randint(num_items, size=len(todo))
+    return neg.astype(np.int32).reshape(epochs, T)
+
+
+def _fold_items_target(model_or_tables):
+    """(P, Q, num_users, num_items, default hparams) of an MF-like model or a
+    (P, Q) pair; the defaults as _fold_target's."""
+    m = model_or_tables
+    P, Q, n_users, n_items = _neighbor_tables(m)
+    if hasattr(m, "hparams"):
+        hp = m.hparams()
+        hp = ops.StepHParams(lr=hp.lr, eps=hp.eps, reg=hp.reg, reg_adv=hp.reg_adv, adver=hp.adver)
+    else:
+        hp = ops.StepHParams(adver=1)
+    return P, Q, n_users, n_items, hp
+
+
+def fold_in_items(model_or_tables, lists, epochs: int = 20, batch: int = 512, seed: int = 0, hp=None, init=None,
+                  dataset=None) -> FoldInItems:
+    """Fit a row to every NEW item's list of users while both tables stay fixed
+    (ops.fold_in_items): APR's own step with the new item as the positive of
+    every triplet.  model_or_tables: an MF (or anything with embedding_P /
+    embedding_Q / num_users / num_items) or a (P, Q) pair.  lists: a sequence of
+    user lists or a dict key -> users (sorted and de-duplicated by fold_lists);
+    users must lie in [0, num_users).  Negatives: fold_item_negatives(seed) over
+    [0, num_items); with a dataset, a draw among the train items of that
+    position's user is rejected.  hp and init as in fold_in (init: a FoldInItems
+    or (Q [n, d], acc [n, d]) of an earlier fit of the same items)."""
+    P, Q, n_users, n_items, hp0 = _fold_items_target(model_or_tables)
+    hp = hp0 if hp is None else hp
+    keys, off, users = fold_lists(lists)
+    if len(users) and users.max() >= n_users:
+        raise ValueError(f"a list holds a user outside [0, {n_users})")
+    eo = ex = None
+    if dataset is not None:
+        eo, ex = train_exclusions(dataset, np.arange(n_users, dtype=np.int64))
+    neg = fold_item_negatives(off, users, n_items, epochs, seed, eo, ex)
+    Q0 = A0 = None
+    if init is not None:
+        Q0, A0 = (init.Q, init.acc) if isinstance(init, FoldInItems) else init
+    Qn, acc, loss = ops.fold_in_items(P, Q, off, users, neg, hp, int(epochs), int(batch), init=Q0, acc_init=A0)
+    return FoldInItems(keys, off, users, Qn, acc, loss)
+
+
+def audience_new(model_or_tables, lists, k: int, **fold_args):
+    """The k best EXISTING users for every new item ("whom do I show it to?"):
+    fold_in_items(lists, **fold_args), then ops.recommend_topk with the folded
+    rows as queries over the user table, the item's own users excluded.
+    (users int32 [n, k], scores float32 [n, k]) numpy arrays, rows in fold_lists'
+    key order."""
+    import torch
+    P, _, n_users, _, _ = _fold_items_target(model_or_tables)
+    f = fold_in_items(model_or_tables, lists, **fold_args)
+    rows = torch.arange(len(f), dtype=torch.int32, device=P.device)
+    users, scores = ops.recommend_topk(f.Q, P, rows, int(k), n_users, excl_off=f.item_off, excl_items=f.user_pos)
+    return users.cpu().numpy(), scores.cpu().numpy()
+
+
+def extend_items(model_or_tables, fold):
+    """A tables namespace that holds the folded items as well: embedding_P,
+    embedding_Q = the num_items real rows of Q followed by the folded rows
+    (fold: a FoldInItems or a [n, d] tensor), num_users, num_items + n.  New item
+    r has id num_items + r for evaluate.recommend, similar_items and
+    evaluate_multi.  The model itself is not modified."""
+    import types
+
+    import torch
+    P, Q, n_users, n_items, _ = _fold_items_target(model_or_tables)
+    rows = fold.Q if isinstance(fold, FoldInItems) else fold
+    return types.SimpleNamespace(embedding_P=P, embedding_Q=torch.cat([Q[:n_items], rows]).contiguous(),
+                                 num_users=n_users, num_items=n_items + int(rows.shape[0]))
+
+
 # ---- nearest neighbours: similar items, similar users -----------------------
 def _neighbor_tables(model_or_tables):
     """(P, Q, num_users, num_items) of an MF-like model or a (P, Q) pair.  A
@@ -456,19 +587,23 @@ def _neighbor_tables(model_or_tables):
     return m[0], m[1], m[0].shape[0], m[1].shape[0]
 
 
-def similar_items(model_or_tables, items, k: int = 10, metric: str = "cosine", num_candidates=None):
+def similar_items(model_or_tables, items, k: int = 10, metric: str = "cosine", num_candidates=None, rows=None):
     """The k items most like each item of `items` (rows of the item table), on
     the GPU (ops.neighbors_topk): (ids int32 [n, k], scores float32 [n, k]) numpy
     arrays, best first, -1 / -inf past the candidates.  metric: 'cosine', 'dot'
     or 'euclid' (minus the squared distance).  An item is never its own
     neighbour, and the table's padding row (a model's row num_items) is never a
     candidate: the candidates are [0, num_candidates), default the model's
-    num_items (a (P, Q) pair: every row of Q)."""
+    num_items (a (P, Q) pair: every row of Q).  rows: a [m, d] device tensor of
+    other rows, for example a FoldInItems' Q (or the FoldInItems itself); `items`
+    then index `rows`, the candidates are still the model's items, and nothing is
+    self-excluded (row j of `rows` is not item j)."""
     _, Q, _, n_items = _neighbor_tables(model_or_tables)
     n_items = int(n_items if num_candidates is None else num_candidates)
     items = np.asarray(items, dtype=np.int64).reshape(-1)
-    ids, scores = ops.neighbors_topk(Q, items.astype(np.int32), int(k), metric, num_candidates=n_items,
-                                     exclude_self=True)
+    X = rows.Q if isinstance(rows, FoldInItems) else rows
+    ids, scores = ops.neighbors_topk(Q, items.astype(np.int32), int(k), metric, X=X, num_candidates=n_items,
+                                     exclude_self=X is None)
     return ids.cpu().numpy(), scores.cpu().numpy()
 
 

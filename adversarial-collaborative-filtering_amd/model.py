@@ -217,12 +217,25 @@ class MF:
         from .evaluate import recommend_new
         return recommend_new(self, lists, k, **fold_args)
 
-    def similar_items(self, items, k=10, metric="cosine"):
+    def fold_in_items(self, lists, **fold_args):
+        """evaluate.fold_in_items: rows for new items fitted to their user lists
+        against this model's frozen tables (a FoldInItems)."""
+        from .evaluate import fold_in_items
+        return fold_in_items(self, lists, **fold_args)
+
+    def audience_new(self, lists, k, **fold_args):
+        """evaluate.audience_new: the k best existing users of new items, their own
+        users excluded: (users [n, k], scores [n, k]) numpy arrays."""
+        from .evaluate import audience_new
+        return audience_new(self, lists, k, **fold_args)
+
+    def similar_items(self, items, k=10, metric="cosine", rows=None):
         """evaluate.similar_items: the k items nearest to each of `items` in the
         item table ('cosine', 'dot' or 'euclid'): (ids [n, k], scores [n, k])
-        numpy arrays; never the item itself, never the padding row."""
+        numpy arrays; never the item itself, never the padding row.  With rows (a
+        FoldInItems or a [m, d] tensor) the queries are those rows instead."""
         from .evaluate import similar_items
-        return similar_items(self, items, k=k, metric=metric)
+        return similar_items(self, items, k=k, metric=metric, rows=rows)
 
     def similar_users(self, users, k=10, metric="cosine", rows=None):
         """evaluate.similar_users: the k users nearest to each of `users`; with

@@ -1300,6 +1300,76 @@ def fold_in_users(Q, user_off, item_pos, item_neg, hp: StepHParams, epochs: int,
     return P_new, acc_new, loss
 
 
+def fold_in_items(P, Q, item_off, user_pos, item_neg, hp: StepHParams, epochs: int, batch: int = FOLD_MAX_BATCH,
+                  init=None, acc_init=None, check: bool = True):
+    """Rows for n NEW items fitted against the frozen tables P and Q, on the GPU
+    (acf_fold_in_items): (Q_new [n, d], acc_new [n, d], loss [epochs, n]).
+    New item r owns user_pos[item_off[r]:item_off[r+1]] (CSR; item_off int64
+    [n + 1], user_pos int32 [T]: the users who interacted with it); item_neg
+    [epochs, T] holds one negative item (a row of Q) per position per epoch.  For
+    every epoch, every consecutive slice of at most `batch` positions of an item's
+    list is one training_batch iteration (APR.py:143-195) on P and [Q ; q_r] with
+    the new item as the positive of every triplet: with hp.adver the step's own
+    gradient delta (of q_r, of every user row and of every negative row of the
+    slice), reg as in the step; only q_r and its Adagrad accumulator are kept, P
+    and Q are never written.  init / acc_init [n, d] (default zeros / 0.1): pass a
+    previous (Q_new, acc_new) to continue a fit.  loss[e, r]: the item's clean
+    loss of epoch e, each slice before its update.  An item's outputs depend on
+    that item's inputs only, bit for bit, and equal inputs give equal bits.  Bad
+    arguments raise ValueError before any native call; with check, a user outside
+    P or a negative outside Q raises NativeIndexError."""
+    if not isinstance(hp, StepHParams):
+        raise ValueError(f"hp must be a StepHParams, got {type(hp).__name__}")
+    if hp.adv != "grad" or hp.zero_delta:
+        raise ValueError("fold-in takes only the gradient delta: adv='grad' and zero_delta=0 "
+                         f"(got adv={hp.adv!r}, zero_delta={hp.zero_delta})")
+    if isinstance(batch, bool) or not isinstance(batch, int) or not 1 <= batch <= FOLD_MAX_BATCH:
+        raise ValueError(f"batch must be an int in [1, {FOLD_MAX_BATCH}], got {batch!r}")
+    if isinstance(epochs, bool) or not isinstance(epochs, int) or epochs < 0:
+        raise ValueError(f"epochs must be an int >= 0, got {epochs!r}")
+    T = len(user_pos)
+    try:
+        off = _fold_csr(item_off, T)
+    except ValueError as e:  # the helper speaks of the user call's arguments
+        raise ValueError(str(e).replace("user_off", "item_off").replace("item_pos", "user_pos")) from None
+    n = off.size - 1
+    if tuple(getattr(item_neg, "shape", ())) != (epochs, T):
+        raise ValueError(f"item_neg must have shape (epochs, len(user_pos)) = {(epochs, T)}, "
+                         f"got {tuple(getattr(item_neg, 'shape', ()))}")
+    _fold_table(P, "embedding_P", None)
+    dev = P.device
+    _fold_table(Q, "embedding_Q", dev)
+    U1, d = P.shape
+    I1 = Q.shape[0]
+    if Q.shape[1] != d:
+        raise ValueError(f"embedding_P and embedding_Q differ in dim: {d} and {Q.shape[1]}")
+    if d < 4 or d > 1024 or d % 4:
+        raise ValueError(f"dim must be a multiple of 4 in [4, 1024], got {d}")
+    up = _fold_items(user_pos, "user_pos", dev, (T,))
+    ineg = _fold_items(item_neg, "item_neg", dev, (epochs, T))
+    if init is not None:
+        _fold_table(init, "init", dev, (n, d))
+    if acc_init is not None:
+        _fold_table(acc_init, "acc_init", dev, (n, d))
+    offd = (item_off if isinstance(item_off, torch.Tensor) and item_off.dtype == torch.int64
+            and item_off.device == dev and item_off.is_contiguous()
+            else torch.as_tensor(off).to(dev))
+    settle_tables()
+    Q_new = torch.empty((n, d), dtype=torch.float32, device=dev)
+    acc_new = torch.empty((n, d), dtype=torch.float32, device=dev)
+    loss = torch.empty((epochs, n), dtype=torch.float32, device=dev)
+    if n == 0:
+        return Q_new, acc_new, loss
+    c = hp.to_c()
+    with _on(dev):
+        call("acf_fold_in_items", P.data_ptr(), U1, Q.data_ptr(), I1, d, offd.data_ptr(), n,
+             up.data_ptr() if T else None, ineg.data_ptr() if T and epochs else None, T, epochs, batch,
+             ctypes.byref(c), init.data_ptr() if init is not None else None,
+             acc_init.data_ptr() if acc_init is not None else None, Q_new.data_ptr(), acc_new.data_ptr(),
+             loss.data_ptr() if epochs else None, int(bool(check)), _stream_ptr(dev))
+    return Q_new, acc_new, loss
+
+
 def eval_positions_list(P, Q, users, test_items, cand_off, cand_items):
     """_eval_by_user positions over explicit candidate lists ("sample" mode)."""
     settle_tables()

@@ -262,6 +262,27 @@ class APR(Recommender):
         fold_args.setdefault("num_items", self.iNum)
         return self.model.recommend_new(self._new_lists(train), k, **fold_args)
 
+    @staticmethod
+    def _new_item_lists(train):
+        """User lists of new items: a dok/CSC matrix (column c = new item c, rows
+        = the existing users), or lists / a dict as evaluate.fold_lists takes them."""
+        if hasattr(train, "tocsc"):
+            csc = train.tocsc()
+            return [csc.indices[csc.indptr[c]:csc.indptr[c + 1]] for c in range(csc.shape[1])]
+        return train
+
+    def fold_in_items(self, train, **fold_args):
+        """evaluate.fold_in_items for the new items of `train` (a matrix with one
+        COLUMN per new item and the existing users as rows, or user lists)."""
+        self._ensure()
+        return self.model.fold_in_items(self._new_item_lists(train), **fold_args)
+
+    def audience_new(self, train, k, **fold_args):
+        """evaluate.audience_new for the new items of `train`: (users [n, k],
+        scores [n, k]) numpy arrays among [0, uNum), their own users excluded."""
+        self._ensure()
+        return self.model.audience_new(self._new_item_lists(train), k, **fold_args)
+
     def evaluate_multi(self, plan, cutoffs=(10, 50, 100), raw=False):
         """evaluate.evaluate_multi against the test lists of `plan`
         (evaluate.init_eval_multi): a dict of recall / ndcg / map / ... @K, mrr, auc."""

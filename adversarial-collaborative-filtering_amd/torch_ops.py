@@ -25,6 +25,10 @@ SURVEY.md §8(b) proposes:
   of the items (``check=1``: a small stream-ordered allocation, one kernel and a stream
   synchronise before the fold-in launch).  Use ``ops.fold_in_users(..., check=False)`` with a
   host ``user_off`` for a call that stays asynchronous;
+- ``fold_in_items(P, Q, item_off, user_pos, item_neg, epochs, batch, init, acc_init, lr, eps, reg,
+  reg_adv, adver, clip_lo, clip_hi) -> (Q_new, acc_new, loss)``: rows for new items against frozen
+  user and item tables (``ops.fold_in_items``, the same bits); it synchronises with the host as
+  ``fold_in_users`` does (CSR read back, native range check of users and negatives);
 - ``eval_positions_multi(P, Q, users, test_off, test_items, num_candidates, excl_off, excl_items)
   -> positions`` and ``rank_metrics(positions, test_off, n_neg, cutoffs) -> (per_user,
   per_user_free, mean_cut, mean_free, n_scored)``: evaluation against several held-out items
@@ -53,7 +57,7 @@ from . import build_native
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libacf_torch.so")
 OPS = ("bpr_apr_step", "apr_train", "gather_bpr_fwd_bwd", "row_segment_sum", "l2norm_perturb",
        "sparse_adagrad_apply", "score_rank", "score_rank_all", "recommend_topk", "adv_direction", "adv_apply",
-       "fold_in_users", "eval_positions_multi", "rank_metrics", "eval_positions_worst", "release_contexts")
+       "fold_in_users", "fold_in_items", "eval_positions_multi", "rank_metrics", "eval_positions_worst", "release_contexts")
 _lock = threading.Lock()
 _loaded = False
 

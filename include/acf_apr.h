@@ -609,6 +609,43 @@ int acf_fold_in_users(const float* Q, int64_t num_item_rows, int32_t dim, const 
                       const float* acc_init, float* P_new, float* acc_new, float* loss, int32_t check,
                       void* stream);
 
+/* ---- fold-in: new items against frozen user and item tables -------------------
+ * (no reference counterpart.)  New item r of the CSR item_off int64 [n + 1] /
+ * user_pos [T] gets a row fitted to the users who interacted with it while P and
+ * Q stay fixed.  For epoch e = 0..epochs-1 and every consecutive slice of at most
+ * `batch` positions of [item_off[r], item_off[r+1]) (the last one may be short;
+ * the same order every epoch) the item takes ONE training_batch iteration
+ * (APR.py:143-195) on the tables P and [Q ; q_r] -- q_r appended as row
+ * num_item_rows -- with the batch {(user_pos[k], num_item_rows, item_neg[e*T + k])};
+ * only q_r and its Adagrad accumulator are kept.  A negative lies in
+ * [0, num_item_rows), so it can never equal the new item.  With hp->adver the
+ * delta is the step's own: delta_q from the slice's summed clean gradient of q_r;
+ * per user row of the slice from its clean gradient summed over all the row's
+ * occurrences in the slice (pos branch g * q_r, then neg branch -g * q_j, triplet
+ * order); per negative row likewise (-g * p_u, triplet order); all l2-normalised
+ * with the 1e-12 floor.  reg acts on q_r as in the step on the extended tables
+ * (2*reg/(B_slice*dim) per occurrence, twice when adversarial).
+ * hp->adv_mode != 0 or hp->zero_delta != 0 is ACF_E_INVALID.
+ *   init, acc_init [n, dim]: starting rows / accumulators (NULL: zeros / 0.1);
+ *   Q_new, acc_new [n, dim]: the fitted rows and accumulators (pass them back as
+ *     init / acc_init to continue when a list grows);
+ *   loss [epochs, n] (may be NULL): the clean loss summed over the item's slices
+ *     of that epoch, each slice before its own update.
+ * An item with an empty list keeps its inits and has loss 0; epochs = 0 copies the
+ * inits.  An item's outputs depend on that item's inputs only and are the same
+ * bits in every call (no float atomics, fixed summation orders).  P and Q are
+ * never written; no workspace.  1 <= batch <= ACF_FOLD_MAX_BATCH.
+ * num_user_rows <= 2^31, num_item_rows < 2^31.  item_off must be non-decreasing
+ * within [0, T] (offsets outside are clamped).
+ * check != 0: the call first synchronises and returns ACF_E_RANGE when a user is
+ * outside [0, num_user_rows) or a negative outside [0, num_item_rows), before
+ * anything is written (check == 0: such an index is read as row 0). */
+int acf_fold_in_items(const float* P, int64_t num_user_rows, const float* Q, int64_t num_item_rows, int32_t dim,
+                      const int64_t* item_off, int64_t n_items, const int32_t* user_pos, const int32_t* item_neg,
+                      int64_t T, int32_t epochs, int32_t batch, const acf_apr_hparams* hp,
+                      const float* init, const float* acc_init, float* Q_new, float* acc_new, float* loss,
+                      int32_t check, void* stream);
+
 /* ---- sampler: shuffle/_get_train_batch (APR.py:39-81) --------------------
  * Shuffles the n_pos positive pairs with a counter-based permutation of
  * `seed`, keeps floor(n_pos / batch_size) * batch_size of them (drop-last,
