@@ -2323,7 +2323,9 @@ extern "C" int acf_neumf_train(acf_neumf_ctx* c, float* P, float* G, float* m, f
   hipStream_t s = static_cast<hipStream_t>(stream_);
   int r = settle_unchecked(c, s);
   if (r != ACF_OK) return r;
-  const bool fr = n > 0 && std::min<int64_t>(batch, n) <= FR_MAXB && c->rows_in_line;
+  // any batch of the call in line: the full batches, or a shorter last one
+  const int64_t tail = n % batch;
+  const bool fr = n > 0 && c->rows_in_line && (batch <= FR_MAXB || (tail != 0 && tail <= FR_MAXB));
   float* bufs[4] = {P, G, m, v};
   const bool snap = fr && c->failsafe;
   if (snap && (r = take_snapshot(c, s, bufs, 4)) != ACF_OK) return r;
@@ -2331,9 +2333,9 @@ extern "C" int acf_neumf_train(acf_neumf_ctx* c, float* P, float* G, float* m, f
   if (r != ACF_OK) return r;
   int32_t herr = 0;
   if ((r = fetch_err(c, s, &herr)) != ACF_OK) return r;
-  if ((herr & 512) && fr) {
+  if (herr & 512) {  // whatever gave up, no stale arrival counter outlives the call
     if ((r = reset_row_counters(c, s)) != ACF_OK) return r;
-    if (!snap) return check_err(herr);
+    if (!snap) return check_err(herr);  // (snap implies fr)
     if ((r = restore_snapshot(c, s, bufs, 4)) != ACF_OK) return r;
     c->rows_in_line = 0;
     r = train_launches(c, P, G, m, v, u, i, y, n, batch, t_first, hp, losses, s);

@@ -1,15 +1,20 @@
 """NeuMF / adversarial NeuMF HIP path (libacf_neumf.so) vs the CPU oracle
 (oracle/neumf_oracle.py, itself checked against torch autograd in
 test_neumf_oracle.py).  Tolerance: fp32, rtol 1e-4 / atol 1e-6 on gradients —
-the MLP sums run in a different order than numpy's BLAS.  Parity with the
+the MLP sums run in a different order than numpy's BLAS; the two gradient tests
+also hold every tensor to float64 autograd with neumf_ref.check_grads, whose bar
+scales with the tensor (the embedding gradients are mostly below that atol).
+Batches over 1,024 and the other dims: test_gpu_neumf_batches.py.  Parity with the
 reference's own adversarial NeuMF is unpinned (it does not run, NeuMF.py:131)."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 import torch
 
 import neumf_oracle as N
+import neumf_ref as R
 
 pytestmark = pytest.mark.gpu
 
@@ -30,6 +35,35 @@ def _problem(seed, U1=41, I1=37, d=16, B=96):
     i[10:20] = 3
     y = (rng.random(B) < 0.5).astype(np.float32)
     return P, u, i, y
+
+
+def _yelp_problem(adver):
+    U1, I1, d, B = 25_678, 25_816, 64, 512
+    P = N.init_params(U1, I1, d, 17)
+    rng = np.random.default_rng(4 + adver)
+    u = rng.integers(0, U1, B).astype(np.int32)
+    i = ((rng.zipf(1.2, B) - 1) % I1).astype(np.int32)
+    y = (rng.random(B) < 0.5).astype(np.float32)
+    return P, u, i, y
+
+
+@functools.lru_cache(maxsize=None)
+def _ref64(shape, d, adver):
+    """(float64 gradient, the fp32 oracle's distance from it) of a gradient test's
+    problem: shape "small" is test_grad_matches_oracle's, "yelp" the yelp-shaped one."""
+    P, u, i, y = _problem(d + adver, d=d) if shape == "small" else _yelp_problem(adver)
+    hp = N.NeuMFHParams(adver=adver, eps=0.5, reg_adv=0.7 if shape == "small" else 1.0)
+    want64, _, _ = R.torch_grads_losses(P, u.astype(np.int64), i.astype(np.int64), y, hp)
+    return want64, R.oracle_distance(N.grad_step(P, u, i, y, hp)[0], want64)
+
+
+@functools.lru_cache(maxsize=None)
+def _k64():
+    """neumf_ref.check_grads' k for the two gradient tests here: 4x the oracle's
+    largest distance from float64 over their ten cases (measured: 1.31e-5; the
+    oracle's worst is 3.3e-6 of |bo|, yelp shape, adver 0)."""
+    cases = [("small", d, a) for d in (8, 16, 64, 128) for a in (0, 1)] + [("yelp", 64, a) for a in (0, 1)]
+    return R.calibrate([_ref64(*c)[1] for c in cases])
 
 
 def _state(nm, P, dev):
@@ -57,6 +91,8 @@ def test_grad_matches_oracle(nm, dev, d, adver):
         np.testing.assert_allclose(st.view(n, st.grad).cpu().numpy(), want[n], rtol=1e-4, atol=1e-6,
                                    err_msg=n)
     np.testing.assert_allclose(loss.cpu().numpy(), [lc, la], rtol=1e-5)
+    # the atol above is most of an embedding gradient (they carry 1/B): float64, a bar per tensor
+    R.check_grads({n: st.view(n, st.grad).cpu().numpy() for n in N.NAMES}, _ref64("small", d, adver)[0], _k64())
 
 
 def test_predict_matches_oracle(nm, dev):
@@ -212,12 +248,8 @@ def test_yelp_shaped_grad_matches_oracle(nm, dev, adver):
     """The bench's configs[3] shape (yelp-sort-shaped: 25,677 x 25,815 rows, d = 64,
     batch 512) with Zipf-popular items (rows with many occurrences per batch):
     one gradient of the adversarial step vs the oracle, rtol 1e-4 as above."""
-    U1, I1, d, B = 25_678, 25_816, 64, 512
-    P = N.init_params(U1, I1, d, 17)
-    rng = np.random.default_rng(4 + adver)
-    u = rng.integers(0, U1, B).astype(np.int32)
-    i = ((rng.zipf(1.2, B) - 1) % I1).astype(np.int32)
-    y = (rng.random(B) < 0.5).astype(np.float32)
+    B = 512
+    P, u, i, y = _yelp_problem(adver)
     hp_o = N.NeuMFHParams(adver=adver, eps=0.5, reg_adv=1.0)
     want, lc, la = N.grad_step(P, u, i, y, hp_o)
     st = _state(nm, P, dev)
@@ -232,6 +264,8 @@ def test_yelp_shaped_grad_matches_oracle(nm, dev, adver):
         np.testing.assert_allclose(st.view(n, st.grad).cpu().numpy(), want[n], rtol=1e-4, atol=1e-6,
                                    err_msg=n)
     np.testing.assert_allclose(loss.cpu().numpy(), [lc, la], rtol=1e-5)
+    # float64, a bar per tensor (most rows here are untouched: their gradient is exactly zero)
+    R.check_grads({n: st.view(n, st.grad).cpu().numpy() for n in N.NAMES}, _ref64("yelp", 64, adver)[0], _k64())
 
 
 @pytest.mark.parametrize("B,U1,I1,n,d", [

@@ -8,6 +8,8 @@ import pytest
 import torch
 
 import neumf_oracle as N
+import neumf_ref as R
+from neumf_ref import _torch_grads
 
 U1, I1, D, B = 23, 19, 8, 40
 
@@ -21,36 +23,6 @@ def _problem(seed):
     i[3:9] = 7
     y = (rng.random(B) < 0.5).astype(np.float32)
     return P, u, i, y
-
-
-def _torch_grads(P, u, i, y, hp):
-    T = {n: torch.tensor(P[n], dtype=torch.float64, requires_grad=True) for n in N.NAMES}
-    ut, it = torch.tensor(u), torch.tensor(i)
-    yt = torch.tensor(y, dtype=torch.float64)
-
-    def loss_fn(delta=None):
-        mu, mi, lu, li = T["MF_U"][ut], T["MF_I"][it], T["MLP_U"][ut], T["MLP_I"][it]
-        if delta is not None:
-            mu, mi, lu, li = mu + delta["MF_U"], mi + delta["MF_I"], lu + delta["MLP_U"], li + delta["MLP_I"]
-        a1 = torch.relu(torch.cat([lu, li], 1) @ T["W1"] + T["b1"])
-        a2 = torch.relu(a1 @ T["W2"] + T["b2"])
-        p = torch.sigmoid(torch.cat([mu * mi, a2], 1) @ T["Wo"] + T["bo"])[:, 0]
-        pc = torch.clamp(p, 1e-7, 1 - 1e-7)
-        return -(yt * torch.log(pc) + (1 - yt) * torch.log(1 - pc)).mean()
-
-    lc = loss_fn()
-    total = lc
-    if hp.adver:
-        tabs = ("MF_U", "MF_I", "MLP_U", "MLP_I")
-        G = torch.autograd.grad(lc, [T[n] for n in tabs], retain_graph=True)
-        delta = {}
-        for n, g in zip(tabs, G):
-            idx = ut if n.endswith("_U") else it
-            r = g[idx]
-            delta[n] = (hp.eps * r / torch.sqrt(torch.clamp((r * r).sum(1, keepdim=True), min=1e-12))).detach()
-        total = lc + hp.reg_adv * loss_fn(delta)
-    grads = torch.autograd.grad(total, [T[n] for n in N.NAMES])
-    return {n: g.numpy() for n, g in zip(N.NAMES, grads)}, float(lc)
 
 
 @pytest.mark.parametrize("adver", [0, 1])
@@ -89,3 +61,43 @@ def test_adam_matches_keras_formula():
     before = P["W1"].copy()
     N.adam(P, g0, m, v, 2, hp)
     assert np.all(P["W1"] < before)  # momentum keeps moving it
+
+
+@pytest.mark.parametrize("adver", [0, 1])
+@pytest.mark.parametrize("case", R.GRAD_CASES + R.LIMIT_CASES[:1] + R.DIM_CASES, ids=R.case_id)
+def test_batches_bar_is_met_by_the_oracle_alone(case, adver):
+    """The bar test_gpu_neumf_batches.py holds the GPU to (neumf_ref.check_grads with
+    the calibrated k) checked without a GPU, per case: the fp32 oracle is within a
+    quarter of it; it has teeth (no tensor would pass as all zero, and no touched
+    row of MF_U or MF_I would pass as a zero row, which is what a kernel that
+    lost a row's owner leaves; the MLP rows travel with them); every row
+    of the small tables is in the batch, and the planted rows are where
+    neumf_ref.plants says."""
+    B, d, U1, I1 = case
+    ref = R.reference(case, adver)
+    k = R.batches_k()
+    assert k <= R.K_MAX
+    worst = max(ref["dist"], key=ref["dist"].get)
+    print(f"{R.case_id(case)} adver={adver}: oracle worst {ref['dist'][worst]:.2e} ({worst}); k = {k:.3e}")
+    assert 4 * ref["dist"][worst] <= k
+    want, u, i = ref["want"], ref["u"], ref["i"]
+    for n in N.NAMES:
+        quarter = R.bar(want[n], k) / 4
+        err = np.abs(ref["oracle"][n].astype(np.float64) - want[n])
+        assert (err <= quarter).all(), f"{n}: the oracle is {float((err / quarter).max()):.2f} quarter-bars off"
+    zeros = {n: np.zeros_like(want[n]) for n in N.NAMES}
+    for n in N.NAMES:
+        with pytest.raises(AssertionError, match=n + ":"):
+            R.check_grads({**zeros, **{m: want[m] for m in N.NAMES if m != n}}, want, k)
+    for n in ("MF_U", "MF_I"):  # (an MLP row can have next to no gradient: dead relus)
+        touched = np.unique(u if n.endswith("_U") else i)
+        row_top = np.abs(want[n][touched]).max(1)
+        floor = k * np.abs(want[n]).max() / (1 - R.RTOL)  # |w| <= rtol |w| + k max: passes as zero
+        assert (row_top > floor).all(), f"{n}: {int((row_top <= floor).sum())} touched rows would pass as zero rows"
+    if U1 <= B and I1 <= B:
+        assert len(np.unique(u)) == U1 and len(np.unique(i)) == I1
+    if B >= 2064:
+        assert list(np.nonzero(u == 7)[0][[0, -1]]) == [0, B - 1] and u[2047] == u[2048] == 7
+        assert np.nonzero(u == 9)[0][0] == 2049 and list(np.nonzero(u == 11)[0]) == [B - 2]
+        assert np.nonzero(i == 9)[0][0] == 2048 and list(np.nonzero(i == 11)[0]) == [B - 1]
+    np.testing.assert_allclose(ref["oracle_losses"], [ref["lc"], ref["la"]], rtol=2e-6)
