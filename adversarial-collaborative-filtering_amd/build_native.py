@@ -29,9 +29,10 @@ PKG = os.path.basename(PKG_DIR)
 # per library: sources (compiled), headers (included; hashed), relative to REPO
 LIBS = {
     "apr": {"lib": f"{PKG}/lib/libacf_apr.so",
-            "srcs": [f"{PKG}/csrc/acf_apr.hip", f"{PKG}/csrc/acf_rank.hip", f"{PKG}/csrc/acf_ops.hip"],
+            "srcs": [f"{PKG}/csrc/acf_apr.hip", f"{PKG}/csrc/acf_plan.hip", f"{PKG}/csrc/acf_rank.hip",
+                     f"{PKG}/csrc/acf_ops.hip"],
             "headers": ["include/acf_apr.h", f"{PKG}/csrc/acf_host.h", f"{PKG}/csrc/acf_rows.h",
-                        f"{PKG}/csrc/acf_hplan.h",
+                        f"{PKG}/csrc/acf_plan.h", f"{PKG}/csrc/acf_hplan.h",
                         f"{PKG}/csrc/acf_eval.h", f"{PKG}/csrc/acf_topk.h", f"{PKG}/csrc/acf_adv.h",
                         f"{PKG}/csrc/acf_fold.h", f"{PKG}/csrc/acf_fold_items.h", f"{PKG}/csrc/acf_topk_select.h",
                         f"{PKG}/csrc/acf_eval_multi.h", f"{PKG}/csrc/acf_sweep.h",

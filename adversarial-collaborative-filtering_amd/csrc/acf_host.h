@@ -1,5 +1,5 @@
 // acf_host.h — host plumbing of the entry points of both libraries: libacf_apr.so (acf_apr.hip, training
-// engine; acf_rank.hip, ranking family) and libacf_neumf.so (acf_neumf.hip, acf_keras_mf.hip): error macros,
+// step; acf_plan.hip, its plan; acf_rank.hip, ranking family) and libacf_neumf.so (acf_neumf.hip, acf_keras_mf.hip): error macros,
 // launch grid, row geometry, dim check, the kernels' range bits.  After hip_runtime.h, acf_apr.h.
 #pragma once
 

@@ -1,5 +1,5 @@
-// Hash plan kernels (r04) of libacf_apr.so: included by acf_apr.hip after the
-// plan records (OccRec, HotLists, hot_pieces) they fill; one translation unit.
+// Hash plan kernels (r04) of libacf_apr.so: included by acf_plan.hip after the
+// plan records (acf_plan.h: OccRec, HotLists, hot_pieces) they fill; one translation unit.
 #pragma once
 
 // ---------------------------------------------------------------------------

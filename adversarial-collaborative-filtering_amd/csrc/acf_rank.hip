@@ -3,7 +3,7 @@
 // training context (acf_apr.hip).  Every entry point follows one frame: argument checks,
 // workspace size and alignment, zero the error word, launch, sum the strips, read the error
 // word back when `check` is set; its repeated pieces are the first section's functions.
-// Build: one hipcc line with acf_apr.hip and acf_ops.hip, same flags.
+// Build: one hipcc line with acf_apr.hip, acf_plan.hip and acf_ops.hip, same flags.
 
 #include <hip/hip_runtime.h>
 #include <rocprim/block/block_radix_sort.hpp>

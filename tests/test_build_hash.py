@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import importlib
 import os
+import re
 import shutil
 
 import pytest
@@ -45,6 +46,28 @@ def test_hash_covers_sources_headers_and_flags(tmp_path):
         assert bn.source_hash("apr") != h0
     finally:
         bn.HIPCC_FLAGS[:] = flags
+
+
+@pytest.mark.parametrize("name", ["apr", "neumf", "torch"])
+def test_hash_covers_every_included_file(name):
+    """Every file a unit of the library pulls in with #include "..." (through other
+    headers too) is one of the library's hashed files: an edit to a header that LIBS
+    does not list would leave a stale library accepted."""
+    spec = bn.LIBS[name]
+    dirs = ["include", os.path.join(PKG, "csrc")]  # where the build finds a quoted include
+    listed = set(spec["srcs"]) | set(spec["headers"])
+    seen, todo = set(), list(spec["srcs"])
+    while todo:
+        rel = todo.pop()
+        if rel in seen:
+            continue
+        seen.add(rel)
+        with open(os.path.join(bn.REPO, rel)) as f:
+            for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M):
+                found = [os.path.join(d, inc) for d in dirs if os.path.isfile(os.path.join(bn.REPO, d, inc))]
+                assert found, f'{rel} includes "{inc}", which is in neither of {dirs}'
+                todo.append(found[0])
+    assert seen - listed == set(), f"LIBS[{name!r}] does not hash {sorted(seen - listed)}"
 
 
 def test_load_refuses_library_after_header_edit(tmp_path):

@@ -11,7 +11,7 @@ for f in $(git ls-tree --name-only $rev adversarial-collaborative-filtering_amd/
   case $f in *.hip|*.h) git show $rev:$f > $tmp/csrc/$(basename $f);; esac
 done
 srcs=
-for s in acf_apr acf_rank acf_ops; do  # the library's sources that exist at $rev (acf_rank.hip: not before the split)
+for s in acf_apr acf_plan acf_rank acf_ops; do  # the library's sources that exist at $rev (not before their splits)
   [ -f $tmp/csrc/$s.hip ] && srcs="$srcs $tmp/csrc/$s.hip"
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -I $tmp/include \
