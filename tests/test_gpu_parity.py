@@ -3,6 +3,10 @@
 Tolerance: fp32, rtol 1e-5 / atol 1e-6 on tables of magnitude O(0.1-1) — the
 bar north_star sets ("within 1e-5 fp32").  Differences come only from the order
 of the per-row dot-product sums (wavefront butterfly vs sequential).
+
+The step tests here run d/4 a power of two; test_gpu_step_geometry.py runs them
+at every dispatched row geometry (padded row-groups, three and four chunks per
+lane).
 """
 import importlib
 
