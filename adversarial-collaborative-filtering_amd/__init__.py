@@ -16,7 +16,7 @@ import sys as _sys
 from . import _native  # noqa: F401
 from .data import (DeviceDataset, OriginalDataset, SyntheticDataset, get_dataset, ml1m_like, pinterest_like,
                    synthetic_dataset, synthetic_large, yelp_like)
-from .evaluate import certified, evaluate, init_eval_model, robustness
+from .evaluate import certified, certified_radius, evaluate, init_eval_model, robustness
 from .evaluation import evaluate_apr_mode, evaluate_model
 from .model import MF, Session
 from .neumf import AdversarialNeuMF, NeuMF
@@ -33,4 +33,5 @@ __all__ = [
     "SyntheticDataset", "evaluate", "evaluate_apr_mode", "evaluate_model", "get_dataset", "init_eval_model", "ml1m_like", "output_evaluate",
     "pinterest_like", "prediction2file", "sampling", "shuffle", "synthetic_dataset", "synthetic_large", "training",
     "training_batch", "training_loss_acc", "write2file", "yelp_like", "adv_update", "robustness", "certified",
+    "certified_radius",
 ]

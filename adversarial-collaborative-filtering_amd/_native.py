@@ -90,6 +90,9 @@ SIGNATURES = {
     "acf_eval_positions_worst_workspace": (ctypes.c_int, [_I32, _I32, _I32, ctypes.POINTER(ctypes.c_size_t)]),
     "acf_eval_positions_worst": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _I32, _I32, _P, _P, _P, _I32, _I32,
                                                 _P, _P, ctypes.c_size_t, _I32, _P]),
+    "acf_eval_radius_workspace": (ctypes.c_int, [_I32, _I32, _I32, ctypes.POINTER(ctypes.c_size_t)]),
+    "acf_eval_radius": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P,
+                                       ctypes.c_size_t, _I32, _P]),
     "acf_adv_direction_workspace": (ctypes.c_int, [_I64, _I64, _I64, _I32, ctypes.POINTER(ctypes.c_size_t)]),
     "acf_adv_direction": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _P, _I64, _F, _F, _I32, _U64,
                                          ctypes.c_uint32, _I32, _P, _P, _P, ctypes.c_size_t, _I32, _P]),

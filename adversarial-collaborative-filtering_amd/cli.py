@@ -72,8 +72,13 @@ def parse_args(argv=None, flavor="ori"):
                         "lower bounds of HR@K, NDCG@K and AUC (all-items evaluation) under EVERY perturbation of "
                         "at most eps per embedding row in L2; writes <out>/<runName>.certified (empty: off).")
     p.add_argument("--certify_side", choices=["user", "item", "both"], default="user",
-                   help="Which rows --certify_eps lets the attacker move: the user rows, the item rows, or both "
-                        "as two separate passes (not a joint attack).")
+                   help="Which rows --certify_eps and --certify_radius let the attacker move: the user rows, the "
+                        "item rows, or both as two separate passes (not a joint attack).")
+    p.add_argument("--certify_radius", type=parse_radius_cutoffs, default=[],
+                   help="After training, write the distribution over users of the certified radius at these K "
+                        "(comma separated, e.g. \"1,10,50\"; 1 to 8 integers in [1, 128]): the largest eps up to "
+                        "which the held-out item provably stays in the top K (all-items evaluation, one sweep at "
+                        "K = the largest), to <out>/<runName>.radius (empty: off).  Uses --certify_side.")
     p.add_argument("--fold_in", type=str, default=None, metavar="FILE",
                    help="After training, fold in the new users of FILE (rating TSV: uid<TAB>item<TAB>...; its "
                         "uids are keys of new users, not rows of the user table) and write their --topk best "
@@ -167,6 +172,15 @@ def read_multi(file):
     return out
 
 
+def parse_radius_cutoffs(text):
+    """"1,10,50" -> [1, 10, 50]: 1 to 8 integers in [1, 128] (ops.TOPK_MAX_K)."""
+    out = parse_cutoffs(text)
+    for v in out:
+        if v > 128:
+            raise argparse.ArgumentTypeError(f"a radius cutoff must lie in [1, 128], got {v}")
+    return out
+
+
 def write_robust(path, name, rows):
     """One line "mode<TAB>eps<TAB>hr<TAB>ndcg<TAB>auc" per row of evaluate.robustness
     (floats by repr: the reader gets the same values back)."""
@@ -206,6 +220,30 @@ def read_certified(file):
             if len(parts) != 6:
                 raise ValueError(f"{file}: line {n} has {len(parts)} fields, expected 6")
             rows.append((parts[0], float(parts[1]), int(parts[2]), *[float(x) for x in parts[3:]]))
+    return rows
+
+
+def write_radius(path, name, rows):
+    """One line "side<TAB>K<TAB>missed<TAB>unbounded<TAB>q10<TAB>q25<TAB>q50<TAB>q75<TAB>q90" per
+    (side, *row of evaluate.radius_summary) (floats by repr: the reader gets the same
+    values back; a quantile of no finite radius is nan)."""
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, name), "w") as f:
+        for side, K, missed, unbounded, *qs in rows:
+            if len(qs) != 5:
+                raise ValueError(f"a radius row has 5 quantiles, got {len(qs)}")
+            f.write("%s\t%d\t%s\n" % (side, int(K), "\t".join(repr(float(v)) for v in (missed, unbounded, *qs))))
+
+
+def read_radius(file):
+    """The rows [(side, K, missed, unbounded, q10, q25, q50, q75, q90)] write_radius wrote."""
+    rows = []
+    with open(file) as f:
+        for n, line in enumerate(f):
+            parts = line.rstrip("\n").split("\t")
+            if len(parts) != 9:
+                raise ValueError(f"{file}: line {n} has {len(parts)} fields, expected 9")
+            rows.append((parts[0], int(parts[1]), *[float(x) for x in parts[2:]]))
     return rows
 
 
@@ -387,4 +425,14 @@ def main(argv=None, flavor="ori"):
         sides = ("user", "item") if args.certify_side == "both" else (args.certify_side,)
         rows = [row for side in sides for row in certified(final, plan, args.certify_eps, side=side)]
         write_certified(out, runName + ".certified", rows)
+    if args.certify_radius:
+        from .evaluate import certified_radius, init_eval_model, radius_summary
+        final = amf if args.model == "apr" else m
+        plan = init_eval_model(dataset, argparse.Namespace(eval_mode="all"))  # the radius ranks all items
+        sides = ("user", "item") if args.certify_side == "both" else (args.certify_side,)
+        rows = []
+        for side in sides:  # one sweep per side at K = the largest cutoff serves every smaller one
+            eps, _ = certified_radius(final, plan, k=max(args.certify_radius), side=side)
+            rows += [(side, *row) for row in radius_summary(eps.cpu().numpy(), args.certify_radius)]
+        write_radius(out, runName + ".radius", rows)
     return 0

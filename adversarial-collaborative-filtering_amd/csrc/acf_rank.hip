@@ -24,6 +24,7 @@
 #include "acf_adv.h"   // whole-stream adversarial direction (k_adv_*): DESIGN.md §4c
 #include "acf_eval_multi.h"  // multi-item evaluation and rank metrics (k_evx_*): DESIGN.md §4f
 #include "acf_eval_worst.h"  // certified worst-case positions (k_evw_*): DESIGN.md §4g
+#include "acf_eval_radius.h"  // certified radius, the K weakest candidates (k_evr_*): DESIGN.md §4j
 
 // ---- the host frame's shared pieces --------------------------------------------
 static int check_kernel(int32_t kernel) {
@@ -417,6 +418,69 @@ extern "C" int acf_eval_positions_worst(const float* P, const float* Q, int64_t 
          strip_target(part, S, worst), err, s);
   HIP_TRY(hipGetLastError());
   ACF_RET(sum_strips(part, S, (int64_t)n_eps * n_users, worst, s));
+  if (check) ACF_RET(check_eval_range(err, s));
+  return ACF_OK;
+}
+
+// ---- certified radius (acf_eval_radius.h) ---------------------------------------
+static int evr_check(int32_t n_users, int32_t num_cand, int32_t k) {
+  ACF_CHECK(n_users >= 0, ACF_E_INVALID, "negative count");
+  ACF_CHECK(num_cand >= 1, ACF_E_INVALID, "num_candidates must be >= 1, got %d", num_cand);
+  ACF_CHECK(k >= 1 && k <= TOPK_MAX_K, ACF_E_INVALID, "k must be in [1, %d], got %d", TOPK_MAX_K, k);
+  return ACF_OK;
+}
+
+extern "C" int acf_eval_radius_workspace(int32_t n_users, int32_t num_cand, int32_t k, size_t* bytes) {
+  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
+  ACF_RET(evr_check(n_users, num_cand, k));
+  *bytes = evr_workspace(n_users, num_cand, k);
+  return ACF_OK;
+}
+
+// The keys and the rows together pass the 64 KB default of dynamic LDS (side user at d = 512: 64 KB + the static
+// part), so every instance opts in to its largest, as topk_lds_optin does; UB = 8 serves d <= 512, UB = 4 d <= 1024.
+template <int UB, bool USER>
+static int launch_evr(const float* P, const float* Q, int d, int64_t U1, int64_t I1, const int32_t* users,
+                      const int32_t* tests, int n_users, int num_cand, const int64_t* excl_off, const int32_t* excl,
+                      int K, int wper, int S, uint64_t* lists, int32_t* err, hipStream_t s) {
+  constexpr int D_MAX = UB == EVW_UB ? EVW_D_SPLIT : 1024;
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_evr_sweep<UB, USER>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)evr_lds(UB, USER, D_MAX)));
+  const dim3 grid((unsigned)((n_users + UB - 1) / UB), (unsigned)S);
+  k_evr_sweep<UB, USER><<<grid, 256, evr_lds(UB, USER, d), s>>>(P, Q, d, U1, I1, users, tests, n_users, num_cand,
+                                                                excl_off, excl, K, wper, S, lists, err);
+  HIP_TRY(hipGetLastError());
+  return ACF_OK;
+}
+
+extern "C" int acf_eval_radius(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
+                               const int32_t* users, const int32_t* test_items, int32_t n_users, int32_t num_cand,
+                               const int64_t* excl_off, const int32_t* excl, int32_t k, int32_t side, float* eps_out,
+                               int32_t* items_out, void* workspace, size_t workspace_bytes, int32_t check,
+                               void* stream_) {
+  ACF_RET(check_dim(d));
+  ACF_RET(evr_check(n_users, num_cand, k));
+  ACF_CHECK(side == 0 || side == 1, ACF_E_INVALID, "side must be 0 (user) or 1 (item), got %d", side);
+  ACF_CHECK(U1 > 0 && I1 > 0, ACF_E_INVALID, "empty table");
+  ACF_CHECK(num_cand <= I1, ACF_E_INVALID, "num_candidates %d > item rows", num_cand);
+  ACF_CHECK(P && Q && users && test_items && eps_out && items_out && workspace, ACF_E_INVALID, "NULL argument");
+  ACF_RET(check_excl_pair(excl_off, excl));
+  ACF_RET(check_workspace(workspace, workspace_bytes, evr_workspace(n_users, num_cand, k), 8));
+  if (n_users == 0) return ACF_OK;
+  int wper = 0, S = 0;
+  evr_strips(n_users, num_cand, k, &wper, &S);
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  int32_t* err = static_cast<int32_t*>(workspace);
+  uint64_t* lists = reinterpret_cast<uint64_t*>(static_cast<char*>(workspace) + EVR_WS_HEAD);
+  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+  const bool wide = d <= EVW_D_SPLIT;  // 8 entries per workgroup, 4 above: the rows stay within 32 KB of LDS
+  const auto launch = side == 0 ? (wide ? &launch_evr<EVW_UB, true> : &launch_evr<EVW_UB / 2, true>)
+                                : (wide ? &launch_evr<EVW_UB, false> : &launch_evr<EVW_UB / 2, false>);
+  ACF_RET(launch(P, Q, d, U1, I1, users, test_items, n_users, num_cand, excl_off, excl, k, wper, S, lists, err, s));
+  k_topk_merge<<<(unsigned)n_users, 256, 0, s>>>(lists, S, k, items_out, eps_out);  // scores: -eps
+  HIP_TRY(hipGetLastError());
+  k_evr_negate<<<grid_for((int64_t)n_users * k), 256, 0, s>>>(eps_out, (int64_t)n_users * k);
+  HIP_TRY(hipGetLastError());
   if (check) ACF_RET(check_eval_range(err, s));
   return ACF_OK;
 }

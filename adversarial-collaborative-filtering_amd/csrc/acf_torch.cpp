@@ -22,6 +22,7 @@
 //   acf::eval_positions_multi  positions of several held-out items per user, one sweep per user
 //   acf::rank_metrics          hit / recall / precision / ndcg / map @K, mrr, auc of such positions (fp64)
 //   acf::eval_positions_worst  certified worst-case positions under an eps attack on the user or the item rows
+//   acf::eval_radius           certified radius: per entry the k smallest eps at which a candidate breaks the top-K
 #include <torch/library.h>
 #include <ATen/ATen.h>
 // ROCm builds of PyTorch keep the "cuda" device type: the guard and stream
@@ -629,6 +630,43 @@ at::Tensor eval_positions_worst(const at::Tensor& P, const at::Tensor& Q, const 
   return worst;
 }
 
+// the k smallest (eps_c, c) per entry, eps [n, k] ascending and items [n, k] (acf_eval_radius; side:
+// "user" | "item"): eps[r][j] is the certified radius at j + 1.  Checks as eval_positions_worst.
+std::tuple<at::Tensor, at::Tensor> eval_radius(const at::Tensor& P, const at::Tensor& Q, const at::Tensor& users_,
+                                               const at::Tensor& test_items_, int64_t num_candidates,
+                                               const at::Tensor& excl_off, const at::Tensor& excl_items_, int64_t k,
+                                               c10::string_view side) {
+  need_table(P, "embedding_P", P);
+  need_table(Q, "embedding_Q", P);
+  TORCH_CHECK(P.size(1) == Q.size(1), "embedding_P and embedding_Q dims differ");
+  TORCH_CHECK(side == "user" || side == "item", "side must be \"user\" or \"item\", got \"", side, "\"");
+  TORCH_CHECK(k >= 1 && k <= 128, "k must lie in [1, 128], got ", k);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(P.device());
+  at::Tensor users = idx32(users_, "users", P), tests = idx32(test_items_, "test_items", P);
+  at::Tensor excl = idx32(excl_items_, "excl_items", P);
+  const int64_t n = users.numel();
+  TORCH_CHECK(n < (1ll << 31), "too many users");
+  TORCH_CHECK(tests.numel() == n, "test_items must have one entry per user");
+  TORCH_CHECK(num_candidates >= 1 && num_candidates <= Q.size(0), "num_candidates must lie in [1, item rows]");
+  const bool no_excl = excl_off.numel() == 0 && excl.numel() == 0;
+  if (!no_excl) need_csr(excl_off, "excl_off", n, excl.numel(), P);
+  check_range(users, P.size(0), "users");
+  check_range(tests, Q.size(0), "test_items");
+  if (excl.numel() == 0) excl = at::zeros({1}, users.options());
+  at::Tensor eps = at::empty({n, k}, P.options()), items = at::empty({n, k}, users.options());
+  if (n == 0) return {eps, items};
+  size_t ws = 0;
+  ok(acf_eval_radius_workspace((int32_t)n, (int32_t)num_candidates, (int32_t)k, &ws), "acf_eval_radius_workspace");
+  at::Tensor work = at::empty({(int64_t)((ws + 7) / 8)}, users.options().dtype(at::kLong));
+  ok(acf_eval_radius(P.data_ptr<float>(), Q.data_ptr<float>(), P.size(0), Q.size(0), (int32_t)P.size(1),
+                     users.data_ptr<int32_t>(), tests.data_ptr<int32_t>(), (int32_t)n, (int32_t)num_candidates,
+                     no_excl ? nullptr : excl_off.data_ptr<int64_t>(), no_excl ? nullptr : excl.data_ptr<int32_t>(),
+                     (int32_t)k, side == "user" ? 0 : 1, eps.data_ptr<float>(), items.data_ptr<int32_t>(),
+                     work.data_ptr(), ws, 0, stream_of(P)),
+     "acf_eval_radius");
+  return {eps, items};
+}
+
 }  // namespace
 
 #ifndef ACF_BUILD_HASH
@@ -673,6 +711,8 @@ TORCH_LIBRARY(acf, m) {
         "(Tensor per_user, Tensor per_user_free, Tensor mean_cut, Tensor mean_free, Tensor n_scored)");
   m.def("eval_positions_worst(Tensor P, Tensor Q, Tensor users, Tensor test_items, int num_candidates, "
         "Tensor excl_off, Tensor excl_items, float[] eps, str side=\"user\") -> Tensor");
+  m.def("eval_radius(Tensor P, Tensor Q, Tensor users, Tensor test_items, int num_candidates, Tensor excl_off, "
+        "Tensor excl_items, int k=10, str side=\"user\") -> (Tensor eps, Tensor items)");
 }
 
 TORCH_LIBRARY_IMPL(acf, CUDA, m) {
@@ -692,4 +732,5 @@ TORCH_LIBRARY_IMPL(acf, CUDA, m) {
   m.impl("eval_positions_multi", &eval_positions_multi);
   m.impl("rank_metrics", &rank_metrics);
   m.impl("eval_positions_worst", &eval_positions_worst);
+  m.impl("eval_radius", &eval_radius);
 }

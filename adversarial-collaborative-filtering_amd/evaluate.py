@@ -312,6 +312,142 @@ def certified(model_or_tables, plan: EvalPlan, eps_list, side="user", cutoffs=No
     return rows
 
 
+# ---- certified radius: the largest eps each user's top-K hit survives -----------
+_F32_MAX = np.float32(np.finfo(np.float32).max)
+
+
+def min_eps_f32(m, base, side="user", return_fallback=False):
+    """Per element the smallest finite float32 e >= 0 with the fp32 predicate of
+    ops.eval_positions_worst, m <= fl(e * base) (side "user") or m <= fl(fl(2 e) *
+    base) ("item"), +inf where no finite e satisfies it: ops.eval_radius's
+    per-candidate value restated in numpy float32 with the kernel's operations
+    (the quotient, up to 4 steps over neighbouring floats, then a bisection on
+    the bit pattern).  m and base broadcast; float32 out.  return_fallback: also
+    the mask of the elements the 4 steps did not settle."""
+    if side not in CERT_SIDES:
+        raise ValueError(f"side must be one of {CERT_SIDES}, got {side!r}")
+    m, base = np.broadcast_arrays(np.asarray(m, dtype=np.float32), np.asarray(base, dtype=np.float32))
+    shape = m.shape
+    m, base = np.ascontiguousarray(m).reshape(-1), np.ascontiguousarray(base).reshape(-1)
+    two, half = np.float32(2.0), np.float32(0.5)
+
+    def pred(e):
+        return m <= (e * base if side == "user" else (two * e) * base)
+
+    def nudge(e, by):  # the float whose bit pattern is by away
+        return (e.view(np.int32) + np.int32(by)).view(np.float32)
+
+    with np.errstate(all="ignore"):
+        out = np.full(m.shape, np.inf, dtype=np.float32)
+        zero = pred(np.zeros_like(m))
+        out[zero] = 0.0
+        todo = ~zero & pred(np.full_like(m, _F32_MAX))
+        e = m / base if side == "user" else (m / base) * half
+        e = np.where(e <= _F32_MAX, e, _F32_MAX).astype(np.float32)
+        e = np.where(e > 0, e, np.uint32(1).view(np.float32)).astype(np.float32)  # the smallest denormal
+        for _ in range(4):
+            lo = nudge(e, -1)
+            p = pred(e)
+            hit = todo & p & ~pred(lo)
+            out[hit] = e[hit]
+            todo &= ~hit
+            e = np.where(p, lo, nudge(e, 1))
+        fallback = todo.copy()
+        if todo.any():
+            idx = np.flatnonzero(todo)
+            lo = np.zeros(len(idx), dtype=np.uint32)
+            hi = np.full(len(idx), _F32_MAX.view(np.uint32), dtype=np.uint32)
+            m, base = m[idx], base[idx]  # pred is over these from here on
+            while ((hi - lo) > 1).any():  # !pred(lo), pred(hi): at most 31 rounds
+                wide = (hi - lo) > 1
+                mid = lo + ((hi - lo) >> np.uint32(1))
+                ok = pred(mid.view(np.float32))
+                hi = np.where(wide & ok, mid, hi)
+                lo = np.where(wide & ~ok, mid, lo)
+            out[idx] = hi.view(np.float32)
+    out = out.reshape(shape)
+    return (out, fallback.reshape(shape)) if return_fallback else out
+
+
+def _k_smallest(val, cand, k):
+    """Per row the k smallest val over cand, ascending, ties to the lower column:
+    (values [n, k] padded with +inf, columns int64 [n, k] padded with -1)."""
+    n = val.shape[0]
+    eps = np.full((n, k), np.inf, dtype=val.dtype)
+    items = np.full((n, k), -1, dtype=np.int64)
+    for r in range(n):
+        cols = np.flatnonzero(cand[r])
+        order = cols[np.argsort(val[r, cols], kind="stable")][:k]
+        eps[r, :len(order)], items[r, :len(order)] = val[r, order], order
+    return eps, items
+
+
+def radius_host(P, Q, users, test_items, num_candidates, excl_lists, k, side="user"):
+    """ops.eval_radius restated in float64 numpy from worst_margins_host: per
+    candidate m / base clipped at 0 (+inf for m > 0 with base 0), per entry the k
+    smallest ascending, ties to the lower id: (eps float64 [n, k] padded with
+    +inf, items int64 [n, k] padded with -1)."""
+    m, base, cand = worst_margins_host(P, Q, users, test_items, num_candidates, excl_lists, side)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        e = np.where(m <= 0, 0.0, m / base)
+    return _k_smallest(e, cand, int(k))
+
+
+def certified_radius(model_or_tables, plan: EvalPlan, k=None, side="user"):
+    """The certified radius of every user of an all-items plan
+    (ops.eval_radius on the plan's exclusions): (eps float32 [n, k], items int32
+    [n, k]), device tensors, k = plan.K by default.  eps[r, j] is the largest
+    budget up to which user r's held-out item provably stays in the top j + 1
+    under every perturbation of the side's rows (strictly below it the item is
+    certified; at it, it no longer is), items[r] the candidates that break the
+    certificate first.  One sweep of the catalogue serves every cutoff <= k;
+    radius_summary and radius_curve reduce eps."""
+    if plan.mode != "all":
+        raise ValueError("certified_radius needs an all-items plan (init_eval_model with eval_mode='all')")
+    if side not in CERT_SIDES:
+        raise ValueError(f"side must be one of {CERT_SIDES}, got {side!r}")
+    k = int(plan.K) if k is None else k
+    if hasattr(model_or_tables, "embedding_P"):
+        P, Q = model_or_tables.embedding_P, model_or_tables.embedding_Q
+    else:
+        P, Q = model_or_tables[0], model_or_tables[1]
+    u, t, eo, ex = plan.device_arrays(P.device)
+    return ops.eval_radius(P, Q, u, t, int(plan.num_candidates), eo, ex, k=k, side=side)
+
+
+RADIUS_QUANTILES = (0.10, 0.25, 0.50, 0.75, 0.90)
+
+
+def _radius_column(eps, K):
+    eps = np.asarray(eps)
+    if eps.ndim != 2 or not 1 <= int(K) <= eps.shape[1]:
+        raise ValueError(f"K must lie in [1, {eps.shape[1] if eps.ndim == 2 else 0}] of eps [n, k], got {K!r}")
+    return eps[:, int(K) - 1].astype(np.float64)
+
+
+def radius_summary(eps, cutoffs):
+    """The distribution over users of the radius at every K of cutoffs: rows (K,
+    the share of users already missed (radius 0), the share unbounded (+inf: no
+    finite budget pushes the item out), the 10 / 25 / 50 / 75 / 90 % quantiles of
+    the finite radii (nan without one)).  eps: certified_radius's [n, k] array."""
+    rows = []
+    for K in cutoffs:
+        col = _radius_column(eps, K)
+        n = max(len(col), 1)
+        finite = col[np.isfinite(col)]
+        qs = np.quantile(finite, RADIUS_QUANTILES) if len(finite) else np.full(len(RADIUS_QUANTILES), np.nan)
+        rows.append((int(K), float((col == 0).sum() / n), float(np.isposinf(col).sum() / n), *[float(q) for q in qs]))
+    return rows
+
+
+def radius_curve(eps, K, eps_list):
+    """hr_lb(e) = the share of users whose radius at K exceeds e, for every e of
+    eps_list: certified(..., eps_list, cutoffs=(K,))'s hr_lb, since worst < K iff
+    e < eps[:, K - 1]."""
+    col = _radius_column(eps, K)
+    return [float((col > float(e)).sum() / max(len(col), 1)) for e in eps_list]
+
+
 # ---- fold-in: rows for users who were not in the training set -----------------
 class FoldIn:
     """What fold_in returns: keys (the dict's keys ascending, or 0..n-1 for a

@@ -266,6 +266,13 @@ class MF:
         from .evaluate import certified
         return certified(self, plan, eps_list, side=side, cutoffs=cutoffs)
 
+    def certified_radius(self, plan, k=None, side="user"):
+        """evaluate.certified_radius: (eps [n, k], items [n, k]), per user the
+        largest eps up to which the held-out item provably stays in the top 1..k
+        and the items that break the certificate first."""
+        from .evaluate import certified_radius
+        return certified_radius(self, plan, k=k, side=side)
+
 
 class Session:
     """Minimal ``tf.Session`` stand-in for the fetches the APR path uses."""

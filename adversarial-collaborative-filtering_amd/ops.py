@@ -1132,6 +1132,64 @@ def eval_positions_worst(P, Q, users, test_items, num_candidates: int, excl_off=
     return worst
 
 
+def eval_radius_workspace(n_users: int, num_candidates: int, k: int) -> int:
+    """Bytes of device workspace acf_eval_radius needs (a host-only query)."""
+    return _workspace_bytes("acf_eval_radius_workspace", n_users, num_candidates, k)
+
+
+def eval_radius(P, Q, users, test_items, num_candidates: int, excl_off=None, excl_items=None, k: int = 10,
+                side: str = "user", check: bool = True, workspace=None):
+    """Certified radius (acf_eval_radius): (eps float32 [n, k], items int32 [n,
+    k]).  Entries, candidates, exclusions and sides are eval_positions_worst's.
+    Every candidate c has a smallest fp32 eps_c >= 0 at which that call's
+    predicate counts it (0 when it already scores >= t, +inf when no finite
+    budget lifts it); eps[r] are the k smallest of entry r ascending, ties to
+    the lower item id, items[r] their candidates, +inf / -1 past the entry's
+    candidates.  eps[r, j] is the certified radius at j + 1: for every finite e
+    >= 0, eval_positions_worst(..., eps=(e,))[0, r] < j + 1 iff e < eps[r, j],
+    exactly, so no perturbation within a smaller budget pushes t out of the top
+    j + 1.  One sweep of the candidates whatever k (1..128); identical bits run
+    to run.  workspace: None (allocated per call) or an int64 tensor on the
+    tables' device of at least eval_radius_workspace(n, num_candidates, k)
+    bytes, kept by a caller that repeats the call.  Bad shapes, dtypes, k, side
+    and a short workspace raise ValueError / TypeError before any native call;
+    with check, a user or test item outside its table raises NativeIndexError
+    (one sync), without it such an index is read as row 0."""
+    _check_k(k)
+    if side not in WORST_SIDES:
+        raise ValueError(f"side must be one of {sorted(WORST_SIDES)}, got {side!r}")
+    ti = _csr_items(test_items, "test_items")
+    us = _csr_items(users, "users")
+    n = us.numel()
+    if ti.numel() != n:
+        raise ValueError(f"test_items must have one entry per user: {ti.numel()} for {n}")
+    _check_num_candidates(num_candidates)
+    _table_types(P, Q)
+    if num_candidates > Q.shape[0]:
+        raise ValueError("num_candidates exceeds item rows")
+    eoff, ex = _exclusions(excl_off, excl_items, n, P.device)
+    dev = _table_pair(P, Q)
+    settle_tables()
+    u, t = _to_i32(us, dev), _to_i32(ti, dev)
+    eps = torch.empty((n, k), dtype=torch.float32, device=dev)
+    items = torch.empty((n, k), dtype=torch.int32, device=dev)
+    if n == 0:
+        return eps, items
+    nbytes = eval_radius_workspace(n, num_candidates, k)
+    if workspace is None:
+        work = _workspace(nbytes, 8, dev)
+    else:
+        _require(workspace, "workspace", torch.int64, dev, 1)
+        work = workspace
+        if work.numel() * 8 < nbytes:
+            raise ValueError(f"workspace too small: {work.numel() * 8} < {nbytes} bytes")
+    with _on(dev):
+        call("acf_eval_radius", P.data_ptr(), Q.data_ptr(), P.shape[0], Q.shape[0], P.shape[1], u.data_ptr(),
+             t.data_ptr(), n, num_candidates, _ptr(eoff), _ptr(ex), k, WORST_SIDES[side], eps.data_ptr(),
+             items.data_ptr(), work.data_ptr(), nbytes, int(bool(check)), _stream_ptr(dev))
+    return eps, items
+
+
 ADV_MODES = {"grad": 0, "random": 1}
 ADV_MAX_TRIPLETS = (1 << 29) - 1
 

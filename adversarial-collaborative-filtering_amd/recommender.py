@@ -307,3 +307,10 @@ class APR(Recommender):
         ndcg_lb, auc_lb), lower bounds under every attack of that budget."""
         self._ensure()
         return self.model.certified(plan, eps_list, side=side, cutoffs=cutoffs)
+
+    def certified_radius(self, plan, k=None, side="user"):
+        """evaluate.certified_radius against an all-items plan: (eps [n, k], items
+        [n, k]), per user the largest eps up to which the held-out item provably
+        stays in the top 1..k and the items that break the certificate first."""
+        self._ensure()
+        return self.model.certified_radius(plan, k=k, side=side)

@@ -39,6 +39,11 @@ SURVEY.md §8(b) proposes:
   -> worst [n_eps, n]``: certified worst-case positions under an eps attack on the user or the
   item rows (``ops.eval_positions_worst``, the same values); users and test items are checked
   before any gather; empty ``excl_off`` and ``excl_items`` exclude nothing;
+- ``eval_radius(P, Q, users, test_items, num_candidates, excl_off, excl_items, k, side)
+  -> (eps [n, k], items [n, k])``: the certified radius, per entry the k smallest eps at which a
+  candidate breaks the certificate and those candidates (``ops.eval_radius``, the same values);
+  ``eps[r, j]`` is the largest budget up to which the test item provably stays in the top j + 1.
+  Checks as ``eval_positions_worst``;
 - ``release_contexts() -> int``: frees the cached step contexts (plan workspace and
   the streamed step's version buffers) that ``apr_train`` / ``bpr_apr_step`` keep per
   (device, table shape, batch shape).
@@ -57,7 +62,8 @@ from . import build_native
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libacf_torch.so")
 OPS = ("bpr_apr_step", "apr_train", "gather_bpr_fwd_bwd", "row_segment_sum", "l2norm_perturb",
        "sparse_adagrad_apply", "score_rank", "score_rank_all", "recommend_topk", "adv_direction", "adv_apply",
-       "fold_in_users", "fold_in_items", "eval_positions_multi", "rank_metrics", "eval_positions_worst", "release_contexts")
+       "fold_in_users", "fold_in_items", "eval_positions_multi", "rank_metrics", "eval_positions_worst", "eval_radius",
+       "release_contexts")
 _lock = threading.Lock()
 _loaded = False
 

@@ -538,6 +538,44 @@ int acf_eval_positions_worst(const float* P, const float* Q, int64_t num_user_ro
                              const float* eps, int32_t n_eps, int32_t side, int32_t* worst, void* workspace,
                              size_t workspace_bytes, int32_t check, void* stream);
 
+/* ---- certified radius: the largest eps each entry's top-K hit survives --------
+ * (no reference counterpart.)  Entries, candidates C_r, exclusions and the test
+ * item are acf_eval_positions_worst's, and so are the fp32 values m_c, D_c and
+ * Np, bit for bit.  For candidate c, eps_c is the smallest finite fp32 eps >= 0
+ * at which acf_eval_positions_worst's predicate holds as that kernel evaluates
+ * it,
+ *   side 0 (user): m_c <= fl(eps * D_c)
+ *   side 1 (item): m_c <= fl(fl(2 eps) * Np)
+ * and +inf when no finite eps satisfies it (m_c > 0 with D_c or Np equal to 0).
+ * Both products do not decrease in eps, so the minimum exists and is exact (a
+ * quotient fl(m / D) would be off by a few ulps either way); m_c <= 0 gives 0.
+ * Per entry r the call returns the k smallest (eps_c, c) over c in C_r, c != t:
+ *   eps_out[r * k + j] ascending, ties to the lower item id, items_out[r * k + j]
+ * their items, padded with +inf / -1 when the entry has fewer than k candidates.
+ * eps_out[r * k + j] is the certified radius at j + 1: for every finite eps >= 0
+ *   worst_eps[r] < j + 1  <=>  eps < eps_out[r * k + j]
+ * with acf_eval_positions_worst's integers, so no perturbation within a smaller
+ * budget pushes t out of the top j + 1, and the number of zeros in the row is
+ * min(k, acf_eval_positions_multi's position of t).  items_out are the
+ * candidates that break the certificate first.  One sweep of the candidates
+ * whatever k; exact, identical bits run to run; no [n_users, num_candidates]
+ * array is formed.  eps_out: device float [n_users][k]; items_out: device int32
+ * [n_users][k].  `workspace`: device memory, 8-byte aligned, at least
+ * acf_eval_radius_workspace(n_users, num_candidates, k) bytes -- a host-only
+ * query that touches no device; a smaller or misaligned one is ACF_E_INVALID, as
+ * are k outside [1, 128], a side other than 0 or 1, num_candidates outside [1,
+ * num_item_rows] and a NULL argument (excl_off = excl_items = NULL excludes
+ * nothing), all before any launch.  n_users = 0 does nothing.  A user outside
+ * [0, num_user_rows) or a test item outside [0, num_item_rows) is read as row
+ * 0; with check != 0 the call then synchronises once, after its launches, and
+ * returns ACF_E_RANGE (check == 0: no error, no sync).  Tables are assumed
+ * finite. */
+int acf_eval_radius_workspace(int32_t n_users, int32_t num_candidates, int32_t k, size_t* bytes);
+int acf_eval_radius(const float* P, const float* Q, int64_t num_user_rows, int64_t num_item_rows, int32_t dim,
+                    const int32_t* users, const int32_t* test_items, int32_t n_users, int32_t num_candidates,
+                    const int64_t* excl_off, const int32_t* excl_items, int32_t k, int32_t side, float* eps_out,
+                    int32_t* items_out, void* workspace, size_t workspace_bytes, int32_t check, void* stream);
+
 /* ---- robustness evaluation: a whole-stream adversarial direction ------------
  * utils.py:145-154 (adv_update): ONE delta over all n triplets as one batch, as
  * dense tables.  acf_adv_direction fills EVERY row of the unit-direction tables
