@@ -20,16 +20,8 @@
 #include <algorithm>
 
 #include "acf_apr.h"
+#include "acf_host.h"  // HIP_TRY, ACF_CHECK, ACF_RET, grid_for, geometry, check_dim
 #include "acf_rows.h"
-
-// acf_apr.hip (thread-local message); hidden as in acf_host.h
-__attribute__((visibility("hidden"))) int acf_set_error(int code, const char* fmt, ...);
-
-#define OPS_TRY(expr)                                                               \
-  do {                                                                              \
-    hipError_t e_ = (expr);                                                         \
-    if (e_ != hipSuccess) return acf_set_error(ACF_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 static inline unsigned ops_grid(int64_t items, int lpr) {
   return (unsigned)((items * lpr + 255) / 256);
@@ -121,9 +113,7 @@ __global__ void __launch_bounds__(256) k_l2norm_perturb(const float* __restrict_
   int l;
   const int64_t r = ops_item<LPR>(l);
   if (r >= k) return;
-  const RowV<NV> x = load_row<LPR, NV>(g, r, d, l);
-  const float inv = __builtin_amdgcn_rsqf(fmaxf(dot_row<LPR, NV>(x, x), 1e-12f));
-  store_row<LPR, NV>(out, r, d, l, scale_row(scale_row(x, inv), eps));
+  store_row<LPR, NV>(out, r, d, l, l2_delta<LPR, NV>(load_row<LPR, NV>(g, r, d, l), eps));
 }
 
 template <int LPR, int NV>
@@ -135,18 +125,7 @@ __global__ void __launch_bounds__(256) k_sparse_adagrad(float* __restrict__ W, f
   if (r >= k) return;
   const int64_t row = idx[r];
   RowV<NV> w = load_row<LPR, NV>(W, row, d, l), c = load_row<LPR, NV>(acc, row, d, l);
-  const RowV<NV> x = load_row<LPR, NV>(g, r, d, l);
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    c.v[v].x = c.v[v].x + x.v[v].x * x.v[v].x;
-    c.v[v].y = c.v[v].y + x.v[v].y * x.v[v].y;
-    c.v[v].z = c.v[v].z + x.v[v].z * x.v[v].z;
-    c.v[v].w = c.v[v].w + x.v[v].w * x.v[v].w;
-    w.v[v].x = w.v[v].x - (lr * x.v[v].x) * __builtin_amdgcn_rsqf(c.v[v].x);
-    w.v[v].y = w.v[v].y - (lr * x.v[v].y) * __builtin_amdgcn_rsqf(c.v[v].y);
-    w.v[v].z = w.v[v].z - (lr * x.v[v].z) * __builtin_amdgcn_rsqf(c.v[v].z);
-    w.v[v].w = w.v[v].w - (lr * x.v[v].w) * __builtin_amdgcn_rsqf(c.v[v].w);
-  }
+  adagrad_apply(w, c, load_row<LPR, NV>(g, r, d, l), lr);
   store_row<LPR, NV>(acc, row, d, l, c);
   store_row<LPR, NV>(W, row, d, l, w);
 }
@@ -154,10 +133,8 @@ __global__ void __launch_bounds__(256) k_sparse_adagrad(float* __restrict__ W, f
 // lanes per row and float4 per lane for dim d (as the step kernels)
 #define OPS_GEOM(d, BODY)                                                             \
   do {                                                                                \
-    const int d4_ = (d) / 4;                                                          \
-    int lpr_ = 1;                                                                     \
-    while (lpr_ < d4_ && lpr_ < 64) lpr_ <<= 1;                                       \
-    const int nv_ = (d4_ + lpr_ - 1) / lpr_;                                          \
+    int lpr_, nv_;                                                                    \
+    geometry((d), &lpr_, &nv_);                                                       \
     switch (lpr_ * 100 + nv_) {                                                       \
       case 101: { constexpr int LPR = 1, NV = 1; BODY; } break;                       \
       case 201: { constexpr int LPR = 2, NV = 1; BODY; } break;                       \
@@ -173,17 +150,11 @@ __global__ void __launch_bounds__(256) k_sparse_adagrad(float* __restrict__ W, f
     }                                                                                 \
   } while (0)
 
-static int ops_dim(int d) {
-  if (d < 4 || d > 1024 || d % 4) return acf_set_error(ACF_E_INVALID, "dim must be a multiple of 4 in [4, 1024]");
-  return ACF_OK;
-}
-
 extern "C" int acf_gather_bpr_fwd_bwd(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
                                       const int32_t* u, const int32_t* ip, const int32_t* in, int64_t n,
                                       float clip_lo, float clip_hi, float* loss, float* x, int32_t* p_idx,
                                       float* p_val, int32_t* q_idx, float* q_val, void* stream) {
-  int r = ops_dim(d);
-  if (r) return r;
+  ACF_RET(check_dim(d));
   if (!P || !Q || !u || !ip || !in || !loss || !x || !p_idx || !p_val || !q_idx || !q_val || n < 0 || U1 <= 0 ||
       I1 <= 0)
     return acf_set_error(ACF_E_INVALID, "gather_bpr_fwd_bwd: NULL argument or bad size");
@@ -191,7 +162,7 @@ extern "C" int acf_gather_bpr_fwd_bwd(const float* P, const float* Q, int64_t U1
   hipStream_t s = static_cast<hipStream_t>(stream);
   OPS_GEOM(d, (k_gather_bpr<LPR, NV><<<ops_grid(n, LPR), 256, 0, s>>>(P, Q, d, u, ip, in, n, clip_lo, clip_hi,
                                                                          loss, x, p_idx, p_val, q_idx, q_val)));
-  OPS_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return ACF_OK;
 }
 
@@ -216,8 +187,7 @@ extern "C" int acf_row_segment_sum_workspace(int64_t m, size_t* bytes) {
 extern "C" int acf_row_segment_sum(const int32_t* idx, const float* vals, int64_t m, int32_t d,
                                    int64_t num_rows, void* workspace, size_t ws_bytes, int32_t* out_uniq,
                                    float* out_sum, int32_t* out_count, int64_t* out_k, void* stream) {
-  int r = ops_dim(d);
-  if (r) return r;
+  ACF_RET(check_dim(d));
   size_t need = 0;
   acf_row_segment_sum_workspace(m, &need);
   if (!idx || !vals || !out_uniq || !out_sum || !out_count || !out_k || (m > 0 && (!workspace || ws_bytes < need)))
@@ -226,7 +196,7 @@ extern "C" int acf_row_segment_sum(const int32_t* idx, const float* vals, int64_
     return acf_set_error(ACF_E_INVALID, "row_segment_sum: num_rows outside (0, 2^31]");
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (m == 0) {
-    OPS_TRY(hipMemsetAsync(out_k, 0, sizeof(int64_t), s));
+    HIP_TRY(hipMemsetAsync(out_k, 0, sizeof(int64_t), s));
     return ACF_OK;
   }
   char* w = static_cast<char*>(workspace);
@@ -245,39 +215,37 @@ extern "C" int acf_row_segment_sum(const int32_t* idx, const float* vals, int64_
   while (bits < 32 && (1ll << bits) < num_rows) ++bits;
   // indices in [0, num_rows) sort as unsigned on their low `bits`; stable: the
   // positions of one index stay in input order
-  OPS_TRY(rocprim::radix_sort_pairs(tmp, tb, reinterpret_cast<const uint32_t*>(idx), kout, pin, pout, (size_t)m,
+  HIP_TRY(rocprim::radix_sort_pairs(tmp, tb, reinterpret_cast<const uint32_t*>(idx), kout, pin, pout, (size_t)m,
                                     0, bits, s));
   k_seg_heads<<<g, 256, 0, s>>>(kout, m, flag);
   tb = ws_bytes - 5 * a;
-  OPS_TRY(rocprim::inclusive_scan(tmp, tb, flag, inc, (size_t)m, rocprim::plus<int32_t>(), s));
+  HIP_TRY(rocprim::inclusive_scan(tmp, tb, flag, inc, (size_t)m, rocprim::plus<int32_t>(), s));
   k_seg_compact<<<g, 256, 0, s>>>(kout, inc, m, out_uniq, start, out_k);
   OPS_GEOM(d, (k_seg_sum<LPR, NV><<<ops_grid(m, LPR), 256, 0, s>>>(vals, d, pout, start, out_count, out_k, m,
                                                                       out_sum)));
-  OPS_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return ACF_OK;
 }
 
 extern "C" int acf_l2norm_perturb(const float* g, int64_t k, int32_t d, float eps, float* out, void* stream) {
-  int r = ops_dim(d);
-  if (r) return r;
+  ACF_RET(check_dim(d));
   if (!g || !out || k < 0) return acf_set_error(ACF_E_INVALID, "l2norm_perturb: bad argument");
   if (k == 0) return ACF_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   OPS_GEOM(d, (k_l2norm_perturb<LPR, NV><<<ops_grid(k, LPR), 256, 0, s>>>(g, k, d, eps, out)));
-  OPS_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return ACF_OK;
 }
 
 extern "C" int acf_sparse_adagrad_apply(float* W, float* acc, int64_t rows, int32_t d, const int32_t* idx,
                                         const float* g, int64_t k, float lr, void* stream) {
-  int r = ops_dim(d);
-  if (r) return r;
+  ACF_RET(check_dim(d));
   if (!W || !acc || !idx || !g || k < 0 || rows <= 0)
     return acf_set_error(ACF_E_INVALID, "sparse_adagrad_apply: bad argument");
   if (k == 0) return ACF_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   OPS_GEOM(d, (k_sparse_adagrad<LPR, NV><<<ops_grid(k, LPR), 256, 0, s>>>(W, acc, idx, g, k, d, lr)));
-  OPS_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return ACF_OK;
 }
 

@@ -149,6 +149,29 @@ __device__ __forceinline__ float dot_row(const RowV<NV>& a, const RowV<NV>& b) {
   return group_sum<LPR>(s);
 }
 
+// eps * l2_normalize(G) (APR.py:186-191): G * rsqrt(max(G.G, 1e-12)), then * eps, two rounded products.
+template <int LPR, int NV>
+__device__ __forceinline__ RowV<NV> l2_delta(const RowV<NV>& G, float eps) {
+  const float inv = __builtin_amdgcn_rsqf(fmaxf(dot_row<LPR, NV>(G, G), 1e-12f));
+  return scale_row(scale_row(G, inv), eps);
+}
+
+// Adagrad on one row (APR.py:193-195): a += g * g; w -= (lr * g) * rsqrt(a).
+template <int NV>
+__device__ __forceinline__ void adagrad_apply(RowV<NV>& w, RowV<NV>& a, const RowV<NV>& g, float lr) {
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    a.v[v].x = a.v[v].x + g.v[v].x * g.v[v].x;
+    a.v[v].y = a.v[v].y + g.v[v].y * g.v[v].y;
+    a.v[v].z = a.v[v].z + g.v[v].z * g.v[v].z;
+    a.v[v].w = a.v[v].w + g.v[v].w * g.v[v].w;
+    w.v[v].x = w.v[v].x - (lr * g.v[v].x) * __builtin_amdgcn_rsqf(a.v[v].x);
+    w.v[v].y = w.v[v].y - (lr * g.v[v].y) * __builtin_amdgcn_rsqf(a.v[v].y);
+    w.v[v].z = w.v[v].z - (lr * g.v[v].z) * __builtin_amdgcn_rsqf(a.v[v].z);
+    w.v[v].w = w.v[v].w - (lr * g.v[v].w) * __builtin_amdgcn_rsqf(a.v[v].w);
+  }
+}
+
 // softplus threshold of TF's SoftplusOp: log(FLT_EPSILON) + 2.
 #define ACF_SOFTPLUS_T 13.942385f
 

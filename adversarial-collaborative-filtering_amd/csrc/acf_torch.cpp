@@ -410,103 +410,6 @@ std::tuple<at::Tensor, at::Tensor> adv_apply(const at::Tensor& W, const at::Tens
   return {sum, delta};
 }
 
-// rows, accumulators and per-epoch losses of n new users fitted against a frozen Q
-// (acf_fold_in_users, items range-checked by the call); init / acc_init: [n, d] or None
-std::tuple<at::Tensor, at::Tensor, at::Tensor> fold_in_users(
-    const at::Tensor& Q, const at::Tensor& user_off, const at::Tensor& item_pos_, const at::Tensor& item_neg_,
-    int64_t epochs, int64_t batch, const c10::optional<at::Tensor>& init, const c10::optional<at::Tensor>& acc_init,
-    double lr, double eps, double reg, double reg_adv, bool adver, double clip_lo, double clip_hi) {
-  need_table(Q, "embedding_Q", Q);
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
-  need(user_off, "user_off", at::kLong, 1);
-  TORCH_CHECK(user_off.device() == Q.device(), "user_off must live on ", Q.device());
-  TORCH_CHECK(user_off.numel() >= 1, "user_off must have n + 1 entries");
-  TORCH_CHECK(epochs >= 0 && epochs < (1ll << 31), "epochs must be >= 0");
-  TORCH_CHECK(batch >= 1 && batch <= ACF_FOLD_MAX_BATCH, "batch must lie in [1, ", ACF_FOLD_MAX_BATCH, "], got ", batch);
-  at::Tensor ip = idx32(item_pos_, "item_pos", Q);
-  const int64_t n = user_off.numel() - 1, T = ip.numel(), d = Q.size(1);
-  TORCH_CHECK(item_neg_.dim() == 2 && item_neg_.size(0) == epochs && item_neg_.size(1) == T,
-              "item_neg must have shape (epochs, len(item_pos))");
-  at::Tensor in = idx32(item_neg_, "item_neg", Q);
-  const at::Tensor off = user_off.cpu();
-  const int64_t* o = off.data_ptr<int64_t>();
-  TORCH_CHECK(o[0] == 0 && o[n] == T, "user_off must start at 0 and end at len(item_pos)");
-  for (int64_t r = 0; r < n; ++r) TORCH_CHECK(o[r] <= o[r + 1], "user_off must be non-decreasing");
-  const float *ini = nullptr, *aci = nullptr;
-  if (init.has_value()) {
-    need(*init, "init", at::kFloat, 2);
-    TORCH_CHECK(init->device() == Q.device() && init->size(0) == n && init->size(1) == d, "init must be [n, dim] on ",
-                Q.device());
-    ini = init->data_ptr<float>();
-  }
-  if (acc_init.has_value()) {
-    need(*acc_init, "acc_init", at::kFloat, 2);
-    TORCH_CHECK(acc_init->device() == Q.device() && acc_init->size(0) == n && acc_init->size(1) == d,
-                "acc_init must be [n, dim] on ", Q.device());
-    aci = acc_init->data_ptr<float>();
-  }
-  const acf_apr_hparams hp = hparams(lr, eps, reg, reg_adv, adver, clip_lo, clip_hi);
-  at::Tensor P_new = at::empty({n, d}, Q.options()), acc_new = at::empty({n, d}, Q.options());
-  at::Tensor loss = at::empty({epochs, n}, Q.options());
-  ok(acf_fold_in_users(Q.data_ptr<float>(), Q.size(0), (int32_t)d, user_off.data_ptr<int64_t>(), n,
-                       T ? ip.data_ptr<int32_t>() : nullptr, T && epochs ? in.data_ptr<int32_t>() : nullptr, T,
-                       (int32_t)epochs, (int32_t)batch, &hp, ini, aci, n ? P_new.data_ptr<float>() : nullptr,
-                       n ? acc_new.data_ptr<float>() : nullptr, n && epochs ? loss.data_ptr<float>() : nullptr, 1,
-                       stream_of(Q)),
-     "acf_fold_in_users");
-  return {P_new, acc_new, loss};
-}
-
-// rows, accumulators and per-epoch losses of n new items fitted against frozen P and Q
-// (acf_fold_in_items, users and negatives range-checked by the call); init / acc_init: [n, d] or None
-std::tuple<at::Tensor, at::Tensor, at::Tensor> fold_in_items(
-    const at::Tensor& P, const at::Tensor& Q, const at::Tensor& item_off, const at::Tensor& user_pos_,
-    const at::Tensor& item_neg_, int64_t epochs, int64_t batch, const c10::optional<at::Tensor>& init,
-    const c10::optional<at::Tensor>& acc_init, double lr, double eps, double reg, double reg_adv, bool adver,
-    double clip_lo, double clip_hi) {
-  need_table(P, "embedding_P", P);
-  need_table(Q, "embedding_Q", P);
-  TORCH_CHECK(P.size(1) == Q.size(1), "embedding_P and embedding_Q differ in dim: ", P.size(1), " and ", Q.size(1));
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
-  need(item_off, "item_off", at::kLong, 1);
-  TORCH_CHECK(item_off.device() == Q.device(), "item_off must live on ", Q.device());
-  TORCH_CHECK(item_off.numel() >= 1, "item_off must have n + 1 entries");
-  TORCH_CHECK(epochs >= 0 && epochs < (1ll << 31), "epochs must be >= 0");
-  TORCH_CHECK(batch >= 1 && batch <= ACF_FOLD_MAX_BATCH, "batch must lie in [1, ", ACF_FOLD_MAX_BATCH, "], got ", batch);
-  at::Tensor up = idx32(user_pos_, "user_pos", Q);
-  const int64_t n = item_off.numel() - 1, T = up.numel(), d = Q.size(1);
-  TORCH_CHECK(item_neg_.dim() == 2 && item_neg_.size(0) == epochs && item_neg_.size(1) == T,
-              "item_neg must have shape (epochs, len(user_pos))");
-  at::Tensor in = idx32(item_neg_, "item_neg", Q);
-  const at::Tensor off = item_off.cpu();
-  const int64_t* o = off.data_ptr<int64_t>();
-  TORCH_CHECK(o[0] == 0 && o[n] == T, "item_off must start at 0 and end at len(user_pos)");
-  for (int64_t r = 0; r < n; ++r) TORCH_CHECK(o[r] <= o[r + 1], "item_off must be non-decreasing");
-  const float *ini = nullptr, *aci = nullptr;
-  if (init.has_value()) {
-    need(*init, "init", at::kFloat, 2);
-    TORCH_CHECK(init->device() == Q.device() && init->size(0) == n && init->size(1) == d, "init must be [n, dim] on ",
-                Q.device());
-    ini = init->data_ptr<float>();
-  }
-  if (acc_init.has_value()) {
-    need(*acc_init, "acc_init", at::kFloat, 2);
-    TORCH_CHECK(acc_init->device() == Q.device() && acc_init->size(0) == n && acc_init->size(1) == d,
-                "acc_init must be [n, dim] on ", Q.device());
-    aci = acc_init->data_ptr<float>();
-  }
-  const acf_apr_hparams hp = hparams(lr, eps, reg, reg_adv, adver, clip_lo, clip_hi);
-  at::Tensor Q_new = at::empty({n, d}, Q.options()), acc_new = at::empty({n, d}, Q.options());
-  at::Tensor loss = at::empty({epochs, n}, Q.options());
-  ok(acf_fold_in_items(P.data_ptr<float>(), P.size(0), Q.data_ptr<float>(), Q.size(0), (int32_t)d,
-                       item_off.data_ptr<int64_t>(), n, T ? up.data_ptr<int32_t>() : nullptr,
-                       T && epochs ? in.data_ptr<int32_t>() : nullptr, T, (int32_t)epochs, (int32_t)batch, &hp, ini,
-                       aci, n ? Q_new.data_ptr<float>() : nullptr, n ? acc_new.data_ptr<float>() : nullptr,
-                       n && epochs ? loss.data_ptr<float>() : nullptr, 1, stream_of(Q)),
-     "acf_fold_in_items");
-  return {Q_new, acc_new, loss};
-}
-
 // a CSR's offsets: int64 [n + 1] on `like`'s device, 0 = off[0] <= ... <= off[n] = total (read back once)
 void need_csr(const at::Tensor& off, const char* name, int64_t n, int64_t total, const at::Tensor& like) {
   need(off, name, at::kLong, 1);
@@ -516,6 +419,84 @@ void need_csr(const at::Tensor& off, const char* name, int64_t n, int64_t total,
   const int64_t* o = h.data_ptr<int64_t>();
   TORCH_CHECK(o[0] == 0 && o[n] == total, name, " must start at 0 and end at ", total);
   for (int64_t r = 0; r < n; ++r) TORCH_CHECK(o[r] <= o[r + 1], name, " must be non-decreasing");
+}
+
+// What the two fold-in ops share: the CSR (off, first) and the negatives checked and as int32, init /
+// acc_init [n, d] or None, the outputs; a pointer is null where the C ABI takes no array (an empty one).
+struct FoldArgs {
+  int64_t n, T, d;
+  at::Tensor first, neg, rows, acc, loss;
+  const int32_t *first_p, *neg_p;
+  const float *init_p = nullptr, *acc_init_p = nullptr;
+  float *rows_p, *acc_p, *loss_p;
+};
+
+FoldArgs fold_args(const at::Tensor& Q, const at::Tensor& off, const char* off_name, const at::Tensor& first_,
+                   const char* first_name, const at::Tensor& neg_, int64_t epochs, int64_t batch,
+                   const c10::optional<at::Tensor>& init, const c10::optional<at::Tensor>& acc_init) {
+  TORCH_CHECK(off.numel() >= 1, off_name, " must have n + 1 entries");
+  TORCH_CHECK(epochs >= 0 && epochs < (1ll << 31), "epochs must be >= 0");
+  TORCH_CHECK(batch >= 1 && batch <= ACF_FOLD_MAX_BATCH, "batch must lie in [1, ", ACF_FOLD_MAX_BATCH, "], got ", batch);
+  FoldArgs a;
+  a.first = idx32(first_, first_name, Q);
+  a.n = off.numel() - 1, a.T = a.first.numel(), a.d = Q.size(1);
+  TORCH_CHECK(neg_.dim() == 2 && neg_.size(0) == epochs && neg_.size(1) == a.T,
+              "item_neg must have shape (epochs, len(", first_name, "))");
+  a.neg = idx32(neg_, "item_neg", Q);
+  need_csr(off, off_name, a.n, a.T, Q);
+  const auto start = [&](const c10::optional<at::Tensor>& t, const char* name) -> const float* {
+    if (!t.has_value()) return nullptr;
+    need(*t, name, at::kFloat, 2);
+    TORCH_CHECK(t->device() == Q.device() && t->size(0) == a.n && t->size(1) == a.d, name, " must be [n, dim] on ",
+                Q.device());
+    return t->data_ptr<float>();
+  };
+  a.init_p = start(init, "init"), a.acc_init_p = start(acc_init, "acc_init");
+  a.rows = at::empty({a.n, a.d}, Q.options()), a.acc = at::empty({a.n, a.d}, Q.options());
+  a.loss = at::empty({epochs, a.n}, Q.options());
+  a.first_p = a.T ? a.first.data_ptr<int32_t>() : nullptr;
+  a.neg_p = a.T && epochs ? a.neg.data_ptr<int32_t>() : nullptr;
+  a.rows_p = a.n ? a.rows.data_ptr<float>() : nullptr;
+  a.acc_p = a.n ? a.acc.data_ptr<float>() : nullptr;
+  a.loss_p = a.n && epochs ? a.loss.data_ptr<float>() : nullptr;
+  return a;
+}
+
+// rows, accumulators and per-epoch losses of n new users fitted against a frozen Q
+// (acf_fold_in_users, items range-checked by the call); init / acc_init: [n, d] or None
+std::tuple<at::Tensor, at::Tensor, at::Tensor> fold_in_users(
+    const at::Tensor& Q, const at::Tensor& user_off, const at::Tensor& item_pos, const at::Tensor& item_neg,
+    int64_t epochs, int64_t batch, const c10::optional<at::Tensor>& init, const c10::optional<at::Tensor>& acc_init,
+    double lr, double eps, double reg, double reg_adv, bool adver, double clip_lo, double clip_hi) {
+  need_table(Q, "embedding_Q", Q);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
+  const FoldArgs a = fold_args(Q, user_off, "user_off", item_pos, "item_pos", item_neg, epochs, batch, init, acc_init);
+  const acf_apr_hparams hp = hparams(lr, eps, reg, reg_adv, adver, clip_lo, clip_hi);
+  ok(acf_fold_in_users(Q.data_ptr<float>(), Q.size(0), (int32_t)a.d, user_off.data_ptr<int64_t>(), a.n, a.first_p,
+                       a.neg_p, a.T, (int32_t)epochs, (int32_t)batch, &hp, a.init_p, a.acc_init_p, a.rows_p, a.acc_p,
+                       a.loss_p, 1, stream_of(Q)),
+     "acf_fold_in_users");
+  return {a.rows, a.acc, a.loss};
+}
+
+// rows, accumulators and per-epoch losses of n new items fitted against frozen P and Q
+// (acf_fold_in_items, users and negatives range-checked by the call); init / acc_init: [n, d] or None
+std::tuple<at::Tensor, at::Tensor, at::Tensor> fold_in_items(
+    const at::Tensor& P, const at::Tensor& Q, const at::Tensor& item_off, const at::Tensor& user_pos,
+    const at::Tensor& item_neg, int64_t epochs, int64_t batch, const c10::optional<at::Tensor>& init,
+    const c10::optional<at::Tensor>& acc_init, double lr, double eps, double reg, double reg_adv, bool adver,
+    double clip_lo, double clip_hi) {
+  need_table(P, "embedding_P", P);
+  need_table(Q, "embedding_Q", P);
+  TORCH_CHECK(P.size(1) == Q.size(1), "embedding_P and embedding_Q differ in dim: ", P.size(1), " and ", Q.size(1));
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
+  const FoldArgs a = fold_args(Q, item_off, "item_off", user_pos, "user_pos", item_neg, epochs, batch, init, acc_init);
+  const acf_apr_hparams hp = hparams(lr, eps, reg, reg_adv, adver, clip_lo, clip_hi);
+  ok(acf_fold_in_items(P.data_ptr<float>(), P.size(0), Q.data_ptr<float>(), Q.size(0), (int32_t)a.d,
+                       item_off.data_ptr<int64_t>(), a.n, a.first_p, a.neg_p, a.T, (int32_t)epochs, (int32_t)batch, &hp,
+                       a.init_p, a.acc_init_p, a.rows_p, a.acc_p, a.loss_p, 1, stream_of(Q)),
+     "acf_fold_in_items");
+  return {a.rows, a.acc, a.loss};
 }
 
 // positions of every test item of every entry's list (acf_eval_positions_multi).  users and

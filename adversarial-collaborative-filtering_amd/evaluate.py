@@ -449,18 +449,27 @@ def radius_curve(eps, K, eps_list):
 
 
 # ---- fold-in: rows for users who were not in the training set -----------------
-class FoldIn:
+class _Folded:
+    """A fold-in's result: keys, the CSR (offsets, list) of the sorted unique
+    lists, the fitted rows, their Adagrad accumulators and the losses, in that
+    order; a side names the CSR and the rows (_names)."""
+    _names = ()
+
+    def __init__(self, keys, off, first, rows, acc, loss):
+        self.keys, self.acc, self.loss = keys, acc, loss
+        for name, value in zip(self._names, (off, first, rows)):
+            setattr(self, name, value)
+
+    def __len__(self):
+        return len(self.keys)
+
+
+class FoldIn(_Folded):
     """What fold_in returns: keys (the dict's keys ascending, or 0..n-1 for a
     list of lists), the CSR (user_off int64 [n + 1], item_pos int32 [T], numpy)
     of the sorted unique lists, and the device tensors P [n, d], acc [n, d] (the
     fitted rows and their Adagrad accumulators) and loss [epochs, n]."""
-
-    def __init__(self, keys, user_off, item_pos, P, acc, loss):
-        self.keys, self.user_off, self.item_pos = keys, user_off, item_pos
-        self.P, self.acc, self.loss = P, acc, loss
-
-    def __len__(self):
-        return len(self.keys)
+    _names = ("user_off", "item_pos", "P")
 
 
 def fold_lists(lists):
@@ -491,6 +500,18 @@ def fold_lists(lists):
     return keys, off, items.astype(np.int32)
 
 
+def _redraw(rng, neg, own, keys, num_items: int):
+    """Redraw neg[k], uniform on [0, num_items), while own[k] * num_items + neg[k]
+    is one of `keys` (sorted, not empty unless neg is): in place, one rng.randint
+    per round over what is still refused (APR.py:76-77)."""
+    todo = np.arange(len(neg))
+    while len(todo):
+        k = own[todo] * num_items + neg[todo]
+        at = np.minimum(np.searchsorted(keys, k), len(keys) - 1)
+        todo = todo[keys[at] == k]
+        neg[todo] = rng.randint(num_items, size=len(todo))
+
+
 def fold_negatives(user_off, item_pos, num_items: int, epochs: int, seed: int = 0):
     """item_neg int32 [epochs, T]: per positive and epoch one item uniform on
     [0, num_items), redrawn while it is in that user's own list (APR.py:76-77).
@@ -509,31 +530,32 @@ def fold_negatives(user_off, item_pos, num_items: int, epochs: int, seed: int = 
     owner = np.repeat(np.arange(len(lens), dtype=np.int64), lens)
     keys = owner * num_items + items  # ascending: owners ascend, lists are sorted
     rng = np.random.RandomState(int(seed) & 0xFFFFFFFF)
-    own = np.tile(owner, epochs)
     neg = rng.randint(num_items, size=epochs * T).astype(np.int64)
-    todo = np.arange(epochs * T)
-    while len(todo):
-        k = own[todo] * num_items + neg[todo]
-        at = np.minimum(np.searchsorted(keys, k), T - 1)
-        todo = todo[keys[at] == k]
-        neg[todo] = rng.randint(num_items, size=len(todo))
+    _redraw(rng, neg, np.tile(owner, epochs), keys, num_items)
     return neg.astype(np.int32).reshape(epochs, T)
 
 
+def _fold_hparams(m):
+    """The default hparams of a fold-in.  A model's (anything with hparams())
+    takes its lr, eps, reg, reg_adv and adver as they are: a plain BPR model
+    (adver=0) folds in WITHOUT the adversarial term.  The rest is not carried
+    over: the delta is always the gradient one (a model trained with adv="random"
+    folds in with adv="grad", the only delta fold-in takes) and the clip bounds
+    are the graph's constants (-80, 1e8).  Bare tables: StepHParams(adver=1)."""
+    if not hasattr(m, "hparams"):
+        return ops.StepHParams(adver=1)
+    hp = m.hparams()
+    return ops.StepHParams(lr=hp.lr, eps=hp.eps, reg=hp.reg, reg_adv=hp.reg_adv, adver=hp.adver)
+
+
 def _fold_target(model_or_tables):
-    """(Q, num_items, default hparams) of an MF-like model, a (P, Q) pair or Q.
-    A model's default takes its lr, eps, reg, reg_adv and adver as they are: a
-    plain BPR model (adver=0) folds in WITHOUT the adversarial term.  The rest is
-    not carried over: the delta is always the gradient one (a model trained with
-    adv="random" folds in with adv="grad", the only delta fold-in takes) and the
-    clip bounds are the graph's constants (-80, 1e8)."""
+    """(Q, num_items, default hparams: _fold_hparams) of an MF-like model, a
+    (P, Q) pair or Q."""
     m = model_or_tables
     if hasattr(m, "embedding_Q"):
-        hp = m.hparams()
-        hp = ops.StepHParams(lr=hp.lr, eps=hp.eps, reg=hp.reg, reg_adv=hp.reg_adv, adver=hp.adver)
-        return m.embedding_Q, min(int(m.num_items), m.embedding_Q.shape[0]), hp
+        return m.embedding_Q, min(int(m.num_items), m.embedding_Q.shape[0]), _fold_hparams(m)
     Q = m[1] if isinstance(m, (tuple, list)) else m
-    return Q, Q.shape[0], ops.StepHParams(adver=1)
+    return Q, Q.shape[0], _fold_hparams(m)
 
 
 def fold_in(model_or_tables, lists, epochs: int = 20, batch: int = 512, seed: int = 0, hp=None, init=None,
@@ -579,18 +601,12 @@ def recommend_new(model_or_tables, lists, k: int, **fold_args):
 
 
 # ---- fold-in: rows for items that were not in the training set ----------------
-class FoldInItems:
+class FoldInItems(_Folded):
     """What fold_in_items returns: keys (the dict's keys ascending, or 0..n-1 for
     a list of lists), the CSR (item_off int64 [n + 1], user_pos int32 [T], numpy)
     of the sorted unique user lists, and the device tensors Q [n, d], acc [n, d]
     (the fitted rows and their Adagrad accumulators) and loss [epochs, n]."""
-
-    def __init__(self, keys, item_off, user_pos, Q, acc, loss):
-        self.keys, self.item_off, self.user_pos = keys, item_off, user_pos
-        self.Q, self.acc, self.loss = Q, acc, loss
-
-    def __len__(self):
-        return len(self.keys)
+    _names = ("item_off", "user_pos", "Q")
 
 
 def fold_item_negatives(item_off, user_pos, num_items: int, epochs: int, seed: int = 0, excl_off=None, excl=None):
@@ -630,27 +646,14 @@ def fold_item_negatives(item_off, user_pos, num_items: int, epochs: int, seed: i
         raise ValueError("a user's train list holds every item: no admissible negative")
     if len(keys) == 0:
         return neg.astype(np.int32).reshape(epochs, T)
-    own = np.tile(users, epochs)
-    todo = np.arange(epochs * T)
-    while len(todo):
-        k = own[todo] * num_items + neg[todo]
-        at = np.minimum(np.searchsorted(keys, k), len(keys) - 1)
-        todo = todo[keys[at] == k]
-        neg[todo] = rng.randint(num_items, size=len(todo))
+    _redraw(rng, neg, np.tile(users, epochs), keys, num_items)
     return neg.astype(np.int32).reshape(epochs, T)
 
 
 def _fold_items_target(model_or_tables):
     """(P, Q, num_users, num_items, default hparams) of an MF-like model or a
-    (P, Q) pair; the defaults as _fold_target's."""
-    m = model_or_tables
-    P, Q, n_users, n_items = _neighbor_tables(m)
-    if hasattr(m, "hparams"):
-        hp = m.hparams()
-        hp = ops.StepHParams(lr=hp.lr, eps=hp.eps, reg=hp.reg, reg_adv=hp.reg_adv, adver=hp.adver)
-    else:
-        hp = ops.StepHParams(adver=1)
-    return P, Q, n_users, n_items, hp
+    (P, Q) pair; the defaults are _fold_hparams'."""
+    return (*_neighbor_tables(model_or_tables), _fold_hparams(model_or_tables))
 
 
 def fold_in_items(model_or_tables, lists, epochs: int = 20, batch: int = 512, seed: int = 0, hp=None, init=None,

@@ -1259,21 +1259,21 @@ def adv_apply(W, N, eps: float, want_delta: bool = False):
 FOLD_MAX_BATCH = 512  # ACF_FOLD_MAX_BATCH
 
 
-def _fold_csr(user_off, n_items: int):
-    """user_off as a host int64 array after the CSR checks (ValueError)."""
+def _fold_csr(off, n_entries: int, off_name: str, list_name: str):
+    """The CSR offsets `off` as a host int64 array after the CSR checks (ValueError)."""
     import numpy as np
-    off = user_off.detach().cpu().numpy() if isinstance(user_off, torch.Tensor) else np.asarray(user_off)
+    off = off.detach().cpu().numpy() if isinstance(off, torch.Tensor) else np.asarray(off)
     if off.ndim != 1 or off.size < 1:
-        raise ValueError(f"user_off must be 1-D with n + 1 entries, got shape {off.shape}")
+        raise ValueError(f"{off_name} must be 1-D with n + 1 entries, got shape {off.shape}")
     if off.dtype.kind not in "iu":
-        raise ValueError(f"user_off must be an integer array, got {off.dtype}")
+        raise ValueError(f"{off_name} must be an integer array, got {off.dtype}")
     off = off.astype(np.int64)
     if off[0] != 0:
-        raise ValueError(f"user_off[0] must be 0, got {off[0]}")
+        raise ValueError(f"{off_name}[0] must be 0, got {off[0]}")
     if (np.diff(off) < 0).any():
-        raise ValueError("user_off must be non-decreasing")
-    if off[-1] != n_items:
-        raise ValueError(f"user_off[-1] must be len(item_pos) = {n_items}, got {off[-1]}")
+        raise ValueError(f"{off_name} must be non-decreasing")
+    if off[-1] != n_entries:
+        raise ValueError(f"{off_name}[-1] must be len({list_name}) = {n_entries}, got {off[-1]}")
     return off
 
 
@@ -1297,6 +1297,60 @@ def _fold_table(t, name: str, device, shape=None) -> int:
     return ptr
 
 
+def _fold_in(entry: str, tables, off_name: str, off_in, list_name: str, first, item_neg, hp, epochs, batch, init,
+             acc_init, check):
+    """fold_in_users / fold_in_items behind their argument names: the checks, in
+    one order, and the call.  tables: [(tensor, name)], the frozen tables in the
+    entry point's order; the CSR (off_in, first) indexes rows of the first."""
+    if not isinstance(hp, StepHParams):
+        raise ValueError(f"hp must be a StepHParams, got {type(hp).__name__}")
+    if hp.adv != "grad" or hp.zero_delta:
+        raise ValueError("fold-in takes only the gradient delta: adv='grad' and zero_delta=0 "
+                         f"(got adv={hp.adv!r}, zero_delta={hp.zero_delta})")
+    if isinstance(batch, bool) or not isinstance(batch, int) or not 1 <= batch <= FOLD_MAX_BATCH:
+        raise ValueError(f"batch must be an int in [1, {FOLD_MAX_BATCH}], got {batch!r}")
+    if isinstance(epochs, bool) or not isinstance(epochs, int) or epochs < 0:
+        raise ValueError(f"epochs must be an int >= 0, got {epochs!r}")
+    T = len(first)
+    off = _fold_csr(off_in, T, off_name, list_name)
+    n = off.size - 1
+    if tuple(getattr(item_neg, "shape", ())) != (epochs, T):
+        raise ValueError(f"item_neg must have shape (epochs, len({list_name})) = {(epochs, T)}, "
+                         f"got {tuple(getattr(item_neg, 'shape', ()))}")
+    (t0, name0), rest = tables[0], tables[1:]
+    _fold_table(t0, name0, None)
+    dev, d = t0.device, t0.shape[1]
+    for t, name in rest:
+        _fold_table(t, name, dev)
+        if t.shape[1] != d:
+            raise ValueError(f"{name0} and {name} differ in dim: {d} and {t.shape[1]}")
+    if d < 4 or d > 1024 or d % 4:
+        raise ValueError(f"dim must be a multiple of 4 in [4, 1024], got {d}")
+    rows = _fold_items(first, list_name, dev, (T,))
+    ineg = _fold_items(item_neg, "item_neg", dev, (epochs, T))
+    if init is not None:
+        _fold_table(init, "init", dev, (n, d))
+    if acc_init is not None:
+        _fold_table(acc_init, "acc_init", dev, (n, d))
+    offd = (off_in if isinstance(off_in, torch.Tensor) and off_in.dtype == torch.int64
+            and off_in.device == dev and off_in.is_contiguous()
+            else torch.as_tensor(off).to(dev))
+    settle_tables()
+    W_new = torch.empty((n, d), dtype=torch.float32, device=dev)
+    acc_new = torch.empty((n, d), dtype=torch.float32, device=dev)
+    loss = torch.empty((epochs, n), dtype=torch.float32, device=dev)
+    if n == 0:
+        return W_new, acc_new, loss
+    c = hp.to_c()
+    with _on(dev):
+        call(entry, *[x for t, _ in tables for x in (t.data_ptr(), t.shape[0])], d, offd.data_ptr(), n,
+             rows.data_ptr() if T else None, ineg.data_ptr() if T and epochs else None, T, epochs, batch,
+             ctypes.byref(c), init.data_ptr() if init is not None else None,
+             acc_init.data_ptr() if acc_init is not None else None, W_new.data_ptr(), acc_new.data_ptr(),
+             loss.data_ptr() if epochs else None, int(bool(check)), _stream_ptr(dev))
+    return W_new, acc_new, loss
+
+
 def fold_in_users(Q, user_off, item_pos, item_neg, hp: StepHParams, epochs: int, batch: int = FOLD_MAX_BATCH,
                   init=None, acc_init=None, check: bool = True):
     """Rows for n NEW users fitted against the frozen item table Q, on the GPU
@@ -1313,49 +1367,8 @@ def fold_in_users(Q, user_off, item_pos, item_neg, hp: StepHParams, epochs: int,
     A user's outputs depend on that user's inputs only, bit for bit, and equal
     inputs give equal bits.  Bad arguments raise ValueError before any native
     call; with check, an item outside Q raises NativeIndexError."""
-    if not isinstance(hp, StepHParams):
-        raise ValueError(f"hp must be a StepHParams, got {type(hp).__name__}")
-    if hp.adv != "grad" or hp.zero_delta:
-        raise ValueError("fold-in takes only the gradient delta: adv='grad' and zero_delta=0 "
-                         f"(got adv={hp.adv!r}, zero_delta={hp.zero_delta})")
-    if isinstance(batch, bool) or not isinstance(batch, int) or not 1 <= batch <= FOLD_MAX_BATCH:
-        raise ValueError(f"batch must be an int in [1, {FOLD_MAX_BATCH}], got {batch!r}")
-    if isinstance(epochs, bool) or not isinstance(epochs, int) or epochs < 0:
-        raise ValueError(f"epochs must be an int >= 0, got {epochs!r}")
-    T = len(item_pos)
-    off = _fold_csr(user_off, T)
-    n = off.size - 1
-    if tuple(getattr(item_neg, "shape", ())) != (epochs, T):
-        raise ValueError(f"item_neg must have shape (epochs, len(item_pos)) = {(epochs, T)}, "
-                         f"got {tuple(getattr(item_neg, 'shape', ()))}")
-    _fold_table(Q, "embedding_Q", None)
-    dev = Q.device
-    I1, d = Q.shape
-    if d < 4 or d > 1024 or d % 4:
-        raise ValueError(f"dim must be a multiple of 4 in [4, 1024], got {d}")
-    ip = _fold_items(item_pos, "item_pos", dev, (T,))
-    ineg = _fold_items(item_neg, "item_neg", dev, (epochs, T))
-    if init is not None:
-        _fold_table(init, "init", dev, (n, d))
-    if acc_init is not None:
-        _fold_table(acc_init, "acc_init", dev, (n, d))
-    offd = (user_off if isinstance(user_off, torch.Tensor) and user_off.dtype == torch.int64
-            and user_off.device == dev and user_off.is_contiguous()
-            else torch.as_tensor(off).to(dev))
-    settle_tables()
-    P_new = torch.empty((n, d), dtype=torch.float32, device=dev)
-    acc_new = torch.empty((n, d), dtype=torch.float32, device=dev)
-    loss = torch.empty((epochs, n), dtype=torch.float32, device=dev)
-    if n == 0:
-        return P_new, acc_new, loss
-    c = hp.to_c()
-    with _on(dev):
-        call("acf_fold_in_users", Q.data_ptr(), I1, d, offd.data_ptr(), n, ip.data_ptr() if T else None,
-             ineg.data_ptr() if T and epochs else None, T, epochs, batch, ctypes.byref(c),
-             init.data_ptr() if init is not None else None, acc_init.data_ptr() if acc_init is not None else None,
-             P_new.data_ptr(), acc_new.data_ptr(), loss.data_ptr() if epochs else None, int(bool(check)),
-             _stream_ptr(dev))
-    return P_new, acc_new, loss
+    return _fold_in("acf_fold_in_users", [(Q, "embedding_Q")], "user_off", user_off, "item_pos", item_pos, item_neg,
+                    hp, epochs, batch, init, acc_init, check)
 
 
 def fold_in_items(P, Q, item_off, user_pos, item_neg, hp: StepHParams, epochs: int, batch: int = FOLD_MAX_BATCH,
@@ -1376,56 +1389,8 @@ def fold_in_items(P, Q, item_off, user_pos, item_neg, hp: StepHParams, epochs: i
     that item's inputs only, bit for bit, and equal inputs give equal bits.  Bad
     arguments raise ValueError before any native call; with check, a user outside
     P or a negative outside Q raises NativeIndexError."""
-    if not isinstance(hp, StepHParams):
-        raise ValueError(f"hp must be a StepHParams, got {type(hp).__name__}")
-    if hp.adv != "grad" or hp.zero_delta:
-        raise ValueError("fold-in takes only the gradient delta: adv='grad' and zero_delta=0 "
-                         f"(got adv={hp.adv!r}, zero_delta={hp.zero_delta})")
-    if isinstance(batch, bool) or not isinstance(batch, int) or not 1 <= batch <= FOLD_MAX_BATCH:
-        raise ValueError(f"batch must be an int in [1, {FOLD_MAX_BATCH}], got {batch!r}")
-    if isinstance(epochs, bool) or not isinstance(epochs, int) or epochs < 0:
-        raise ValueError(f"epochs must be an int >= 0, got {epochs!r}")
-    T = len(user_pos)
-    try:
-        off = _fold_csr(item_off, T)
-    except ValueError as e:  # the helper speaks of the user call's arguments
-        raise ValueError(str(e).replace("user_off", "item_off").replace("item_pos", "user_pos")) from None
-    n = off.size - 1
-    if tuple(getattr(item_neg, "shape", ())) != (epochs, T):
-        raise ValueError(f"item_neg must have shape (epochs, len(user_pos)) = {(epochs, T)}, "
-                         f"got {tuple(getattr(item_neg, 'shape', ()))}")
-    _fold_table(P, "embedding_P", None)
-    dev = P.device
-    _fold_table(Q, "embedding_Q", dev)
-    U1, d = P.shape
-    I1 = Q.shape[0]
-    if Q.shape[1] != d:
-        raise ValueError(f"embedding_P and embedding_Q differ in dim: {d} and {Q.shape[1]}")
-    if d < 4 or d > 1024 or d % 4:
-        raise ValueError(f"dim must be a multiple of 4 in [4, 1024], got {d}")
-    up = _fold_items(user_pos, "user_pos", dev, (T,))
-    ineg = _fold_items(item_neg, "item_neg", dev, (epochs, T))
-    if init is not None:
-        _fold_table(init, "init", dev, (n, d))
-    if acc_init is not None:
-        _fold_table(acc_init, "acc_init", dev, (n, d))
-    offd = (item_off if isinstance(item_off, torch.Tensor) and item_off.dtype == torch.int64
-            and item_off.device == dev and item_off.is_contiguous()
-            else torch.as_tensor(off).to(dev))
-    settle_tables()
-    Q_new = torch.empty((n, d), dtype=torch.float32, device=dev)
-    acc_new = torch.empty((n, d), dtype=torch.float32, device=dev)
-    loss = torch.empty((epochs, n), dtype=torch.float32, device=dev)
-    if n == 0:
-        return Q_new, acc_new, loss
-    c = hp.to_c()
-    with _on(dev):
-        call("acf_fold_in_items", P.data_ptr(), U1, Q.data_ptr(), I1, d, offd.data_ptr(), n,
-             up.data_ptr() if T else None, ineg.data_ptr() if T and epochs else None, T, epochs, batch,
-             ctypes.byref(c), init.data_ptr() if init is not None else None,
-             acc_init.data_ptr() if acc_init is not None else None, Q_new.data_ptr(), acc_new.data_ptr(),
-             loss.data_ptr() if epochs else None, int(bool(check)), _stream_ptr(dev))
-    return Q_new, acc_new, loss
+    return _fold_in("acf_fold_in_items", [(P, "embedding_P"), (Q, "embedding_Q")], "item_off", item_off, "user_pos",
+                    user_pos, item_neg, hp, epochs, batch, init, acc_init, check)
 
 
 def eval_positions_list(P, Q, users, test_items, cand_off, cand_items):
