@@ -11,7 +11,7 @@
 //   NBR_DOT  s = seq_dot(a, b)
 //   NBR_COS  den = sqrtf(seq_dot(a, a)) * sqrtf(seq_dot(b, b));
 //            den > 0 ? (s / den) + 0.0f : +0.0f
-//   NBR_EUC  0.0f - D2, D2 = k_evw_sweep's chain: the sum over k ascending from
+//   NBR_EUC  0.0f - D2, D2 = k_cert_sweep's chain: the sum over k ascending from
 //            +0.0 of round((a[k] - b[k])^2)
 // every operation fp32 and rounded on its own (-ffp-contract=off), the square
 // roots and the division correctly rounded.

@@ -23,8 +23,8 @@
 #include "acf_neighbors.h"  // nearest-neighbour lists (k_nbr_*): DESIGN.md §4h
 #include "acf_adv.h"   // whole-stream adversarial direction (k_adv_*): DESIGN.md §4c
 #include "acf_eval_multi.h"  // multi-item evaluation and rank metrics (k_evx_*): DESIGN.md §4f
-#include "acf_eval_worst.h"  // certified worst-case positions (k_evw_*): DESIGN.md §4g
-#include "acf_eval_radius.h"  // certified radius, the K weakest candidates (k_evr_*): DESIGN.md §4j
+#include "acf_eval_worst.h"  // the certified margin sweep (k_cert_sweep), worst-case positions: DESIGN.md §4g
+#include "acf_eval_radius.h"  // certified radius, the K weakest candidates (its selecting sink): DESIGN.md §4j
 
 // ---- the host frame's shared pieces --------------------------------------------
 static int check_kernel(int32_t kernel) {
@@ -358,10 +358,76 @@ extern "C" int acf_eval_rank_metrics(const int32_t* positions, const int64_t* te
   return ACF_OK;
 }
 
-// ---- certified worst-case positions (acf_eval_worst.h) -------------------------
-static int evw_check(int32_t n_users, int32_t num_cand, int32_t n_eps) {
+// ---- the certified evaluations' host frame (k_cert_sweep: acf_eval_worst.h, acf_eval_radius.h) ----
+static int cert_check(int32_t n_users, int32_t num_cand) {
   ACF_CHECK(n_users >= 0, ACF_E_INVALID, "negative count");
   ACF_CHECK(num_cand >= 1, ACF_E_INVALID, "num_candidates must be >= 1, got %d", num_cand);
+  return ACF_OK;
+}
+
+// The entries of a call, as both entry points take them.
+struct CertCall {
+  const float *P, *Q;
+  int64_t U1, I1;
+  int32_t d;
+  const int32_t *users, *tests;
+  int32_t n_users, num_cand;
+  const int64_t* excl_off;
+  const int32_t* excl;
+  int32_t side;
+  void* workspace;
+  size_t workspace_bytes;
+  int32_t check;
+  void* stream;
+};
+
+// Dynamic LDS: the sink's keys, then the rows.  A sink with keys passes the 64 KB default (side user at d = 512: 64 KB
+// + the static part), so each of its instances opts in to its largest, as topk_lds_optin does; UB = 8 serves d <= 512,
+// UB = 4 d <= 1024.
+template <int UB, bool USER, template <int> class SINK>
+static int launch_cert(const CertCall& c, int wper, int S, const typename SINK<UB>::Args& a, int32_t* err,
+                       hipStream_t s) {
+  constexpr size_t keys = SINK<UB>::KEYS * sizeof(uint64_t), row = (USER ? 2 : 1) * UB * sizeof(float);
+  if (keys > 0)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cert_sweep<UB, USER, SINK<UB>>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(keys + row * (UB == EVW_UB ? EVW_D_SPLIT : 1024))));
+  const dim3 grid((unsigned)((c.n_users + UB - 1) / UB), (unsigned)S);
+  k_cert_sweep<UB, USER, SINK<UB>><<<grid, 256, keys + row * c.d, s>>>(c.P, c.Q, c.d, c.U1, c.I1, c.users, c.tests,
+                                                                       c.n_users, c.num_cand, c.excl_off, c.excl, wper,
+                                                                       a, err);
+  HIP_TRY(hipGetLastError());
+  return ACF_OK;
+}
+
+// What both entry points do around their sweep.  The caller has checked the arguments of its own (cert_check among
+// them: `need` is computed from them) and says whether its outputs are there; own(launch, err, s) cuts its strips,
+// lays out its workspace behind the error word, calls launch(c, wper, S, its sink's arguments, err, s) and queues its
+// tail.
+template <template <int> class SINK, class OWN>
+static int cert_run(const CertCall& c, bool outputs, size_t need, int align, OWN own) {
+  ACF_RET(check_dim(c.d));
+  ACF_CHECK(c.side == 0 || c.side == 1, ACF_E_INVALID, "side must be 0 (user) or 1 (item), got %d", c.side);
+  ACF_CHECK(c.U1 > 0 && c.I1 > 0, ACF_E_INVALID, "empty table");
+  ACF_CHECK(c.num_cand <= c.I1, ACF_E_INVALID, "num_candidates %d > item rows", c.num_cand);
+  ACF_CHECK(c.P && c.Q && c.users && c.tests && outputs && c.workspace, ACF_E_INVALID, "NULL argument");
+  ACF_RET(check_excl_pair(c.excl_off, c.excl));
+  ACF_RET(check_workspace(c.workspace, c.workspace_bytes, need, align));
+  if (c.n_users == 0) return ACF_OK;
+  hipStream_t s = static_cast<hipStream_t>(c.stream);
+  int32_t* err = static_cast<int32_t*>(c.workspace);
+  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+  const bool wide = c.d <= EVW_D_SPLIT;  // 8 entries per workgroup, 4 above: the rows stay within 32 KB of LDS
+  const auto launch = c.side == 0 ? (wide ? &launch_cert<EVW_UB, true, SINK> : &launch_cert<EVW_UB / 2, true, SINK>)
+                                  : (wide ? &launch_cert<EVW_UB, false, SINK> : &launch_cert<EVW_UB / 2, false, SINK>);
+  ACF_RET(own(launch, err, s));
+  if (c.check) ACF_RET(check_eval_range(err, s));
+  return ACF_OK;
+}
+
+// ---- certified worst-case positions: the counting sink (acf_eval_worst.h) ---------
+static int evw_check(int32_t n_users, int32_t num_cand, int32_t n_eps) {
+  ACF_RET(cert_check(n_users, num_cand));
   ACF_CHECK(n_eps >= 1 && n_eps <= EVW_MAX_EPS, ACF_E_INVALID, "n_eps %d outside [1, %d]", n_eps, EVW_MAX_EPS);
   return ACF_OK;
 }
@@ -373,24 +439,12 @@ extern "C" int acf_eval_positions_worst_workspace(int32_t n_users, int32_t num_c
   return ACF_OK;
 }
 
-template <int UB, bool USER>
-static void launch_evw(const float* P, const float* Q, int d, int64_t U1, int64_t I1, const int32_t* users,
-                       const int32_t* tests, int n_users, int num_cand, const int64_t* excl_off, const int32_t* excl,
-                       const EvwEps& eps, int wper, int S, int32_t* out, int32_t* err, hipStream_t s) {
-  const dim3 grid((unsigned)((n_users + UB - 1) / UB), (unsigned)S);
-  const size_t lds = (size_t)(USER ? 2 : 1) * UB * d * sizeof(float);
-  k_evw_sweep<UB, USER><<<grid, 256, lds, s>>>(P, Q, d, U1, I1, users, tests, n_users, num_cand, excl_off, excl, eps,
-                                               wper, out, err);
-}
-
 extern "C" int acf_eval_positions_worst(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
                                         const int32_t* users, const int32_t* test_items, int32_t n_users,
                                         int32_t num_cand, const int64_t* excl_off, const int32_t* excl,
                                         const float* eps, int32_t n_eps, int32_t side, int32_t* worst,
                                         void* workspace, size_t workspace_bytes, int32_t check, void* stream_) {
-  ACF_RET(check_dim(d));
   ACF_RET(evw_check(n_users, num_cand, n_eps));
-  ACF_CHECK(side == 0 || side == 1, ACF_E_INVALID, "side must be 0 (user) or 1 (item), got %d", side);
   ACF_CHECK(eps, ACF_E_INVALID, "NULL argument");
   EvwEps ev{};
   ev.n = n_eps;
@@ -399,33 +453,21 @@ extern "C" int acf_eval_positions_worst(const float* P, const float* Q, int64_t 
     ACF_CHECK(std::isfinite(v) && v >= 0.f, ACF_E_INVALID, "eps must be finite and >= 0, got %g", (double)v);
     ev.e[e] = v;
   }
-  ACF_CHECK(U1 > 0 && I1 > 0, ACF_E_INVALID, "empty table");
-  ACF_CHECK(num_cand <= I1, ACF_E_INVALID, "num_candidates %d > item rows", num_cand);
-  ACF_CHECK(P && Q && users && test_items && worst && workspace, ACF_E_INVALID, "NULL argument");
-  ACF_RET(check_excl_pair(excl_off, excl));
-  ACF_RET(check_workspace(workspace, workspace_bytes, evw_workspace(n_users, num_cand, n_eps), 4));
-  if (n_users == 0) return ACF_OK;
-  int wper = 0, S = 0;
-  evw_strips(n_users, num_cand, n_eps, &wper, &S);
-  hipStream_t s = static_cast<hipStream_t>(stream_);
-  int32_t* err = static_cast<int32_t*>(workspace);
-  int32_t* part = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + EVW_WS_HEAD);
-  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
-  const bool wide = d <= EVW_D_SPLIT;  // 8 entries per workgroup, 4 above: the rows stay within 32 KB of LDS
-  const auto launch = side == 0 ? (wide ? &launch_evw<EVW_UB, true> : &launch_evw<EVW_UB / 2, true>)
-                                : (wide ? &launch_evw<EVW_UB, false> : &launch_evw<EVW_UB / 2, false>);
-  launch(P, Q, d, U1, I1, users, test_items, n_users, num_cand, excl_off, excl, ev, wper, S,
-         strip_target(part, S, worst), err, s);
-  HIP_TRY(hipGetLastError());
-  ACF_RET(sum_strips(part, S, (int64_t)n_eps * n_users, worst, s));
-  if (check) ACF_RET(check_eval_range(err, s));
-  return ACF_OK;
+  const CertCall c{P,        Q,    U1,   I1,        d,               users, test_items, n_users,
+                   num_cand, excl_off, excl, side, workspace, workspace_bytes, check, stream_};
+  return cert_run<CertCount>(c, worst != nullptr, evw_workspace(n_users, num_cand, n_eps), 4,
+                             [&](auto launch, int32_t* err, hipStream_t s) -> int {
+    int wper = 0, S = 0;
+    evw_strips(n_users, num_cand, n_eps, &wper, &S);
+    int32_t* part = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + EVW_WS_HEAD);
+    ACF_RET(launch(c, wper, S, CertCountArgs{ev, strip_target(part, S, worst)}, err, s));
+    return sum_strips(part, S, (int64_t)n_eps * n_users, worst, s);
+  });
 }
 
-// ---- certified radius (acf_eval_radius.h) ---------------------------------------
+// ---- certified radius: the selecting sink (acf_eval_radius.h) ---------------------
 static int evr_check(int32_t n_users, int32_t num_cand, int32_t k) {
-  ACF_CHECK(n_users >= 0, ACF_E_INVALID, "negative count");
-  ACF_CHECK(num_cand >= 1, ACF_E_INVALID, "num_candidates must be >= 1, got %d", num_cand);
+  ACF_RET(cert_check(n_users, num_cand));
   ACF_CHECK(k >= 1 && k <= TOPK_MAX_K, ACF_E_INVALID, "k must be in [1, %d], got %d", TOPK_MAX_K, k);
   return ACF_OK;
 }
@@ -437,52 +479,26 @@ extern "C" int acf_eval_radius_workspace(int32_t n_users, int32_t num_cand, int3
   return ACF_OK;
 }
 
-// The keys and the rows together pass the 64 KB default of dynamic LDS (side user at d = 512: 64 KB + the static
-// part), so every instance opts in to its largest, as topk_lds_optin does; UB = 8 serves d <= 512, UB = 4 d <= 1024.
-template <int UB, bool USER>
-static int launch_evr(const float* P, const float* Q, int d, int64_t U1, int64_t I1, const int32_t* users,
-                      const int32_t* tests, int n_users, int num_cand, const int64_t* excl_off, const int32_t* excl,
-                      int K, int wper, int S, uint64_t* lists, int32_t* err, hipStream_t s) {
-  constexpr int D_MAX = UB == EVW_UB ? EVW_D_SPLIT : 1024;
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_evr_sweep<UB, USER>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)evr_lds(UB, USER, D_MAX)));
-  const dim3 grid((unsigned)((n_users + UB - 1) / UB), (unsigned)S);
-  k_evr_sweep<UB, USER><<<grid, 256, evr_lds(UB, USER, d), s>>>(P, Q, d, U1, I1, users, tests, n_users, num_cand,
-                                                                excl_off, excl, K, wper, S, lists, err);
-  HIP_TRY(hipGetLastError());
-  return ACF_OK;
-}
-
 extern "C" int acf_eval_radius(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
                                const int32_t* users, const int32_t* test_items, int32_t n_users, int32_t num_cand,
                                const int64_t* excl_off, const int32_t* excl, int32_t k, int32_t side, float* eps_out,
                                int32_t* items_out, void* workspace, size_t workspace_bytes, int32_t check,
                                void* stream_) {
-  ACF_RET(check_dim(d));
   ACF_RET(evr_check(n_users, num_cand, k));
-  ACF_CHECK(side == 0 || side == 1, ACF_E_INVALID, "side must be 0 (user) or 1 (item), got %d", side);
-  ACF_CHECK(U1 > 0 && I1 > 0, ACF_E_INVALID, "empty table");
-  ACF_CHECK(num_cand <= I1, ACF_E_INVALID, "num_candidates %d > item rows", num_cand);
-  ACF_CHECK(P && Q && users && test_items && eps_out && items_out && workspace, ACF_E_INVALID, "NULL argument");
-  ACF_RET(check_excl_pair(excl_off, excl));
-  ACF_RET(check_workspace(workspace, workspace_bytes, evr_workspace(n_users, num_cand, k), 8));
-  if (n_users == 0) return ACF_OK;
-  int wper = 0, S = 0;
-  evr_strips(n_users, num_cand, k, &wper, &S);
-  hipStream_t s = static_cast<hipStream_t>(stream_);
-  int32_t* err = static_cast<int32_t*>(workspace);
-  uint64_t* lists = reinterpret_cast<uint64_t*>(static_cast<char*>(workspace) + EVR_WS_HEAD);
-  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
-  const bool wide = d <= EVW_D_SPLIT;  // 8 entries per workgroup, 4 above: the rows stay within 32 KB of LDS
-  const auto launch = side == 0 ? (wide ? &launch_evr<EVW_UB, true> : &launch_evr<EVW_UB / 2, true>)
-                                : (wide ? &launch_evr<EVW_UB, false> : &launch_evr<EVW_UB / 2, false>);
-  ACF_RET(launch(P, Q, d, U1, I1, users, test_items, n_users, num_cand, excl_off, excl, k, wper, S, lists, err, s));
-  k_topk_merge<<<(unsigned)n_users, 256, 0, s>>>(lists, S, k, items_out, eps_out);  // scores: -eps
-  HIP_TRY(hipGetLastError());
-  k_evr_negate<<<grid_for((int64_t)n_users * k), 256, 0, s>>>(eps_out, (int64_t)n_users * k);
-  HIP_TRY(hipGetLastError());
-  if (check) ACF_RET(check_eval_range(err, s));
-  return ACF_OK;
+  const CertCall c{P,        Q,    U1,   I1,        d,               users, test_items, n_users,
+                   num_cand, excl_off, excl, side, workspace, workspace_bytes, check, stream_};
+  return cert_run<CertSelect>(c, eps_out && items_out, evr_workspace(n_users, num_cand, k), 8,
+                              [&](auto launch, int32_t* err, hipStream_t s) -> int {
+    int wper = 0, S = 0;
+    evr_strips(n_users, num_cand, k, &wper, &S);
+    uint64_t* lists = reinterpret_cast<uint64_t*>(static_cast<char*>(workspace) + EVR_WS_HEAD);
+    ACF_RET(launch(c, wper, S, CertSelectArgs{k, S, lists}, err, s));
+    k_topk_merge<<<(unsigned)n_users, 256, 0, s>>>(lists, S, k, items_out, eps_out);  // scores: -eps
+    HIP_TRY(hipGetLastError());
+    k_evr_negate<<<grid_for((int64_t)n_users * k), 256, 0, s>>>(eps_out, (int64_t)n_users * k);
+    HIP_TRY(hipGetLastError());
+    return ACF_OK;
+  });
 }
 
 // ---- whole-stream adversarial direction (acf_adv.h) -------------------------

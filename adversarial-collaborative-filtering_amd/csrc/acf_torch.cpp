@@ -567,16 +567,47 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> rank_metr
   return {per_user, per_free, mean_cut, mean_free, n_scored};
 }
 
+// Entries with one test item each, as eval_positions_worst and eval_radius take them: the tables and the
+// side checked, the tables' device guarded while this lives, users and test items int32 on it and
+// range-checked here, before any gather; empty excl_off and excl_items: no exclusions (NULL, NULL).
+struct CertEntries {
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard;
+  at::Tensor users, tests, excl;
+  int64_t n;
+  int32_t side;
+  const int64_t* eoff;
+  const int32_t* ex;
+
+  CertEntries(const at::Tensor& P, const at::Tensor& Q, const at::Tensor& users_, const at::Tensor& test_items_,
+              int64_t num_candidates, const at::Tensor& excl_off, const at::Tensor& excl_items_,
+              c10::string_view side_) {
+    need_table(P, "embedding_P", P);
+    need_table(Q, "embedding_Q", P);
+    TORCH_CHECK(P.size(1) == Q.size(1), "embedding_P and embedding_Q dims differ");
+    TORCH_CHECK(side_ == "user" || side_ == "item", "side must be \"user\" or \"item\", got \"", side_, "\"");
+    side = side_ == "user" ? 0 : 1;
+    guard.set_device(P.device());
+    users = idx32(users_, "users", P), tests = idx32(test_items_, "test_items", P);
+    excl = idx32(excl_items_, "excl_items", P);
+    n = users.numel();
+    TORCH_CHECK(n < (1ll << 31), "too many users");
+    TORCH_CHECK(tests.numel() == n, "test_items must have one entry per user");
+    TORCH_CHECK(num_candidates >= 1 && num_candidates <= Q.size(0), "num_candidates must lie in [1, item rows]");
+    const bool no_excl = excl_off.numel() == 0 && excl.numel() == 0;
+    if (!no_excl) need_csr(excl_off, "excl_off", n, excl.numel(), P);
+    check_range(users, P.size(0), "users");
+    check_range(tests, Q.size(0), "test_items");
+    if (excl.numel() == 0) excl = at::zeros({1}, users.options());
+    eoff = no_excl ? nullptr : excl_off.data_ptr<int64_t>();
+    ex = no_excl ? nullptr : excl.data_ptr<int32_t>();
+  }
+};
+
 // worst-case positions [n_eps, n] of every entry's test item under an attack of budget eps on the
-// side's rows (acf_eval_positions_worst; side: "user" | "item").  users and test items are
-// range-checked here, before any gather; empty excl_off and excl_items: no exclusions.
-at::Tensor eval_positions_worst(const at::Tensor& P, const at::Tensor& Q, const at::Tensor& users_,
-                                const at::Tensor& test_items_, int64_t num_candidates, const at::Tensor& excl_off,
-                                const at::Tensor& excl_items_, at::ArrayRef<double> eps, c10::string_view side) {
-  need_table(P, "embedding_P", P);
-  need_table(Q, "embedding_Q", P);
-  TORCH_CHECK(P.size(1) == Q.size(1), "embedding_P and embedding_Q dims differ");
-  TORCH_CHECK(side == "user" || side == "item", "side must be \"user\" or \"item\", got \"", side, "\"");
+// side's rows (acf_eval_positions_worst; side: "user" | "item").
+at::Tensor eval_positions_worst(const at::Tensor& P, const at::Tensor& Q, const at::Tensor& users,
+                                const at::Tensor& test_items, int64_t num_candidates, const at::Tensor& excl_off,
+                                const at::Tensor& excl_items, at::ArrayRef<double> eps, c10::string_view side) {
   const int64_t ne = (int64_t)eps.size();
   TORCH_CHECK(ne >= 1 && ne <= 8, "1 to 8 eps, got ", ne);
   float ev[8] = {0};
@@ -584,65 +615,37 @@ at::Tensor eval_positions_worst(const at::Tensor& P, const at::Tensor& Q, const 
     ev[e] = (float)eps[e];
     TORCH_CHECK(std::isfinite(ev[e]) && ev[e] >= 0.f, "eps must be finite and >= 0, got ", eps[e]);
   }
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(P.device());
-  at::Tensor users = idx32(users_, "users", P), tests = idx32(test_items_, "test_items", P);
-  at::Tensor excl = idx32(excl_items_, "excl_items", P);
-  const int64_t n = users.numel();
-  TORCH_CHECK(n < (1ll << 31), "too many users");
-  TORCH_CHECK(tests.numel() == n, "test_items must have one entry per user");
-  TORCH_CHECK(num_candidates >= 1 && num_candidates <= Q.size(0), "num_candidates must lie in [1, item rows]");
-  const bool no_excl = excl_off.numel() == 0 && excl.numel() == 0;
-  if (!no_excl) need_csr(excl_off, "excl_off", n, excl.numel(), P);
-  check_range(users, P.size(0), "users");
-  check_range(tests, Q.size(0), "test_items");
-  if (excl.numel() == 0) excl = at::zeros({1}, users.options());
-  at::Tensor worst = at::empty({ne, n}, users.options());
-  if (n == 0) return worst;
+  const CertEntries c(P, Q, users, test_items, num_candidates, excl_off, excl_items, side);
+  at::Tensor worst = at::empty({ne, c.n}, c.users.options());
+  if (c.n == 0) return worst;
   size_t ws = 0;
-  ok(acf_eval_positions_worst_workspace((int32_t)n, (int32_t)num_candidates, (int32_t)ne, &ws),
+  ok(acf_eval_positions_worst_workspace((int32_t)c.n, (int32_t)num_candidates, (int32_t)ne, &ws),
      "acf_eval_positions_worst_workspace");
-  at::Tensor work = at::empty({(int64_t)((ws + 3) / 4)}, users.options());
+  at::Tensor work = at::empty({(int64_t)((ws + 3) / 4)}, c.users.options());
   ok(acf_eval_positions_worst(P.data_ptr<float>(), Q.data_ptr<float>(), P.size(0), Q.size(0), (int32_t)P.size(1),
-                              users.data_ptr<int32_t>(), tests.data_ptr<int32_t>(), (int32_t)n,
-                              (int32_t)num_candidates, no_excl ? nullptr : excl_off.data_ptr<int64_t>(),
-                              no_excl ? nullptr : excl.data_ptr<int32_t>(), ev, (int32_t)ne, side == "user" ? 0 : 1,
+                              c.users.data_ptr<int32_t>(), c.tests.data_ptr<int32_t>(), (int32_t)c.n,
+                              (int32_t)num_candidates, c.eoff, c.ex, ev, (int32_t)ne, c.side,
                               worst.data_ptr<int32_t>(), work.data_ptr(), ws, 0, stream_of(P)),
      "acf_eval_positions_worst");
   return worst;
 }
 
 // the k smallest (eps_c, c) per entry, eps [n, k] ascending and items [n, k] (acf_eval_radius; side:
-// "user" | "item"): eps[r][j] is the certified radius at j + 1.  Checks as eval_positions_worst.
-std::tuple<at::Tensor, at::Tensor> eval_radius(const at::Tensor& P, const at::Tensor& Q, const at::Tensor& users_,
-                                               const at::Tensor& test_items_, int64_t num_candidates,
-                                               const at::Tensor& excl_off, const at::Tensor& excl_items_, int64_t k,
+// "user" | "item"): eps[r][j] is the certified radius at j + 1.
+std::tuple<at::Tensor, at::Tensor> eval_radius(const at::Tensor& P, const at::Tensor& Q, const at::Tensor& users,
+                                               const at::Tensor& test_items, int64_t num_candidates,
+                                               const at::Tensor& excl_off, const at::Tensor& excl_items, int64_t k,
                                                c10::string_view side) {
-  need_table(P, "embedding_P", P);
-  need_table(Q, "embedding_Q", P);
-  TORCH_CHECK(P.size(1) == Q.size(1), "embedding_P and embedding_Q dims differ");
-  TORCH_CHECK(side == "user" || side == "item", "side must be \"user\" or \"item\", got \"", side, "\"");
   TORCH_CHECK(k >= 1 && k <= 128, "k must lie in [1, 128], got ", k);
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(P.device());
-  at::Tensor users = idx32(users_, "users", P), tests = idx32(test_items_, "test_items", P);
-  at::Tensor excl = idx32(excl_items_, "excl_items", P);
-  const int64_t n = users.numel();
-  TORCH_CHECK(n < (1ll << 31), "too many users");
-  TORCH_CHECK(tests.numel() == n, "test_items must have one entry per user");
-  TORCH_CHECK(num_candidates >= 1 && num_candidates <= Q.size(0), "num_candidates must lie in [1, item rows]");
-  const bool no_excl = excl_off.numel() == 0 && excl.numel() == 0;
-  if (!no_excl) need_csr(excl_off, "excl_off", n, excl.numel(), P);
-  check_range(users, P.size(0), "users");
-  check_range(tests, Q.size(0), "test_items");
-  if (excl.numel() == 0) excl = at::zeros({1}, users.options());
-  at::Tensor eps = at::empty({n, k}, P.options()), items = at::empty({n, k}, users.options());
-  if (n == 0) return {eps, items};
+  const CertEntries c(P, Q, users, test_items, num_candidates, excl_off, excl_items, side);
+  at::Tensor eps = at::empty({c.n, k}, P.options()), items = at::empty({c.n, k}, c.users.options());
+  if (c.n == 0) return {eps, items};
   size_t ws = 0;
-  ok(acf_eval_radius_workspace((int32_t)n, (int32_t)num_candidates, (int32_t)k, &ws), "acf_eval_radius_workspace");
-  at::Tensor work = at::empty({(int64_t)((ws + 7) / 8)}, users.options().dtype(at::kLong));
+  ok(acf_eval_radius_workspace((int32_t)c.n, (int32_t)num_candidates, (int32_t)k, &ws), "acf_eval_radius_workspace");
+  at::Tensor work = at::empty({(int64_t)((ws + 7) / 8)}, c.users.options().dtype(at::kLong));
   ok(acf_eval_radius(P.data_ptr<float>(), Q.data_ptr<float>(), P.size(0), Q.size(0), (int32_t)P.size(1),
-                     users.data_ptr<int32_t>(), tests.data_ptr<int32_t>(), (int32_t)n, (int32_t)num_candidates,
-                     no_excl ? nullptr : excl_off.data_ptr<int64_t>(), no_excl ? nullptr : excl.data_ptr<int32_t>(),
-                     (int32_t)k, side == "user" ? 0 : 1, eps.data_ptr<float>(), items.data_ptr<int32_t>(),
+                     c.users.data_ptr<int32_t>(), c.tests.data_ptr<int32_t>(), (int32_t)c.n, (int32_t)num_candidates,
+                     c.eoff, c.ex, (int32_t)k, c.side, eps.data_ptr<float>(), items.data_ptr<int32_t>(),
                      work.data_ptr(), ws, 0, stream_of(P)),
      "acf_eval_radius");
   return {eps, items};

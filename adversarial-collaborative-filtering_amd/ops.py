@@ -1081,6 +1081,26 @@ def _worst_eps(eps) -> tuple:
     return es
 
 
+def _cert_entries(P, Q, users, test_items, num_candidates, excl_off, excl_items, side):
+    """The arguments eval_positions_worst and eval_radius share, checked and on the
+    tables' device: (side code, users, test items, n, excl offsets, excl items, device)."""
+    if side not in WORST_SIDES:
+        raise ValueError(f"side must be one of {sorted(WORST_SIDES)}, got {side!r}")
+    ti = _csr_items(test_items, "test_items")
+    us = _csr_items(users, "users")
+    n = us.numel()
+    if ti.numel() != n:
+        raise ValueError(f"test_items must have one entry per user: {ti.numel()} for {n}")
+    _check_num_candidates(num_candidates)
+    _table_types(P, Q)
+    if num_candidates > Q.shape[0]:
+        raise ValueError("num_candidates exceeds item rows")
+    eoff, ex = _exclusions(excl_off, excl_items, n, P.device)
+    dev = _table_pair(P, Q)
+    settle_tables()
+    return WORST_SIDES[side], _to_i32(us, dev), _to_i32(ti, dev), n, eoff, ex, dev
+
+
 def eval_positions_worst_workspace(n_users: int, num_candidates: int, n_eps: int) -> int:
     """Bytes of device workspace acf_eval_positions_worst needs (a host-only query)."""
     return _workspace_bytes("acf_eval_positions_worst_workspace", n_users, num_candidates, n_eps)
@@ -1104,21 +1124,7 @@ def eval_positions_worst(P, Q, users, test_items, num_candidates: int, excl_off=
     side raise ValueError / TypeError before any native call; with check, a
     user or test item outside its table raises NativeIndexError (one sync)."""
     es = _worst_eps(eps)
-    if side not in WORST_SIDES:
-        raise ValueError(f"side must be one of {sorted(WORST_SIDES)}, got {side!r}")
-    ti = _csr_items(test_items, "test_items")
-    us = _csr_items(users, "users")
-    n = us.numel()
-    if ti.numel() != n:
-        raise ValueError(f"test_items must have one entry per user: {ti.numel()} for {n}")
-    _check_num_candidates(num_candidates)
-    _table_types(P, Q)
-    if num_candidates > Q.shape[0]:
-        raise ValueError("num_candidates exceeds item rows")
-    eoff, ex = _exclusions(excl_off, excl_items, n, P.device)
-    dev = _table_pair(P, Q)
-    settle_tables()
-    u, t = _to_i32(us, dev), _to_i32(ti, dev)
+    sd, u, t, n, eoff, ex, dev = _cert_entries(P, Q, users, test_items, num_candidates, excl_off, excl_items, side)
     worst = torch.empty((len(es), n), dtype=torch.int32, device=dev)
     if n == 0:
         return worst
@@ -1127,7 +1133,7 @@ def eval_positions_worst(P, Q, users, test_items, num_candidates: int, excl_off=
     ceps = (ctypes.c_float * len(es))(*es)
     with _on(dev):
         call("acf_eval_positions_worst", P.data_ptr(), Q.data_ptr(), P.shape[0], Q.shape[0], P.shape[1],
-             u.data_ptr(), t.data_ptr(), n, num_candidates, _ptr(eoff), _ptr(ex), ceps, len(es), WORST_SIDES[side],
+             u.data_ptr(), t.data_ptr(), n, num_candidates, _ptr(eoff), _ptr(ex), ceps, len(es), sd,
              worst.data_ptr(), work.data_ptr(), nbytes, int(bool(check)), _stream_ptr(dev))
     return worst
 
@@ -1156,21 +1162,7 @@ def eval_radius(P, Q, users, test_items, num_candidates: int, excl_off=None, exc
     with check, a user or test item outside its table raises NativeIndexError
     (one sync), without it such an index is read as row 0."""
     _check_k(k)
-    if side not in WORST_SIDES:
-        raise ValueError(f"side must be one of {sorted(WORST_SIDES)}, got {side!r}")
-    ti = _csr_items(test_items, "test_items")
-    us = _csr_items(users, "users")
-    n = us.numel()
-    if ti.numel() != n:
-        raise ValueError(f"test_items must have one entry per user: {ti.numel()} for {n}")
-    _check_num_candidates(num_candidates)
-    _table_types(P, Q)
-    if num_candidates > Q.shape[0]:
-        raise ValueError("num_candidates exceeds item rows")
-    eoff, ex = _exclusions(excl_off, excl_items, n, P.device)
-    dev = _table_pair(P, Q)
-    settle_tables()
-    u, t = _to_i32(us, dev), _to_i32(ti, dev)
+    sd, u, t, n, eoff, ex, dev = _cert_entries(P, Q, users, test_items, num_candidates, excl_off, excl_items, side)
     eps = torch.empty((n, k), dtype=torch.float32, device=dev)
     items = torch.empty((n, k), dtype=torch.int32, device=dev)
     if n == 0:
@@ -1185,8 +1177,8 @@ def eval_radius(P, Q, users, test_items, num_candidates: int, excl_off=None, exc
             raise ValueError(f"workspace too small: {work.numel() * 8} < {nbytes} bytes")
     with _on(dev):
         call("acf_eval_radius", P.data_ptr(), Q.data_ptr(), P.shape[0], Q.shape[0], P.shape[1], u.data_ptr(),
-             t.data_ptr(), n, num_candidates, _ptr(eoff), _ptr(ex), k, WORST_SIDES[side], eps.data_ptr(),
-             items.data_ptr(), work.data_ptr(), nbytes, int(bool(check)), _stream_ptr(dev))
+             t.data_ptr(), n, num_candidates, _ptr(eoff), _ptr(ex), k, sd, eps.data_ptr(), items.data_ptr(),
+             work.data_ptr(), nbytes, int(bool(check)), _stream_ptr(dev))
     return eps, items
 
 

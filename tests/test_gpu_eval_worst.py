@@ -150,21 +150,47 @@ def test_item_side_with_a_large_eps_counts_every_candidate():
     assert (got[0] <= got[1]).all() and got[0].sum() < got[1].sum()
 
 
+# ---- entry-tile edges, check=False ---------------------------------------------------
+@pytest.mark.parametrize("side", SIDES)
+@pytest.mark.parametrize("n", [1, 7, 8, 9])
+def test_entry_tile_edges(n, side):
+    """1, 7, 8 and 9 entries around the tile of 8: each column is the 13-entry call's column, byte for
+    byte, so the tile's rows past the last entry leak into no live count."""
+    P, Q, users, tests, num_cand, elists = mixed_case(8)
+    eps = EPS8[::2]
+    got = check_case(P, Q, users[:n], tests[:n], num_cand, elists[:n], eps, side)
+    full = worst(P, Q, users, tests, num_cand, elists, eps, side)
+    assert got.tobytes() == np.ascontiguousarray(full[:, :n]).tobytes()
+
+
+@pytest.mark.parametrize("side", SIDES)
+def test_unchecked_call_on_valid_input_gives_the_checked_bits(side):
+    P, Q, users, tests, num_cand, elists = mixed_case(8)
+    checked = worst(P, Q, users, tests, num_cand, elists, EPS8, side, check=True)
+    assert worst(P, Q, users, tests, num_cand, elists, EPS8, side, check=False).tobytes() == checked.tobytes()
+
+
 # ---- window edges, strips, large d ---------------------------------------------------
-@pytest.mark.parametrize("num_cand", [255, 256, 257, 2053])
+@pytest.mark.parametrize("num_cand", [1, 255, 256, 257, 2049, 2053])
 def test_window_edges(num_cand):
-    """The edges of the 256-candidate sweep window and of the 2,048-candidate bitmap."""
+    """The edges of the 256-candidate sweep window and of the 2,048-candidate bitmap; 1 is a single
+    candidate (where it is the test item nothing counts), 2,049 one candidate in a second bitmap.
+    Entry 2's test item is an item row outside the range and it excludes nothing inside, so every
+    candidate is swept for it, the only one at num_cand = 1 too."""
     rng = np.random.default_rng(num_cand)
     P = (0.1 * rng.standard_normal((12, 8))).astype(np.float32)
     Q = (0.1 * rng.standard_normal((num_cand + 3, 8))).astype(np.float32)
     users = rng.permutation(12)[:9].astype(np.int32)
     tests = rng.integers(0, num_cand, 9).astype(np.int32)
-    tests[0], tests[1] = num_cand - 1, 0
+    tests[0], tests[1], tests[2] = num_cand - 1, 0, num_cand + 1
     elists = [np.concatenate([rng.integers(0, num_cand, 10), [num_cand - 1, num_cand, 0, -1]]).astype(np.int32)
               for _ in users]
     elists[3] = np.zeros(0, np.int32)
+    elists[2] = np.array([-1, num_cand + 1], np.int32)
+    Q[0] = Q[num_cand + 1]  # a twin of entry 2's test item: candidate 0 counts for it at every eps
     for side in SIDES:
-        check_case(P, Q, users, tests, num_cand, elists, EPS8[::2], side)
+        got = check_case(P, Q, users, tests, num_cand, elists, EPS8[::2], side)
+        assert (got[:, 2] >= 1).all()
 
 
 def test_strips():

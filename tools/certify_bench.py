@@ -21,6 +21,7 @@ restatement differ (it rounds differently; no assertion).  Device times are
 events around `reps` back-to-back calls (reps sized from a warm-up so that a
 window is at least ~50 ms, at most 20 calls), per call; the variants alternate
 within a round and the median over the rounds is reported with min and max.
+ACF_ALT_LIB=path times that build of libacf_apr.so in place of the package's.
 Needs a HIP device; writes one JSON document (default
 profiles/certify_bench.json).
 
@@ -38,6 +39,7 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "adversarial-collaborative-filtering_amd"
 sys.path.insert(0, REPO)
+from tools.alt_lib import use_alt_lib  # noqa: E402
 EPS = {1: (0.05,), 4: (0.0, 0.02, 0.05, 0.1)}
 
 
@@ -67,10 +69,11 @@ def main(argv=None):
     ops = importlib.import_module(PKG + ".ops")
     ev = importlib.import_module(PKG + ".evaluate")
     data = importlib.import_module(PKG + ".data")
+    alt = use_alt_lib(PKG)  # $ACF_ALT_LIB: that build in place of the package's
     dev = torch.device("cuda:0")
     g = lambda a, dt: torch.as_tensor(a, dtype=dt, device=dev)  # noqa: E731
-    doc = {"tool": "tools/certify_bench.py", "device": torch.cuda.get_device_name(0), "dim": args.dim,
-           "rounds": args.rounds, "eps": {str(k): list(v) for k, v in EPS.items()}, "cases": []}
+    doc = {"tool": "tools/certify_bench.py", "lib": alt or "package", "device": torch.cuda.get_device_name(0),
+           "dim": args.dim, "rounds": args.rounds, "eps": {str(k): list(v) for k, v in EPS.items()}, "cases": []}
     for shape in args.shapes.split(","):
         ds = data.get_dataset(shape + "-synthetic")
         plan = ev.init_eval_model(ds, argparse.Namespace(eval_mode="all"))

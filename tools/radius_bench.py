@@ -19,7 +19,8 @@ users whose radius at K exceeds it.  Device times are events around `reps`
 back-to-back calls (reps sized from a warm-up so that a window is at least ~50
 ms, at most 20 calls), per call; the variants alternate within a round and the
 median over the rounds is reported with min and max.  Expectation on record,
-not a pass bar: radius within 1.5x of worst at K = 10.  Needs a HIP device;
+not a pass bar: radius within 1.5x of worst at K = 10.  ACF_ALT_LIB=path times
+that build of libacf_apr.so in place of the package's.  Needs a HIP device;
 writes one JSON document (default profiles/radius_bench.json).
 
     python tools/radius_bench.py [--out FILE] [--rounds N] [--shapes ml-1m,pinterest-20]
@@ -36,6 +37,7 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "adversarial-collaborative-filtering_amd"
 sys.path.insert(0, REPO)
+from tools.alt_lib import use_alt_lib  # noqa: E402
 KS = (10, 100)
 BISECT_STEPS = 24
 
@@ -66,10 +68,11 @@ def main(argv=None):
     ops = importlib.import_module(PKG + ".ops")
     ev = importlib.import_module(PKG + ".evaluate")
     data = importlib.import_module(PKG + ".data")
+    alt = use_alt_lib(PKG)  # $ACF_ALT_LIB: that build in place of the package's
     dev = torch.device("cuda:0")
     g = lambda a, dt: torch.as_tensor(a, dtype=dt, device=dev)  # noqa: E731
-    doc = {"tool": "tools/radius_bench.py", "device": torch.cuda.get_device_name(0), "dim": args.dim,
-           "rounds": args.rounds, "bisect_steps": BISECT_STEPS, "cases": []}
+    doc = {"tool": "tools/radius_bench.py", "lib": alt or "package", "device": torch.cuda.get_device_name(0),
+           "dim": args.dim, "rounds": args.rounds, "bisect_steps": BISECT_STEPS, "cases": []}
     for shape in args.shapes.split(","):
         ds = data.get_dataset(shape + "-synthetic")
         plan = ev.init_eval_model(ds, argparse.Namespace(eval_mode="all"))
