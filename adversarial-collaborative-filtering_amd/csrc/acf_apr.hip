@@ -2656,9 +2656,14 @@ static bool decided(const Pending& p, bool* failed) {
   return (v >> 2) == (unsigned long long)p.seq;
 }
 
+// The phases of a triplet-centric batch (a mask): the two-phase API runs one each
+// (delta_update the clean phase; optimizer_step the adversarial / BPR phase and
+// the call-counter bump), a whole step both.  The other schedules run whole steps.
+enum { PHASE_CLEAN = 1, PHASE_STEP = 2, PHASE_BOTH = PHASE_CLEAN | PHASE_STEP };
+
 static int run_loop(acf_apr_ctx* c, const acf_apr_tables* tb, const acf_apr_hparams* hp,
                     int32_t first, int32_t n, hipStream_t s, hipEvent_t* events, int* kinds,
-                    int allow_stream, int tri_phases);
+                    bool allow_stream, int phases);
 
 // Block until queued call p has reported its outcome: poll its word of the
 // host-mapped status ring, not the stream (a stream sync also waited
@@ -2709,7 +2714,7 @@ int resolve(acf_apr_ctx* c, int mode) {
     for (auto& x : todo) {
       if (x.s != prev) HIP_TRY(hipStreamSynchronize(prev));  // one stream per group in practice
       prev = x.s;
-      ACF_RET(run_loop(x.c, &x.tb, &x.hp, x.first, x.n, x.s, nullptr, nullptr, 0, 3));
+      ACF_RET(run_loop(x.c, &x.tb, &x.hp, x.first, x.n, x.s, nullptr, nullptr, false, PHASE_BOTH));
       ++x.c->recoveries;
       if (!x.c->replay_ev) HIP_TRY(hipEventCreateWithFlags(&x.c->replay_ev, hipEventDisableTiming));
       HIP_TRY(hipEventRecord(x.c->replay_ev, x.s));
@@ -2812,7 +2817,7 @@ static StepArgs make_args(acf_apr_ctx* c, const acf_apr_tables* tb, const acf_ap
   return a;
 }
 
-// kernel kinds for timing: 0 = phase-1 (clean, or fused BPR), 1 = adversarial, 2 = flush
+// the kernels of the context's geometry and mapping (get_kernels)
 struct Kernels {
   void *clean_apr = nullptr, *clean_bpr = nullptr, *adv = nullptr, *flush = nullptr;
   void* stream = nullptr;  // k_stream (one wave per slot, d <= 256)
@@ -2899,7 +2904,6 @@ static void kernel_ptrs(Kernels* k, int packed, int fused, int lists, int tri) {
     }
     k->slots_per_wave = 1;
   }
-  k->flush = reinterpret_cast<void*>(&k_flush);
 }
 
 // slot mapping: 0 auto (packed for batches >= ACF_PACKED_MIN_BATCH), 1 one wave
@@ -2910,20 +2914,77 @@ static int get_kernels(const acf_apr_ctx* c, Kernels* k, int fused = 0) {
                        c->tri && (fused || c->shard));
 }
 
-typedef void (*StepKernel)(StepArgs);
+// The kind of a launch, for acf_apr_time_kernels (ms and launches per kind; include/acf_apr.h):
+//   0 phase 1: the clean pass, or the whole BPR step    1 phase 2: the adversarial pass
+//   2 flush: the end-of-call write-back / call-counter bump (k_flush, k_stream_flush)
+//   3 never recorded (the overlapped step k_ovl, removed in r05; its slot stays in the ABI's six)
+//   4 k_stream                                          5 hot-slot combine (k_hot_combine, k_tri_combine)
+enum { KIND_CLEAN = 0, KIND_ADV = 1, KIND_FLUSH = 2, KIND_STREAM = 4, KIND_HOT = 5, N_KINDS = 6 };
 
-// Launch one step kernel; with events (timing mode) via hipExtLaunchKernelGGL.
-static int launch(void* fn, const StepArgs& a, int waves, hipStream_t s, hipEvent_t e0 = nullptr,
-                  hipEvent_t e1 = nullptr) {
-  const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-  // waves past slot_waves run fused triplets: only when fusion is on
-  if (!a.use_single && a.slot_waves + a.hot_waves < waves) return acf_set_error(ACF_E_STATE, "bad step geometry");
-  if (e0)
-    hipExtLaunchKernelGGL(reinterpret_cast<StepKernel>(fn), grid, block, 0, s, e0, e1, 0, a);
-  else
-    hipLaunchKernelGGL(reinterpret_cast<StepKernel>(fn), grid, block, 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return ACF_OK;
+// Every launch of a step goes through one Launcher per call: `waves` waves in
+// 256-thread workgroups on its stream.  Timing mode (events != nullptr: two
+// events per launch, kinds[] per launch) launches via hipExtLaunchKernelGGL.
+// `tail`: what a kernel takes after its StepArgs (k_stream, k_stream_flush).
+struct Launcher {
+  hipStream_t s;
+  hipEvent_t* events = nullptr;
+  int* kinds = nullptr;
+  int li = 0;  // launches so far: the next one's events, kind and stamp slot (StepArgs.diag_launch)
+
+  template <typename... Tail>
+  int launch(void* fn, StepArgs& a, int64_t waves, int kind, Tail... tail) {
+    // a step kernel's waves past its slot and piece waves run fused triplets: only when fusion is on
+    if (sizeof...(Tail) == 0 && !a.use_single && a.slot_waves + a.hot_waves < waves)
+      return acf_set_error(ACF_E_STATE, "bad step geometry");
+    typedef void (*Fn)(StepArgs, Tail...);
+    const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+    a.diag_launch = li;
+    if (kinds) kinds[li] = kind;
+    if (events)
+      hipExtLaunchKernelGGL(reinterpret_cast<Fn>(fn), grid, block, 0, s, events[2 * li], events[2 * li + 1], 0, a,
+                            tail...);
+    else
+      hipLaunchKernelGGL(reinterpret_cast<Fn>(fn), grid, block, 0, s, a, tail...);
+    ++li;
+    HIP_TRY(hipGetLastError());
+    return ACF_OK;
+  }
+};
+
+// The wave counts of one batch's launches, in one place: the three schedules and
+// the entry points that launch a single pass (two-phase API, shard passes) read them.
+struct StepWaves {
+  int S;           // slots of a batch
+  int per_slot;    // one wave per slots_per_wave slots (the two-phase API's slot kernels, uncapped)
+  int slot;        // slot waves of a step kernel (list kernels: a fixed set that strides)
+  int hot;         // piece waves of a list kernel's hot slots, after its slot waves (0: no lists)
+  int hot_blocks;  // workgroups of k_hot_combine
+  int fused;       // fused-triplet waves at the end of a phase-2 / BPR launch (0: fusion off)
+  // triplet-centric step: triplet waves of k_tri_clean / k_tri_adv; k_tri_combine's piece and
+  // small-slot wave ranges (rounded up to whole workgroups), combining workgroups and grid;
+  // the same for the combine at the head of k_tri_cadv, whose grid ends with the triplet waves
+  int tri, comb_hot, comb_slot, comb_blocks, comb;
+  int cadv_slot, cadv_blocks, cadv;
+};
+
+static StepWaves step_waves(const acf_apr_ctx* c, const Kernels& K) {
+  StepWaves w;
+  const int groups = (c->B + 64 / c->lpr - 1) / (64 / c->lpr);  // one lane-group per triplet
+  w.S = 3 * c->B;
+  w.per_slot = (w.S + K.slots_per_wave - 1) / K.slots_per_wave;
+  w.slot = K.lists ? std::min(w.per_slot, ACF_LIST_WAVES) : w.per_slot;
+  w.hot = K.lists ? std::min(c->hot.piece_stride, ACF_HOT_WAVES) : 0;
+  w.hot_blocks = std::min(c->hot.hot_stride, ACF_HOT_BLOCKS);
+  w.fused = c->fusion ? groups : 0;
+  w.tri = (groups + tri_gpw(c->nv) - 1) / tri_gpw(c->nv);
+  w.comb_hot = (w.hot + 3) & ~3;
+  w.comb_slot = (std::min(w.slot, ACF_TRI_COMB_WAVES) + 3) & ~3;
+  w.comb_blocks = std::min(w.hot_blocks, ACF_TRI_HOT_BLOCKS);
+  w.comb = w.comb_slot + w.comb_hot + 4 * w.comb_blocks;
+  w.cadv_slot = (std::min(w.slot, ACF_CADV_SLOT_WAVES) + 3) & ~3;
+  w.cadv_blocks = std::min(w.hot_blocks, ACF_CADV_HOT_BLOCKS);
+  w.cadv = w.cadv_slot + w.comb_hot + 4 * w.cadv_blocks + w.tri;
+  return w;
 }
 
 static int check_step(acf_apr_ctx* c, const acf_apr_tables* tb, const acf_apr_hparams* hp,
@@ -2935,17 +2996,14 @@ static int check_step(acf_apr_ctx* c, const acf_apr_tables* tb, const acf_apr_hp
   return ACF_OK;
 }
 
-// training_batch over planned batches [first, first+n): per batch phase 1
-// (+ flush of the previous batch) and, for APR, phase 2; a final flush.
-// events != nullptr: timing mode, 2 events per launch, kinds[] per launch.
-// (r05: the overlapped schedule k_ovl -- adv(t) + clean(t+1) per launch -- is
-// gone; k_stream replaced it for d <= 256, the two-kernel schedule serves the
-// rest and the failsafe replay.)
+// positions of a k_stream launch (upper bound of the tasks of a batch): its
+// slots, and with fusion one lane-group per triplet
+static int stream_positions(const acf_apr_ctx* c) {
+  return 3 * c->B + (c->fusion ? (c->B + 64 / c->lpr - 1) / (64 / c->lpr) : 0);
+}
 
 // Streamed step: version buffers (allocated at first use: 3 x maxNB x S x d
 // granules) and the resident-wave budget of k_stream.
-static int stream_positions(const acf_apr_ctx* c, const Kernels& K, int fuse);
-
 static int stream_ready(acf_apr_ctx* c, const Kernels& K) {
   if (c->stream_ok >= 0) return c->stream_ok;
   if (!K.stream) return 0;
@@ -2965,7 +3023,7 @@ static int stream_ready(acf_apr_ctx* c, const Kernels& K) {
   }
   // the version buffers only for a plan the launch can keep resident (otherwise
   // not now: a later plan with a smaller batch may fit)
-  if (stream_positions(c, K, c->fusion) > c->stream_max_waves) return 0;
+  if (stream_positions(c) > c->stream_max_waves) return 0;
   c->stream_ok = 0;
   const size_t n = (size_t)c->maxNB * 3 * c->maxB * c->d;
   if (dalloc(c, &c->ver_w, n) != ACF_OK || dalloc(c, &c->ver_a, n) != ACF_OK ||
@@ -2998,11 +3056,6 @@ static int stream_ready(acf_apr_ctx* c, const Kernels& K) {
   return 1;
 }
 
-static int stream_positions(const acf_apr_ctx* c, const Kernels& K, int fuse) {
-  const int TW = fuse ? (c->B + 64 / c->lpr - 1) / (64 / c->lpr) : 0;
-  return 3 * c->B + TW;
-}
-
 static int capturing(hipStream_t s) {
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(s, &st) != hipSuccess) {
@@ -3016,7 +3069,7 @@ static int capturing(hipStream_t s) {
 static bool use_stream(acf_apr_ctx* c, const Kernels& K, const acf_apr_hparams* hp) {
   if (!(c->stream && hp->adver && K.stream && !K.lists && K.slots_per_wave == 1 && c->plan_kind2)) return false;
   if (c->stream_ok != 1) return false;
-  return stream_positions(c, K, c->fusion) <= c->stream_max_waves;
+  return stream_positions(c) <= c->stream_max_waves;
 }
 
 static void prepare_stream(acf_apr_ctx* c, const acf_apr_hparams* hp) {
@@ -3024,185 +3077,168 @@ static void prepare_stream(acf_apr_ctx* c, const acf_apr_hparams* hp) {
   if (c->stream && hp->adver && c->stream_ok < 0 && get_kernels(c, &K, c->fusion) == ACF_OK) (void)stream_ready(c, K);
 }
 
-// kinds: 0 phase 1 / fused BPR, 1 phase 2, 2 flush, 3 (unused since r05: k_ovl), 4 k_stream,
-// 5 hot-slot combine (list kernels)
-// tri_phases (triplet-centric plans, one batch through the two-phase API): bit 0
-// the clean phase (delta_update), bit 1 the adversarial / BPR phase + the
-// call-counter bump (optimizer_step); train_planned runs both.
+// Schedule 1, the streamed call (d <= 256, one wave per slot, APR): batches
+// [first, first + n) in one k_stream launch; the write-back in its tail, or in
+// k_stream_flush behind it.
+static int run_streamed(acf_apr_ctx* c, const acf_apr_tables* tb, const acf_apr_hparams* hp, int32_t first,
+                        int32_t n, Launcher& L, const Kernels& K) {
+  const int S = 3 * c->B, P = stream_positions(c);
+  const int lists = c->fusion && c->task_lists;
+  // with task lists the kernel sizes its positions from the plan: give it the
+  // resident maximum; otherwise P x depth waves
+  const int64_t waves = lists ? c->stream_max_waves
+                              : std::min<int64_t>(c->stream_max_waves, (int64_t)P * c->stream_depth);
+  const int cap = capturing(L.s);
+  // verified: queued for acf_apr_resolve (no host sync here); a timed or
+  // captured call is unverified (a give-up sets step_err bit 0, the call is dropped)
+  const bool verify = c->failsafe && !L.events && cap == 0;
+  // the write-back in k_stream's tail: the whole plan in one launch (the final-
+  // slot list is the plan's), and a launch the host counts (not captured)
+  const bool tail = c->final_ok && first == 0 && n == c->nb && cap == 0;
+  // an unverified launch behind queued verified calls would run gated if one of
+  // them failed (dropped for good): settle the group first (not
+  // possible while capturing: a captured call is documented as unverified)
+  if (!verify && cap == 0 && !c->grp->q.empty()) ACF_RET(resolve(c, 2));
+  if (verify) {  // at most 8 queued calls per context (its status ring)
+    int mine = 0;
+    for (const auto& x : c->grp->q) mine += x.c == c;
+    if (mine >= 8) ACF_RET(resolve(c, 1));
+  }
+  StepArgs a = make_args(c, tb, hp, first, 0);
+  a.use_single = c->fusion;
+  a.slot_waves = S;
+  a.first = first;
+  a.t_end = first + n;
+  a.task_list = lists ? c->task_list : nullptr;
+  a.task_stride = c->task_stride;
+  a.max_depth = c->stream_depth;
+  a.poll_sleep = c->poll_sleep;
+  if (++c->seq == 0) ++c->seq;  // seq 0 is never a launch's (zeroed words)
+  a.seq = c->seq;
+  a.verify = verify ? 1 : 0;
+  if (tail) {
+    a.tail_par = (int32_t)(c->tail_launches++ & 1);
+    a.tail = 1;
+    a.flushers = ACF_TAIL_FLUSHERS;
+    a.decide_prev = (unsigned long long)c->last_tail_seq << 1;
+    c->last_tail_seq = a.seq;
+  }
+  ACF_RET(L.launch(K.stream, a, waves, KIND_STREAM, (int32_t)P));
+  if (!tail)  // one lane-group per slot
+    ACF_RET(L.launch(K.stream_flush, a, ((int64_t)n * S * c->lpr + 63) / 64, KIND_FLUSH, c->epoch));
+  if (verify) {
+    Pending p;
+    p.c = c; p.seq = a.seq; p.first = first; p.n = n; p.tb = *tb; p.hp = *hp; p.s = L.s;
+    c->grp->q.push_back(p);
+  }
+  return ACF_OK;
+}
+
+// Schedule 2, one batch of a triplet-centric plan (see k_tri_*).  APR: the clean
+// phase is k_tri_clean + k_tri_combine<0>, the second phase k_tri_adv +
+// k_tri_combine<2>; BPR: one phase, k_tri_clean<BPR> + k_tri_combine<1>.  The
+// combine finishes the shared rows, its hot slots' combining workgroups after its
+// piece and small-slot waves.  Every row is updated in its table
+// (StepArgs.inplace): nothing is pending from batch t-1.  Shard passes
+// (acf_apr_shard_pass_export) run one phase with their exchange rows (xbuf, xmap, xn).
+static int run_tri_batch(acf_apr_ctx* c, const acf_apr_tables* tb, const acf_apr_hparams* hp, int32_t t, int phases,
+                         Launcher& L, const Kernels& K, const StepWaves& W, float* xbuf = nullptr,
+                         const int64_t* xmap = nullptr, int32_t xn = 0) {
+  StepArgs a = make_args(c, tb, hp, t, 0);
+  a.use_single = 1;
+  a.xbuf = xbuf;
+  a.xmap = xmap;
+  a.xn = xn;
+  // One StepArgs serves the batch's launches: they differ in the wave split alone.
+  // k_tri_clean reads slot_waves (0: triplet waves only, no write-back of t-1) and
+  // neither hot_waves nor hot_blocks; k_tri_adv reads none of the three
+  // (tri_triplets<PASS 2> indexes by wave and StepArgs.B); k_tri_combine and
+  // k_tri_cadv read all three.
+  auto triplets = [&](void* fn, int kind) {
+    a.slot_waves = 0;
+    return L.launch(fn, a, W.tri, kind);
+  };
+  auto combine = [&](int mode) {
+    a.slot_waves = W.comb_slot;
+    a.hot_waves = W.comb_hot;
+    a.hot_blocks = W.comb_blocks;
+    return L.launch(K.tri_comb[mode], a, W.comb, KIND_HOT);
+  };
+  if (!hp->adver) {
+    if (!(phases & PHASE_STEP)) return ACF_OK;
+    ACF_RET(triplets(K.tri_clean_bpr, KIND_CLEAN));
+    return combine(1);
+  }
+  // hash plans (fused triplets placed first), a whole step, not shard mode: the
+  // clean combine rides at the head of the adversarial launch (k_tri_cadv)
+  const bool merged = phases == PHASE_BOTH && !c->shard && c->plan_kind == 3 && K.tri_cadv;
+  if (phases & PHASE_CLEAN) {
+    ACF_RET(triplets(K.tri_clean, KIND_CLEAN));
+    if (!merged) ACF_RET(combine(0));
+  }
+  if (phases & PHASE_STEP) {
+    if (merged) {
+      a.slot_waves = W.cadv_slot;
+      a.hot_waves = W.comb_hot;
+      a.hot_blocks = W.cadv_blocks;
+      ACF_RET(L.launch(K.tri_cadv, a, W.cadv, KIND_ADV));
+    } else {
+      ACF_RET(triplets(K.tri_adv, KIND_ADV));
+    }
+    ACF_RET(combine(2));
+  }
+  return ACF_OK;
+}
+
+// One pass of the slot / list schedule: `pass` over the slot waves, the piece
+// waves (a.hot_waves, set by the caller) and `extra` fused-triplet waves; list
+// kernels then combine their hot slots in a launch of their own (k_hot_combine:
+// its workgroups stride over them; `xblocks` export workgroups after those).
+static int slot_pass(Launcher& L, const Kernels& K, const StepWaves& W, StepArgs& a, void* pass, int extra,
+                     int kind, void* combine, int xblocks = 0) {
+  a.slot_waves = W.slot;
+  ACF_RET(L.launch(pass, a, W.slot + W.hot + extra, kind));
+  if (!K.lists) return ACF_OK;
+  a.slot_waves = 4 * (W.hot_blocks + xblocks);
+  return L.launch(combine, a, a.slot_waves, KIND_HOT);
+}
+
+// Schedule 3, one batch on the two-kernel schedule (slot kernels, or list
+// kernels with their hot combines): phase 1 (+ the write-back of batch t-1) and,
+// for APR, phase 2; the fused-triplet waves ride in the last pass.
+static int run_slot_batch(acf_apr_ctx* c, const acf_apr_tables* tb, const acf_apr_hparams* hp, int32_t t,
+                          bool prev_valid, bool more, Launcher& L, const Kernels& K, const StepWaves& W) {
+  StepArgs a = make_args(c, tb, hp, t, prev_valid ? 1 : 0);
+  a.use_single = c->fusion;
+  a.hot_waves = W.hot;
+  a.touch_next = (c->touch_next && !K.lists && more) ? 1 : 0;
+  if (!hp->adver) return slot_pass(L, K, W, a, K.clean_bpr, W.fused, KIND_CLEAN, K.hot_bpr);
+  ACF_RET(slot_pass(L, K, W, a, K.clean_apr, 0, KIND_CLEAN, K.hot_clean));
+  return slot_pass(L, K, W, a, K.adv, W.fused, KIND_ADV, K.hot_adv);
+}
+
+// training_batch over planned batches [first, first + n): the streamed call, or
+// batch by batch on the plan's schedule, then one flush (in place, tri: only the
+// call-counter bump).  events / kinds: timing mode, see Launcher.
 static int run_loop(acf_apr_ctx* c, const acf_apr_tables* tb, const acf_apr_hparams* hp,
                     int32_t first, int32_t n, hipStream_t s, hipEvent_t* events, int* kinds,
-                    int allow_stream = 2, int tri_phases = 3) {
+                    bool allow_stream = true, int phases = PHASE_BOTH) {
   ACF_CHECK(!(c->tri && !c->fusion), ACF_E_STATE,
             "fusion was switched off after a triplet-centric plan (rows are updated in place): plan again");
   Kernels K;
   ACF_RET(get_kernels(c, &K, c->fusion));
-  const int S = 3 * c->B;
-  int SW = (S + K.slots_per_wave - 1) / K.slots_per_wave;  // slot waves of a step kernel
-  if (K.lists) SW = std::min(SW, ACF_LIST_WAVES);
-  const int fuse = c->fusion;
-  const int TW = fuse ? (c->B + 64 / c->lpr - 1) / (64 / c->lpr) : 0;  // fused-triplet waves
-  int li = 0;
-  auto L = [&](void* fn, const StepArgs& a, int waves, int kind) -> int {
-    hipEvent_t e0 = events ? events[2 * li] : nullptr, e1 = events ? events[2 * li + 1] : nullptr;
-    if (kinds) kinds[li] = kind;
-    StepArgs b = a;
-    b.diag_launch = li;
-    ++li;
-    return launch(fn, b, waves, s, e0, e1);
-  };
-  if (allow_stream >= 2 && use_stream(c, K, hp)) {
-    const int P = stream_positions(c, K, fuse);  // upper bound of the tasks of a batch
-    const int lists = fuse && c->task_lists;
-    // with task lists the kernel sizes its positions from the plan: give it the
-    // resident maximum; otherwise P x depth waves
-    const int64_t waves = lists ? c->stream_max_waves
-                                : std::min<int64_t>(c->stream_max_waves, (int64_t)P * c->stream_depth);
-    const int cap = capturing(s);
-    // verified: queued for acf_apr_resolve (no host sync here); a timed or
-    // captured call is unverified (a give-up sets step_err bit 0, the call is dropped)
-    const bool verify = c->failsafe && !events && cap == 0;
-    // the write-back in k_stream's tail: the whole plan in one launch (the final-
-    // slot list is the plan's), and a launch the host counts (not captured)
-    const bool tail = c->final_ok && first == 0 && n == c->nb && cap == 0;
-    // an unverified launch behind queued verified calls would run gated if one of
-    // them failed (dropped for good): settle the group first (not
-    // possible while capturing: a captured call is documented as unverified)
-    if (!verify && cap == 0 && !c->grp->q.empty()) ACF_RET(resolve(c, 2));
-    if (verify) {  // at most 8 queued calls per context (its status ring)
-      int mine = 0;
-      for (const auto& x : c->grp->q) mine += x.c == c;
-      if (mine >= 8) ACF_RET(resolve(c, 1));
-    }
-    const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-    StepArgs a = make_args(c, tb, hp, first, 0);
-    a.use_single = fuse;
-    a.slot_waves = S;
-    a.first = first;
-    a.t_end = first + n;
-    a.task_list = lists ? c->task_list : nullptr;
-    a.task_stride = c->task_stride;
-    a.max_depth = c->stream_depth;
-    a.poll_sleep = c->poll_sleep;
-    if (++c->seq == 0) ++c->seq;  // seq 0 is never a launch's (zeroed words)
-    a.seq = c->seq;
-    a.verify = verify ? 1 : 0;
-    if (tail) {
-      a.tail_par = (int32_t)(c->tail_launches++ & 1);
-      a.tail = 1;
-      a.flushers = ACF_TAIL_FLUSHERS;
-      a.decide_prev = (unsigned long long)c->last_tail_seq << 1;
-      c->last_tail_seq = a.seq;
-    }
-    hipEvent_t e0 = events ? events[2 * li] : nullptr, e1 = events ? events[2 * li + 1] : nullptr;
-    if (kinds) kinds[li] = 4;
-    ++li;
-    typedef void (*SK)(StepArgs, int32_t);
-    if (e0)
-      hipExtLaunchKernelGGL(reinterpret_cast<SK>(K.stream), grid, block, 0, s, e0, e1, 0, a, (int32_t)P);
-    else
-      hipLaunchKernelGGL(reinterpret_cast<SK>(K.stream), grid, block, 0, s, a, (int32_t)P);
-    HIP_TRY(hipGetLastError());
-    if (!tail) {
-      e0 = events ? events[2 * li] : nullptr;
-      e1 = events ? events[2 * li + 1] : nullptr;
-      if (kinds) kinds[li] = 2;
-      ++li;
-      typedef void (*FK)(StepArgs, uint32_t*);
-      const dim3 fgrid(grid_for((int64_t)n * S * c->lpr));  // one lane-group per slot
-      if (e0)
-        hipExtLaunchKernelGGL(reinterpret_cast<FK>(K.stream_flush), fgrid, block, 0, s, e0, e1, 0, a, c->epoch);
-      else
-        hipLaunchKernelGGL(reinterpret_cast<FK>(K.stream_flush), fgrid, block, 0, s, a, c->epoch);
-      HIP_TRY(hipGetLastError());
-    }
-    if (verify) {
-      Pending p;
-      p.c = c; p.seq = a.seq; p.first = first; p.n = n; p.tb = *tb; p.hp = *hp; p.s = s;
-      c->grp->q.push_back(p);
-    }
-    return ACF_OK;
-  }
-  {
-  // list kernels: piece waves of the hot slots after the slot waves, and a
-  // combine launch (kind 5) after each pass
-  const int HW = K.lists ? std::min(c->hot.piece_stride, ACF_HOT_WAVES) : 0;
-  const int HB = std::min(c->hot.hot_stride, ACF_HOT_BLOCKS);
-  if (K.tri) {  // triplet-centric list step (see k_tri_*)
-    // k_tri_combine with its hot-slot combining workgroups after the piece waves
-    // (whole workgroups: the two wave ranges rounded up to multiples of 4)
-    const int SWT = std::min(SW, ACF_TRI_COMB_WAVES);
-    const int SW4 = (SWT + 3) & ~3, HW4 = (HW + 3) & ~3, HBT = std::min(HB, ACF_TRI_HOT_BLOCKS);
-    const int TWT = (c->B + 64 / c->lpr - 1) / (64 / c->lpr);  // one lane-group per triplet
-    for (int32_t t = first; t < first + n; ++t) {
-      // every row is updated in its table (StepArgs.inplace): nothing pending from t-1
-      StepArgs a = make_args(c, tb, hp, t, 0);
-      a.use_single = 1;
-      a.slot_waves = SW;
-      a.hot_waves = HW;
-      StepArgs ah = a;
-      ah.slot_waves = 4 * HB;
-      StepArgs at = a;
-      at.slot_waves = 0;  // k_tri_clean: triplet waves only (no write-back of t-1)
-      StepArgs ac = a;
-      ac.slot_waves = SW4;
-      ac.hot_waves = HW4;
-      ac.hot_blocks = HBT;
-      const int CW = SW4 + HW4 + 4 * HBT;
-      (void)ah;
-      // hash plans (fused triplets placed first), a whole step, not shard mode: the
-      // clean combine rides at the head of the adversarial launch (k_tri_cadv)
-      const bool merged = tri_phases == 3 && !c->shard && c->plan_kind == 3 && K.tri_cadv;
-      if (hp->adver) {
-        if (tri_phases & 1) {
-          ACF_RET(L(K.tri_clean, at, (TWT + tri_gpw(c->nv) - 1) / tri_gpw(c->nv), 0));
-          if (!merged) ACF_RET(L(K.tri_comb[0], ac, CW, 5));
-        }
-        if (tri_phases & 2) {
-          if (merged) {
-            StepArgs am = ac;
-            am.slot_waves = (std::min(SW, ACF_CADV_SLOT_WAVES) + 3) & ~3;
-            am.hot_blocks = std::min(HB, ACF_CADV_HOT_BLOCKS);
-            const int CWm = am.slot_waves + HW4 + 4 * am.hot_blocks;
-            ACF_RET(L(K.tri_cadv, am, CWm + (TWT + tri_gpw(c->nv) - 1) / tri_gpw(c->nv), 1));
-          }
-          else ACF_RET(L(K.tri_adv, a, (TWT + tri_gpw(c->nv) - 1) / tri_gpw(c->nv), 1));
-          ACF_RET(L(K.tri_comb[2], ac, CW, 5));
-        }
-      } else if (tri_phases & 2) {
-        ACF_RET(L(K.tri_clean_bpr, at, (TWT + tri_gpw(c->nv) - 1) / tri_gpw(c->nv), 0));
-        ACF_RET(L(K.tri_comb[1], ac, CW, 5));
-      }
-    }
-    if (!(tri_phases & 2)) return ACF_OK;  // delta_update: no call-counter bump
-  } else {
+  Launcher L{s, events, kinds};
+  if (allow_stream && use_stream(c, K, hp)) return run_streamed(c, tb, hp, first, n, L, K);
+  const StepWaves W = step_waves(c, K);
   for (int32_t t = first; t < first + n; ++t) {
-    const int pv = t > first ? 1 : 0;
-    StepArgs a = make_args(c, tb, hp, t, pv);
-    a.use_single = fuse;
-    a.slot_waves = SW;
-    a.hot_waves = HW;
-    a.touch_next = (c->touch_next && !K.lists && t + 1 < first + n) ? 1 : 0;
-    if (hp->adver) {
-      ACF_RET(L(K.clean_apr, a, SW + HW, 0));
-      StepArgs ah = a;
-      ah.slot_waves = 4 * HB;  // k_hot_combine: workgroups stride over the hot slots
-      if (K.lists) ACF_RET(L(K.hot_clean, ah, 4 * HB, 5));
-      ACF_RET(L(K.adv, a, SW + HW + TW, 1));
-      if (K.lists) ACF_RET(L(K.hot_adv, ah, 4 * HB, 5));
-    } else {
-      ACF_RET(L(K.clean_bpr, a, SW + HW + TW, 0));
-      StepArgs ah = a;
-      ah.slot_waves = 4 * HB;
-      if (K.lists) ACF_RET(L(K.hot_bpr, ah, 4 * HB, 5));
-    }
+    if (K.tri) ACF_RET(run_tri_batch(c, tb, hp, t, phases, L, K, W));
+    else ACF_RET(run_slot_batch(c, tb, hp, t, t > first, t + 1 < first + n, L, K, W));
   }
-  }
-  }
+  if (K.tri && !(phases & PHASE_STEP)) return ACF_OK;  // delta_update: no call-counter bump
   StepArgs af = make_args(c, tb, hp, first + n - 1, 0);
-  af.use_single = fuse;
-  af.slot_waves = S;
-  ACF_RET(L(K.flush, af, K.tri ? 4 : S, 2));  // in place (tri): the call-counter bump only
-  return ACF_OK;
+  af.use_single = c->fusion;
+  af.slot_waves = W.S;
+  return L.launch(K.flush, af, K.tri ? 4 : W.S, KIND_FLUSH);
 }
 
 extern "C" int acf_apr_delta_update(acf_apr_ctx* c, const acf_apr_tables* tb,
@@ -3212,16 +3248,17 @@ extern "C" int acf_apr_delta_update(acf_apr_ctx* c, const acf_apr_tables* tb,
   ACF_CHECK(hp->adver, ACF_E_INVALID, "delta_update needs hparams.adver = 1 (APR graph)");
   hipStream_t s = static_cast<hipStream_t>(stream_);
   if (c->tri) {  // triplet-centric plan: its clean phase
-    ACF_RET(run_loop(c, tb, hp, t, 1, s, nullptr, nullptr, 0, 1));
+    ACF_RET(run_loop(c, tb, hp, t, 1, s, nullptr, nullptr, false, PHASE_CLEAN));
     c->last_delta_batch = t;
     return ACF_OK;
   }
   Kernels K;
   ACF_RET(get_kernels(c, &K));
-  const int SW = (3 * c->B + K.slots_per_wave - 1) / K.slots_per_wave;
+  const StepWaves W = step_waves(c, K);
+  Launcher L{s};
   StepArgs a = make_args(c, tb, hp, t, 0);
-  a.slot_waves = SW;
-  ACF_RET(launch(K.clean_apr, a, SW, s));
+  a.slot_waves = W.per_slot;
+  ACF_RET(L.launch(K.clean_apr, a, W.per_slot, KIND_CLEAN));
   c->last_delta_batch = t;
   return ACF_OK;
 }
@@ -3231,26 +3268,19 @@ extern "C" int acf_apr_optimizer_step(acf_apr_ctx* c, const acf_apr_tables* tb,
   ACF_RET(check_step(c, tb, hp, t));
   ACF_RET(resolve(c, 2));  // settle queued streamed calls first (FailGroup)
   hipStream_t s = static_cast<hipStream_t>(stream_);
-  if (c->tri) {  // triplet-centric plan: its adversarial (or BPR) phase, rows in place
-    ACF_CHECK(!hp->adver || c->last_delta_batch == t, ACF_E_STATE,
-              "APR optimizer step on batch %d needs acf_apr_delta_update on the same batch first", t);
-    return run_loop(c, tb, hp, t, 1, s, nullptr, nullptr, 0, 2);
-  }
+  ACF_CHECK(!hp->adver || c->last_delta_batch == t, ACF_E_STATE,
+            "APR optimizer step on batch %d needs acf_apr_delta_update on the same batch first", t);
+  // triplet-centric plan: its adversarial (or BPR) phase, rows in place
+  if (c->tri) return run_loop(c, tb, hp, t, 1, s, nullptr, nullptr, false, PHASE_STEP);
   Kernels K;
   ACF_RET(get_kernels(c, &K));
-  const int SW = (3 * c->B + K.slots_per_wave - 1) / K.slots_per_wave;
+  const StepWaves W = step_waves(c, K);
+  Launcher L{s};
   StepArgs a = make_args(c, tb, hp, t, 0);
-  a.slot_waves = SW;
-  if (hp->adver) {
-    ACF_CHECK(c->last_delta_batch == t, ACF_E_STATE,
-              "APR optimizer step on batch %d needs acf_apr_delta_update on the same batch first", t);
-    ACF_RET(launch(K.adv, a, SW, s));
-  } else {
-    ACF_RET(launch(K.clean_bpr, a, SW, s));
-  }
-  a.slot_waves = 3 * c->B;
-  ACF_RET(launch(K.flush, a, 3 * c->B, s));
-  return ACF_OK;
+  a.slot_waves = W.per_slot;
+  ACF_RET(L.launch(hp->adver ? K.adv : K.clean_bpr, a, W.per_slot, hp->adver ? KIND_ADV : KIND_CLEAN));
+  a.slot_waves = W.S;
+  return L.launch(K.flush, a, W.S, KIND_FLUSH);
 }
 
 extern "C" int acf_apr_train_planned(acf_apr_ctx* c, const acf_apr_tables* tb,
@@ -3276,7 +3306,7 @@ extern "C" int acf_apr_train_planned(acf_apr_ctx* c, const acf_apr_tables* tb,
   key.hp = *hp;
   key.first = first; key.n = n; key.B = c->B; key.d = c->d; key.mapping = c->mapping;
   key.fusion = c->fusion;
-  key.ovl = c->stream;
+  key.stream = c->stream;
   auto it = c->graphs.find(key);
   if (it == c->graphs.end()) {
     hipGraph_t g = nullptr;
@@ -3306,8 +3336,11 @@ extern "C" int acf_apr_train(acf_apr_ctx* c, const acf_apr_tables* tb, const acf
   return acf_apr_train_planned(c, tb, hp, 0, nb, graph_mode, stream_);
 }
 
-static int time_kernels(acf_apr_ctx* c, const acf_apr_tables* tb, const acf_apr_hparams* hp, int32_t first,
-                        int32_t n, double* ms_out, int32_t* launches_out, void* stream_, int nkinds) {
+// per-kind launch times of the launch sequence acf_apr_train_planned runs
+// (kinds: see Launcher; include/acf_apr.h)
+extern "C" int acf_apr_time_kernels(acf_apr_ctx* c, const acf_apr_tables* tb,
+                                    const acf_apr_hparams* hp, int32_t first, int32_t n,
+                                    double* ms_out, int32_t* launches_out, void* stream_) {
   ACF_CHECK(c && tb && hp && ms_out && launches_out, ACF_E_INVALID, "NULL argument");
   ACF_RET(resolve(c, 2));
   ACF_CHECK(n > 0 && first >= 0 && first + n <= c->nb, ACF_E_INVALID,
@@ -3319,11 +3352,11 @@ static int time_kernels(acf_apr_ctx* c, const acf_apr_tables* tb, const acf_apr_
   std::vector<hipEvent_t> ev((size_t)2 * nl, nullptr);
   std::vector<int> kinds(nl, -1);
   for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-  int r = run_loop(c, tb, hp, first, n, s, ev.data(), kinds.data(), nkinds > 4 ? 2 : (nkinds > 3 ? 1 : 0));
+  int r = run_loop(c, tb, hp, first, n, s, ev.data(), kinds.data());
   if (r == ACF_OK && hipStreamSynchronize(s) != hipSuccess) r = acf_set_error(ACF_E_HIP, "sync failed");
-  for (int k = 0; k < nkinds; ++k) { ms_out[k] = 0.0; launches_out[k] = 0; }
+  for (int k = 0; k < N_KINDS; ++k) { ms_out[k] = 0.0; launches_out[k] = 0; }
   for (int x = 0; r == ACF_OK && x < nl; ++x) {
-    if (kinds[x] < 0 || kinds[x] >= nkinds) continue;
+    if (kinds[x] < 0) continue;  // not launched
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, ev[2 * x], ev[2 * x + 1]) != hipSuccess) {
       r = acf_set_error(ACF_E_HIP, "hipEventElapsedTime failed");
@@ -3335,14 +3368,6 @@ static int time_kernels(acf_apr_ctx* c, const acf_apr_tables* tb, const acf_apr_
   for (auto& e : ev) (void)hipEventDestroy(e);
   c->last_delta_batch = -1;
   return r;
-}
-
-// per-kind launch times of the launch sequence acf_apr_train_planned runs
-// (kinds: see run_loop; include/acf_apr.h)
-extern "C" int acf_apr_time_kernels(acf_apr_ctx* c, const acf_apr_tables* tb,
-                                    const acf_apr_hparams* hp, int32_t first, int32_t n,
-                                    double* ms_out, int32_t* launches_out, void* stream_) {
-  return time_kernels(c, tb, hp, first, n, ms_out, launches_out, stream_, 6);
 }
 
 extern "C" int acf_apr_set_slot_mapping(acf_apr_ctx* c, int32_t mode) {
@@ -3416,76 +3441,46 @@ extern "C" int acf_apr_shard_pass_export(acf_apr_ctx* c, const acf_apr_tables* t
   ACF_CHECK((xbuf == nullptr) == (xmap == nullptr), ACF_E_INVALID, "xbuf and xmap go together");
   ACF_CHECK(n_items >= 0 && n_items <= 2 * (int64_t)c->B, ACF_E_INVALID, "n_items %lld outside [0, 2B]",
             (long long)n_items);
-  hipStream_t s = static_cast<hipStream_t>(stream_);
   Kernels K;
   ACF_RET(get_kernels(c, &K, 0));
   ACF_CHECK(K.lists, ACF_E_STATE, "shard mode needs the list kernels");
-  const int S = 3 * c->B;
-  const int SW = std::min((S + K.slots_per_wave - 1) / K.slots_per_wave, ACF_LIST_WAVES);
-  const int HW = std::min(c->hot.piece_stride, ACF_HOT_WAVES);
-  const int HB = std::min(c->hot.hot_stride, ACF_HOT_BLOCKS);
+  const StepWaves W = step_waves(c, K);
+  Launcher L{static_cast<hipStream_t>(stream_)};
+  const bool users_done = pass == 1 || !hp->adver;  // this pass updates the user rows
   if (K.tri) {
-    // (r05) triplet-centric shard passes (hash plan): the triplet pass (a single
-    // item's product goes straight to its exchange row), then k_tri_combine,
-    // whose item slots store their partial sums there too and whose user slots
-    // finish as in the unsharded step (delta; Adagrad in place).  Pass 1 reads
-    // the owners' item deltas from the exchange rows (acf_apr_shard_items_mapped
-    // dir 1 names them).
+    // (r05) triplet-centric shard passes (hash plan), batch shard_t of the plan:
+    // the triplet pass (a single item's product goes straight to its exchange
+    // row), then k_tri_combine, whose item slots store their partial sums there
+    // too and whose user slots finish as in the unsharded step (delta; Adagrad in
+    // place).  Pass 1 reads the owners' item deltas from the exchange rows
+    // (acf_apr_shard_items_mapped dir 1 names them).
     ACF_CHECK(xbuf, ACF_E_INVALID, "triplet-centric shard passes export their item sums: xbuf is required");
     ACF_CHECK(pass == 0 || c->xdelta, ACF_E_STATE, "pass 1 needs the owners' deltas (acf_apr_shard_items_mapped)");
-    const int SW4 = (std::min(SW, ACF_TRI_COMB_WAVES) + 3) & ~3, HW4 = (HW + 3) & ~3;
-    const int HBT = std::min(HB, ACF_TRI_HOT_BLOCKS);
-    const int TWT = (c->B + 64 / c->lpr - 1) / (64 / c->lpr);
-    const int TW = (TWT + tri_gpw(c->nv) - 1) / tri_gpw(c->nv);
-    StepArgs a = make_args(c, tb, hp, c->shard_t, 0);  // batch shard_t of the plan
-    a.use_single = 1;
-    a.xbuf = xbuf;
-    a.xmap = xmap;
-    a.xn = (int32_t)n_items;
-    StepArgs at = a, ac = a;
-    at.slot_waves = 0;
-    ac.slot_waves = SW4;
-    ac.hot_waves = HW4;
-    ac.hot_blocks = HBT;
-    if (pass == 0) {
-      ACF_RET(launch(hp->adver ? K.tri_clean : K.tri_clean_bpr, at, TW, s));
-      ACF_RET(launch(K.tri_comb[hp->adver ? 0 : 1], ac, SW4 + HW4 + 4 * HBT, s));
-    } else {
-      ACF_RET(launch(K.tri_adv, a, TW, s));
-      ACF_RET(launch(K.tri_comb[2], ac, SW4 + HW4 + 4 * HBT, s));
-    }
-    return ACF_OK;
+    return run_tri_batch(c, tb, hp, c->shard_t, users_done ? PHASE_STEP : PHASE_CLEAN, L, K, W, xbuf, xmap,
+                         (int32_t)n_items);
   }
   ACF_CHECK(c->nb == 1 && c->shard_t == 0, ACF_E_STATE, "slot-kernel shard passes take one-batch plans");
   StepArgs a = make_args(c, tb, hp, 0, 0);
-  a.use_single = 0;
-  a.slot_waves = SW;
-  a.hot_waves = HW;
-  if (pass == 0) {
-    ACF_RET(launch(hp->adver ? K.clean_apr : K.clean_bpr, a, SW + HW, s));
-  } else {
-    ACF_RET(launch(K.adv, a, SW + HW, s));
-  }
-  StepArgs ah = a;
+  a.hot_waves = W.hot;
   int XB = 0;
-  const bool users_done = pass == 1 || !hp->adver;  // this pass updates the user rows
-  if (xbuf) {  // export (and write-back) workgroups after the combining ones
+  if (xbuf) {  // export (and write-back) workgroups after the combining ones (read by k_hot_combine alone)
     const int XF = users_done ? (c->B * c->lpr + 255) / 256 : 0;  // one lane-group per user slot
     XB = (int)((n_items * c->lpr + 255) / 256) + XF;                 // one lane-group per item slot
-    ah.xbuf = xbuf;
-    ah.xmap = xmap;
-    ah.xubs = c->ubs;
-    ah.xibs = c->ibs;
-    ah.xn = (int32_t)n_items;
-    ah.xblocks = XB;
-    ah.xflush = XF;
+    a.xbuf = xbuf;
+    a.xmap = xmap;
+    a.xubs = c->ubs;
+    a.xibs = c->ibs;
+    a.xn = (int32_t)n_items;
+    a.xblocks = XB;
+    a.xflush = XF;
   }
-  ah.slot_waves = 4 * (HB + XB);  // k_hot_combine: workgroups stride over the hot slots
-  ACF_RET(launch(pass == 1 ? K.hot_adv : (hp->adver ? K.hot_clean : K.hot_bpr), ah, 4 * (HB + XB), s));
+  if (pass == 1) ACF_RET(slot_pass(L, K, W, a, K.adv, 0, KIND_ADV, K.hot_adv, XB));
+  else if (hp->adver) ACF_RET(slot_pass(L, K, W, a, K.clean_apr, 0, KIND_CLEAN, K.hot_clean, XB));
+  else ACF_RET(slot_pass(L, K, W, a, K.clean_bpr, 0, KIND_CLEAN, K.hot_bpr, XB));
   if (users_done && !xbuf) {  // user rows W scratch -> the user shard
-    a.slot_waves = S;
+    a.slot_waves = W.S;
     a.hot_waves = 0;
-    ACF_RET(launch(K.flush, a, S, s));
+    ACF_RET(L.launch(K.flush, a, W.S, KIND_FLUSH));
   }
   return ACF_OK;
 }

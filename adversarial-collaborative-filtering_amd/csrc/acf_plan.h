@@ -145,7 +145,7 @@ static __device__ int g_stamp_cap = 0;
 struct GraphKey {
   const void* ptrs[4];
   acf_apr_hparams hp;
-  int32_t first, n, B, d, mapping, fusion, ovl;
+  int32_t first, n, B, d, mapping, fusion, stream;  // stream: the context's k_stream switch
   bool operator<(const GraphKey& o) const { return memcmp(this, &o, sizeof(GraphKey)) < 0; }
 };
 

@@ -582,7 +582,90 @@ def test_degenerate_batches_at_padded_geometries(ops, oracle, dev, d, case, stre
 
 
 # ---------------------------------------------------------------------------
-# 9. CPU guard: D still covers the dispatch table
+# 9. the launch sequence of the triplet-centric schedule
+def _tri_problem(seed, U1, I1, d, B, nb):
+    u, i, j = _sparse_stream(seed, U1, I1, B, nb, hot=16, p_hot=0.3)  # some slots exceed 8 occurrences
+    rng = np.random.default_rng(d)
+    P = (rng.standard_normal((U1, d)) * 0.2).astype(np.float32)
+    Q = (rng.standard_normal((I1, d)) * 0.2).astype(np.float32)
+    return P, Q, u, i, j
+
+
+def _bits(ctx, tabs):
+    lc, la = ctx.losses()
+    assert ctx.step_errors() == 0
+    return tabs + [lc.clone(), la.clone()]
+
+
+def _same_bits(base, other, what):
+    torch.cuda.synchronize()
+    for x, y, n in zip(base, other, NAMES + ("loss_clean", "loss_adv")):
+        assert torch.equal(x, y), (what, n)
+
+
+@gpu
+@pytest.mark.parametrize("adver", [1, 0])
+@pytest.mark.parametrize("d", [64, 20])
+def test_sort_plan_triplet_launch_sequence(ops, dev, d, adver):
+    """Mapping "group", B = 128, fusion on, set_plan_mode("sort") (left to
+    itself the context builds a hash plan here too): a triplet-centric sort
+    plan.  Per batch a triplet pass and a combine per phase (APR: two phases),
+    one flush per call, no streamed launch; time_kernels, train_planned and the
+    two-phase API batch by batch leave the same bits."""
+    U1, I1, B, nb = 300, 200, 128, 3
+    P, Q, u, i, j = _tri_problem(d + 9, U1, I1, d, B, nb)
+    assert max(np.bincount(np.concatenate([i[t * B:(t + 1) * B], j[t * B:(t + 1) * B]])).max() for t in range(nb)) > 8
+    hp = ops.StepHParams(adver=adver, reg=0.01)
+    ctx = ops.APRContext(U1, I1, d, B, nb, dev)
+    ctx.set_slot_mapping("group")
+    ctx.set_plan_mode("sort")
+    ctx.plan(*_dev_triplets(u, i, j, dev), B)
+    assert ctx.plan_kind() == "sort"
+    tabs = _gpu_tables(P, Q, dev)
+    ctx.train_planned(tabs, hp, graph=False)
+    base = _bits(ctx, tabs)
+    tabs = _gpu_tables(P, Q, dev)
+    kinds = {k: v[1] for k, v in ctx.time_kernels(tabs, hp).items()}
+    want = ({"clean": nb, "hot": 2 * nb, "adv": nb, "flush": 1, "stream": 0} if adver else
+            {"clean": nb, "hot": nb, "adv": 0, "flush": 1, "stream": 0})
+    assert kinds == want, kinds
+    _same_bits(base, _bits(ctx, tabs), "time_kernels")
+    tabs = _gpu_tables(P, Q, dev)
+    for t in range(nb):
+        if adver:
+            ctx.delta_update(tabs, hp, t)
+        ctx.optimizer_step(tabs, hp, t)
+    _same_bits(base, _bits(ctx, tabs), "two-phase API")
+
+
+@gpu
+def test_hash_plan_triplet_launch_sequence(ops, dev):
+    """B = 4,096 (the smallest batch the auto mapping packs), d = 64: a hash
+    plan.  A whole step is three launches per batch (k_tri_clean, k_tri_cadv =
+    the clean combine + the adversarial pass, the second combine); the two-phase
+    API on the same plan runs the four-launch batch and leaves the same bits."""
+    U1, I1, d, B, nb = 30000, 20000, 64, 4096, 2
+    P, Q, u, i, j = _tri_problem(4096, U1, I1, d, B, nb)
+    hp = ops.StepHParams(adver=1, reg=0.01)
+    ctx = ops.APRContext(U1, I1, d, B, nb, dev)
+    ctx.plan(*_dev_triplets(u, i, j, dev), B)
+    assert ctx.plan_kind() == "hash"
+    tabs = _gpu_tables(P, Q, dev)
+    ctx.train_planned(tabs, hp, graph=False)
+    base = _bits(ctx, tabs)
+    tabs = _gpu_tables(P, Q, dev)
+    kinds = {k: v[1] for k, v in ctx.time_kernels(tabs, hp).items()}
+    assert kinds == {"clean": nb, "adv": nb, "hot": nb, "flush": 1, "stream": 0}, kinds
+    _same_bits(base, _bits(ctx, tabs), "time_kernels")
+    tabs = _gpu_tables(P, Q, dev)
+    for t in range(nb):
+        ctx.delta_update(tabs, hp, t)
+        ctx.optimizer_step(tabs, hp, t)
+    _same_bits(base, _bits(ctx, tabs), "two-phase API")
+
+
+# ---------------------------------------------------------------------------
+# 10. CPU guard: D still covers the dispatch table
 def test_calibrated_bars_come_from_the_oracle_alone(oracle):
     """The float64 restatement agrees with the fp32 oracle within the project's
     bar wherever d < 1024, so those cases keep that bar; the two calibrated bars
