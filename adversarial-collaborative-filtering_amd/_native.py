@@ -62,6 +62,7 @@ SIGNATURES = {
     "acf_apr_step_errors": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int32), _P]),
     "acf_apr_set_failsafe": (ctypes.c_int, [_P, _I32]),
     "acf_apr_set_spin_limit": (ctypes.c_int, [_P, _I32]),
+    "acf_apr_set_poll_sleep": (ctypes.c_int, [_P, _I32]),
     "acf_apr_stream_recoveries": (ctypes.c_int, [_P, ctypes.POINTER(_I64)]),
     "acf_apr_resolve": (ctypes.c_int, [_P]),
     "acf_apr_resolve_all": (ctypes.c_int, []),

@@ -54,6 +54,7 @@
 #include <map>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <mutex>
 #include <vector>
 
@@ -211,6 +212,53 @@ struct StepArgs {
   uint64_t seed;
 };
 
+// k_stream's own arguments: what the streamed step reads and nothing else (the
+// shared StepArgs kept well over a hundred scalar registers live through every
+// task of the launch and the kernel spilled them).  Field names are StepArgs's, so
+// the row helpers shared with the two-kernel step (slot_header, occ_rec, occ_term,
+// make_delta, adagrad_row) take either struct; the batch a task works on is
+// passed beside the struct.  k_stream_flush keeps StepArgs.
+struct StreamArgs {
+  float* P;
+  float* Q;
+  float* accP;
+  float* accQ;
+  const OccRec* inl;
+  const OccRec* urec;
+  const OccRec* irec;
+  const OccRec* trec;
+  float* loss_clean;
+  float* loss_adv;
+  const int32_t* gen_ptr;
+  unsigned long long* ver_w;
+  unsigned long long* ver_a;
+  unsigned long long* ver_d;
+  const int32_t* task_list;
+  const int32_t* task_cnt;
+  int32_t* fail;
+  int32_t d, B, S, R, kb;
+  int32_t Sd;  // S * d: granules of one batch's versions (the host checks that it fits)
+  int32_t first, t_end, task_stride, max_depth, spin_limit, reg_B;
+  uint32_t seq;
+  float lr, eps, reg, reg_adv, clip_lo, clip_hi;
+  // the launch's end (stream_tail): read once, before or after the tasks
+  int32_t* gate;
+  int32_t* step_err;
+  unsigned long long* decide;
+  unsigned long long decide_prev;
+  unsigned long long* arrive;
+  const int2* final_list;
+  const int32_t* final_cnt;
+  unsigned long long* status;
+  const uint32_t* epoch;
+  int32_t verify, tail, tail_par, flushers;
+  // what only the general instance (k_stream_any) reads: the default one has them folded
+  int32_t use_single, poll_sleep, adv_mode, zero_delta;
+  uint64_t seed;
+  unsigned long long* tail_diag;
+  static constexpr int32_t adver = 1;  // the streamed step is the APR step (use_stream)
+};
+
 // An OccRec as three int4 registers (kept in VGPRs; a struct of scalars passed
 // by reference got demoted to scratch).  Field order as in OccRec.
 struct RecV {
@@ -285,13 +333,15 @@ struct SlotRec {
 // Records m and m + TEAM of slot k (those < R; both addresses are known up
 // front, so a slot of up to 2 TEAM occurrences needs no CSR hop) and the slot
 // header broadcast from the team leader's lane.
-template <int LPR, int TEAM>
-__device__ __forceinline__ SlotRec slot_header(const StepArgs& a, int k, int m, int leader_lane) {
+// (t: the batch; use_single: fused triplets' slots are skipped; A: StepArgs or StreamArgs)
+template <int LPR, int TEAM, class A>
+__device__ __forceinline__ SlotRec slot_header_at(const A& a, int32_t t, int use_single, int k, int m,
+                                                  int leader_lane) {
   const int32_t gen = *a.gen_ptr;
   SlotRec s;
   s.r0.a = s.r0.b = s.r0.c = make_int4(0, 0, 0, -1);
   s.r1 = s.r0;
-  const OccRec* base = a.inl + ((int64_t)a.t * a.S + k) * a.R;
+  const OccRec* base = a.inl + ((int64_t)t * a.S + k) * a.R;
   if (m < a.R && k < a.S) s.r0 = load_rec(base + m);
   if (m + TEAM < a.R && k < a.S) s.r1 = load_rec(base + m + TEAM);
   s.r0_valid = s.r0.gen() == gen;
@@ -303,7 +353,7 @@ __device__ __forceinline__ SlotRec slot_header(const StepArgs& a, int k, int m, 
   };
   const int32_t meta = from_leader(s.r0_valid ? s.r0.meta() : 0);
   // a fused triplet's slots are handled by its k_single lane-group
-  s.h.count = (a.use_single && (meta & ACF_SINGLE_BIT)) ? 0 : (meta & ACF_COUNT_MASK);
+  s.h.count = (use_single && (meta & ACF_SINGLE_BIT)) ? 0 : (meta & ACF_COUNT_MASK);
   s.h.is_item = (meta & ACF_ITEM_BIT) != 0;
   s.h.own_row = from_leader(s.r0.own_row());
   s.h.own_src = from_leader(s.r0.own_src());
@@ -311,10 +361,15 @@ __device__ __forceinline__ SlotRec slot_header(const StepArgs& a, int k, int m, 
   return s;
 }
 
+template <int LPR, int TEAM>
+__device__ __forceinline__ SlotRec slot_header(const StepArgs& a, int k, int m, int leader_lane) {
+  return slot_header_at<LPR, TEAM>(a, a.t, a.use_single, k, m, leader_lane);
+}
+
 // record of occurrence idx of the slot (idx < count): the member's inline
 // records for occurrences m and m + TEAM, the CSR records otherwise
-template <int TEAM>
-__device__ __forceinline__ RecV occ_rec(const StepArgs& a, const SlotRec& s, int idx, int m) {
+template <int TEAM, class A>
+__device__ __forceinline__ RecV occ_rec(const A& a, const SlotRec& s, int idx, int m) {
   if (idx == m && m < a.R && s.r0_valid) return s.r0;
   if (idx == m + TEAM && m + TEAM < a.R && s.r1_valid) return s.r1;
   return load_rec((s.h.is_item ? a.irec : a.urec) + s.h.ovf + idx);
@@ -322,20 +377,27 @@ __device__ __forceinline__ RecV occ_rec(const StepArgs& a, const SlotRec& s, int
 
 // record of occurrence idx of slot k re-read from memory (inline or CSR): the
 // streamed step's hot-row passes, which keep no records in registers
-__device__ __forceinline__ RecV occ_rec_mem(const StepArgs& a, const SlotHdr& h, int k, int idx) {
-  if (idx < a.R) return load_rec(a.inl + ((int64_t)a.t * a.S + k) * a.R + idx);
+template <class A>
+__device__ __forceinline__ RecV occ_rec_mem(const A& a, int32_t t, const SlotHdr& h, int k, int idx) {
+  if (idx < a.R) return load_rec(a.inl + ((int64_t)t * a.S + k) * a.R + idx);
   return load_rec((h.is_item ? a.irec : a.urec) + h.ovf + idx);
+}
+
+__device__ __forceinline__ RecV occ_rec_mem(const StepArgs& a, const SlotHdr& h, int k, int idx) {
+  return occ_rec_mem(a, a.t, h, k, idx);
 }
 
 // One occurrence's BPR term (APR.py:127-150) against the slot's own row (clean,
 // or own + delta for the adversarial loss) and the partner rows ra / rb; the
 // gradient w.r.t. the own row goes into G, the loss to loss[e] (or to *keep,
-// for the caller to store later).
-template <int LPR, int NV>
-__device__ __forceinline__ void occ_term(const StepArgs& a, int is_item, const RowV<NV>& own, const RecV& r,
+// for the caller to store later; or, xkeep, only the clipped argument is kept
+// and the caller evaluates bpr_loss of it later: the same function of the same
+// input, and the softplus chain leaves this place).
+template <int LPR, int NV, class A>
+__device__ __forceinline__ void occ_term(const A& a, int is_item, const RowV<NV>& own, const RecV& r,
                                          const RowV<NV>& ra, const RowV<NV>& rb, bool active, int l,
                                          float* __restrict__ loss_out, RowV<NV>& G, float* keep = nullptr,
-                                         float* gkeep = nullptr) {
+                                         float* gkeep = nullptr, float* xkeep = nullptr) {
   float gb, loss;
   if (!is_item) {
     const float x = dot_row<LPR, NV>(own, ra) - dot_row<LPR, NV>(own, rb);
@@ -344,7 +406,8 @@ __device__ __forceinline__ void occ_term(const StepArgs& a, int is_item, const R
     if (active) {
       axpy_row(G, gb, ra);   // pos branch: dx+/dp = q_i
       axpy_row(G, -gb, rb);  // neg branch: dx-/dp = q_j
-      if (keep) *keep = loss;
+      if (xkeep) *xkeep = bpr_clip(x, a.clip_lo, a.clip_hi);
+      else if (keep) *keep = loss;
       else if (l == 0) loss_out[r.e_role()] = loss;
     }
   } else {
@@ -406,8 +469,8 @@ __device__ __forceinline__ void flush_store(const FlushOp& f) {
 
 // Adagrad (TF SparseApplyAdagrad after the dedup) for one row held by a
 // lane-group, plus the reg*mean(w^2) terms of APR.py:153-154,164-165.
-template <int NV>
-__device__ __forceinline__ void adagrad_row(const StepArgs& a, RowV<NV>& G, const RowV<NV>& w,
+template <int NV, class A>
+__device__ __forceinline__ void adagrad_row(const A& a, RowV<NV>& G, const RowV<NV>& w,
                                             RowV<NV>& acc, int m, RowV<NV>& wout) {
   if (a.reg != 0.f) {
     const float coef = (2.0f * a.reg / ((float)a.reg_B * (float)a.d)) * (float)(a.adver ? 2 * m : m);
@@ -504,19 +567,22 @@ struct Geo {
 };
 
 // delta of one row from its batch-summed clean gradient G (APR.py:180-191)
+// (t: the batch, a key of the random delta; A: StepArgs or StreamArgs)
+template <int LPR, int NV, class A>
+__device__ __forceinline__ RowV<NV> make_delta_at(const A& a, int32_t t, const RowV<NV>& G, int is_item,
+                                                  int32_t row, int l) {
+  if (a.zero_delta) return zero_row<NV>();
+  // tf.nn.l2_normalize(g, 1) * eps  (epsilon 1e-12 on the squared norm)
+  if (a.adv_mode == 0) return l2_delta<LPR, NV>(G, a.eps);
+  // keyed on the context's call counter too (advanced by every call's write-back
+  // kernel), so every run draws fresh noise, as truncated_normal does per sess.run
+  return random_delta<LPR, NV>(a.seed, *a.epoch, t, a.d, a.eps, is_item, row, l);
+}
+
 template <int LPR, int NV>
 __device__ __forceinline__ RowV<NV> make_delta(const StepArgs& a, const RowV<NV>& G, int is_item,
                                                int32_t row, int l) {
-  if (a.zero_delta) return zero_row<NV>();
-  if (a.adv_mode == 0) {
-    // tf.nn.l2_normalize(g, 1) * eps  (epsilon 1e-12 on the squared norm)
-    const float ss = dot_row<LPR, NV>(G, G);
-    const float inv = __builtin_amdgcn_rsqf(fmaxf(ss, 1e-12f));
-    return scale_row(scale_row(G, inv), a.eps);
-  }
-  // keyed on the context's call counter too (advanced by every call's write-back
-  // kernel), so every run draws fresh noise, as truncated_normal does per sess.run
-  return random_delta<LPR, NV>(a.seed, *a.epoch, a.t, a.d, a.eps, is_item, row, l);
+  return make_delta_at<LPR, NV>(a, a.t, G, is_item, row, l);
 }
 
 // A fused triplet (fuse_info, acf_plan.hip): its whole step in one lane-group.  The operation
@@ -793,15 +859,21 @@ __device__ __forceinline__ const u64* vrow(const u64* base, const StepArgs& a, i
   return base + ((int64_t)t * a.S + k) * a.d;
 }
 
-// where the value of a row at the start of batch a.t lives, as ONE 64-bit word:
+// the same row through k_stream's precomputed stride: one 32 x 32 -> 64 multiply-add
+// (k * d < S * d = Sd fits 31 bits)
+__device__ __forceinline__ const u64* vrow(const u64* base, const StreamArgs& a, int32_t t, int32_t k) {
+  return base + ((int64_t)t * a.Sd + k * a.d);
+}
+
+// where the value of a row at the start of batch t lives, as ONE 64-bit word:
 // the table row's address, or a version row's address | 1 (a version of an
 // earlier batch of this launch)
 typedef uint64_t VSrc;
 
-__device__ __forceinline__ VSrc ver_src(const StepArgs& a, const float* table, const u64* vbase, int32_t row,
-                                        int32_t src) {
+__device__ __forceinline__ VSrc ver_src(const StreamArgs& a, int32_t t, const float* table, const u64* vbase,
+                                        int32_t row, int32_t src) {
   if (src < 0) {
-    const int32_t tp = a.t - src_dt(src, a.kb);
+    const int32_t tp = t - src_dt(src, a.kb);
     if (tp >= a.first) return (VSrc)(uintptr_t)vrow(vbase, a, tp, src_slot(src, a.kb)) | 1ull;
   }
   return (VSrc)(uintptr_t)(table + (int64_t)row * a.d);
@@ -831,7 +903,9 @@ __device__ __forceinline__ void store_ver(u64* dst, int d, int l, const RowV<NV>
 }
 
 // wave-uniform end of a wait round: true = stop (all there, or give up)
-__device__ __forceinline__ bool wait_round(const StepArgs& a, bool ok, int it) {
+// (GEN: the general instance k_stream_any; the default one sleeps ACF_POLL_SLEEP)
+template <bool GEN>
+__device__ __forceinline__ bool wait_round(const StreamArgs& a, bool ok, int it) {
   if (__all(ok)) return true;
   if (it >= a.spin_limit) {
     if ((threadIdx.x & 63) == 0)
@@ -841,6 +915,11 @@ __device__ __forceinline__ bool wait_round(const StepArgs& a, bool ok, int it) {
   if ((it & 31) == 31 &&
       __any(__hip_atomic_load(a.fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int32_t)a.seq))
     return true;  // another wave gave up: the launch is failing, drain it
+  if constexpr (!GEN) {
+    static_assert(ACF_POLL_SLEEP == 2, "wait_round: the default sleep is the switch's default case");
+    __builtin_amdgcn_s_sleep(ACF_POLL_SLEEP);
+    return false;
+  }
   switch (a.poll_sleep) {  // s_sleep takes an immediate
     case 0: break;
     case 1: __builtin_amdgcn_s_sleep(1); break;
@@ -923,8 +1002,8 @@ __device__ __forceinline__ void check_row(VSrc s, int d, int l, uint32_t tag, co
 }
 
 // Wait until every listed row is there (ok[k] true on entry: not needed).
-template <int LPR, int NV, int K>
-__device__ __forceinline__ void poll_rows(const StepArgs& a, const VSrc (&s)[K], RowV<NV>* const (&r)[K],
+template <int LPR, int NV, int K, bool GEN>
+__device__ __forceinline__ void poll_rows(const StreamArgs& a, const VSrc (&s)[K], RowV<NV>* const (&r)[K],
                                           bool (&ok)[K], uint32_t tag, int l) {
   for (int it = 0;; ++it) {
     RawRow<NV> w[K];
@@ -936,24 +1015,33 @@ __device__ __forceinline__ void poll_rows(const StepArgs& a, const VSrc (&s)[K],
       check_row<LPR, NV>(s[k], a.d, l, tag, w[k], *r[k], ok[k]);
       all = all && ok[k];
     }
-    if (wait_round(a, all, it)) break;
+    if (wait_round<GEN>(a, all, it)) break;
   }
 }
 
 // Partner rows of the member's two occurrences of a pass (batch-start values)
-template <int LPR, int NV>
-__device__ __forceinline__ void stream_partners(const StepArgs& a, int is_item, const RecV& r0, const RecV& r1,
-                                                bool a0, bool a1, uint32_t tag, int l, RowV<NV>& ra0,
-                                                RowV<NV>& rb0, RowV<NV>& ra1, RowV<NV>& rb1) {
+template <int LPR, int NV, bool GEN>
+__device__ __forceinline__ void stream_partners(const StreamArgs& a, int32_t t, int is_item, const RecV& r0,
+                                                const RecV& r1, bool a0, bool a1, uint32_t tag, int l,
+                                                RowV<NV>& ra0, RowV<NV>& rb0, RowV<NV>& ra1, RowV<NV>& rb1) {
   const float* ptab = is_item ? a.P : a.Q;
-  const VSrc sa0 = a0 ? ver_src(a, ptab, a.ver_w, r0.pa_row(), r0.pa_src()) : 0;
-  const VSrc sb0 = a0 ? ver_src(a, a.Q, a.ver_w, r0.pb_row(), r0.pb_src()) : 0;
-  const VSrc sa1 = a1 ? ver_src(a, ptab, a.ver_w, r1.pa_row(), r1.pa_src()) : 0;
-  const VSrc sb1 = a1 ? ver_src(a, a.Q, a.ver_w, r1.pb_row(), r1.pb_src()) : 0;
+  const VSrc sa0 = a0 ? ver_src(a, t, ptab, a.ver_w, r0.pa_row(), r0.pa_src()) : 0;
+  const VSrc sb0 = a0 ? ver_src(a, t, a.Q, a.ver_w, r0.pb_row(), r0.pb_src()) : 0;
+  const VSrc sa1 = a1 ? ver_src(a, t, ptab, a.ver_w, r1.pa_row(), r1.pa_src()) : 0;
+  const VSrc sb1 = a1 ? ver_src(a, t, a.Q, a.ver_w, r1.pb_row(), r1.pb_src()) : 0;
   const VSrc src[4] = {sa0, sb0, sa1, sb1};
   RowV<NV>* const dst[4] = {&ra0, &rb0, &ra1, &rb1};
   bool ok[4] = {!a0, !a0, !a1, !a1};
-  poll_rows<LPR, NV, 4>(a, src, dst, ok, tag, l);
+  poll_rows<LPR, NV, 4, GEN>(a, src, dst, ok, tag, l);
+}
+
+// make_delta of the streamed step: the default instance forms the gradient delta
+// (make_delta_at's adv_mode 0 branch) without testing the launch's modes
+template <int LPR, int NV, bool GEN>
+__device__ __forceinline__ RowV<NV> stream_delta(const StreamArgs& a, int32_t t, const RowV<NV>& G, int is_item,
+                                                 int32_t row, int l) {
+  if constexpr (GEN) return make_delta_at<LPR, NV>(a, t, G, is_item, row, l);
+  else return l2_delta<LPR, NV>(G, a.eps);
 }
 
 // Delta of a SOLO partner (pb = 0: pa, 1: pb) of one occurrence, formed here
@@ -966,8 +1054,8 @@ __device__ __forceinline__ void stream_partners(const StepArgs& a, int is_item, 
 // same bits and the dots and the loss chain need not run again.  (Forming both
 // partners' deltas in one straight-line block, with the published-delta loads
 // issued before it, measured slower: 4.56 vs 4.37 us per batch.)
-template <int LPR, int NV, int TEAM>
-__device__ __forceinline__ RowV<NV> solo_delta(const StepArgs& a, int is_item, const RowV<NV>& own,
+template <int LPR, int NV, int TEAM, bool GEN>
+__device__ __forceinline__ RowV<NV> solo_delta(const StreamArgs& a, int32_t t, int is_item, const RowV<NV>& own,
                                                const RecV& r, const RowV<NV>& ra, const RowV<NV>& rb, int pb,
                                                int l, const float* gk = nullptr) {
   float gb, loss;
@@ -997,57 +1085,59 @@ __device__ __forceinline__ RowV<NV> solo_delta(const StepArgs& a, int is_item, c
   }
 #pragma unroll
   for (int s = 1; s < TEAM; s <<= 1) G = add_row(G, zero_row<NV>());
-  return make_delta<LPR, NV>(a, G, p_item, pb ? r.pb_row() : r.pa_row(), l);
+  return stream_delta<LPR, NV, GEN>(a, t, G, p_item, pb ? r.pb_row() : r.pa_row(), l);
 }
 
 // Adversarial terms of one pass: partner rows (batch-start values) plus their
 // deltas: formed here for a solo partner, otherwise the one its clean half
 // publishes in this batch (wait for it).
-template <int LPR, int NV, int TEAM>
-__device__ __forceinline__ void stream_adv_pass(const StepArgs& a, int is_item, const RowV<NV>& own,
+template <int LPR, int NV, int TEAM, bool GEN>
+__device__ __forceinline__ void stream_adv_pass(const StreamArgs& a, int32_t t, int is_item, const RowV<NV>& own,
                                                 const RowV<NV>& ownp, const RecV& r0, const RecV& r1, bool a0,
                                                 bool a1, RowV<NV> ra0, RowV<NV> rb0, RowV<NV> ra1,
                                                 RowV<NV> rb1, uint32_t tag, int l, RowV<NV>& GA,
                                                 int k = 0,  // k: diagnostic stamps only
-                                                const float* g0 = nullptr, const float* g1 = nullptr) {
+                                                const float* g0 = nullptr, const float* g1 = nullptr,
+                                                // a user occurrence's clipped argument, its loss left to the caller
+                                                float* x0 = nullptr, float* x1 = nullptr) {
   RowV<NV> da0 = zero_row<NV>(), db0 = da0, da1 = da0, db1 = da0;
   const bool sa0 = a0 && r0.pa_solo(), sb0 = a0 && r0.pb_solo();
   const bool sa1 = a1 && r1.pa_solo(), sb1 = a1 && r1.pb_solo();
-  const VSrc ta0 = a0 && !sa0 ? ver_at(vrow(a.ver_d, a, a.t, r0.pa_slot())) : 0;
-  const VSrc tb0 = a0 && !sb0 ? ver_at(vrow(a.ver_d, a, a.t, r0.pb_slot())) : 0;
-  const VSrc ta1 = a1 && !sa1 ? ver_at(vrow(a.ver_d, a, a.t, r1.pa_slot())) : 0;
-  const VSrc tb1 = a1 && !sb1 ? ver_at(vrow(a.ver_d, a, a.t, r1.pb_slot())) : 0;
+  const VSrc ta0 = a0 && !sa0 ? ver_at(vrow(a.ver_d, a, t, r0.pa_slot())) : 0;
+  const VSrc tb0 = a0 && !sb0 ? ver_at(vrow(a.ver_d, a, t, r0.pb_slot())) : 0;
+  const VSrc ta1 = a1 && !sa1 ? ver_at(vrow(a.ver_d, a, t, r1.pa_slot())) : 0;
+  const VSrc tb1 = a1 && !sb1 ? ver_at(vrow(a.ver_d, a, t, r1.pb_slot())) : 0;
   bool pa0 = !ta0, pb0 = !tb0, pa1 = !ta1, pb1 = !tb1;
   if (__any(sa0)) {
-    const RowV<NV> x = solo_delta<LPR, NV, TEAM>(a, is_item, own, r0, ra0, rb0, 0, l, g0);
+    const RowV<NV> x = solo_delta<LPR, NV, TEAM, GEN>(a, t, is_item, own, r0, ra0, rb0, 0, l, g0);
     if (sa0) da0 = x;
   }
   if (__any(sb0)) {
-    const RowV<NV> x = solo_delta<LPR, NV, TEAM>(a, is_item, own, r0, ra0, rb0, 1, l, g0);
+    const RowV<NV> x = solo_delta<LPR, NV, TEAM, GEN>(a, t, is_item, own, r0, ra0, rb0, 1, l, g0);
     if (sb0) db0 = x;
   }
   if (__any(sa1)) {
-    const RowV<NV> x = solo_delta<LPR, NV, TEAM>(a, is_item, own, r1, ra1, rb1, 0, l, g1);
+    const RowV<NV> x = solo_delta<LPR, NV, TEAM, GEN>(a, t, is_item, own, r1, ra1, rb1, 0, l, g1);
     if (sa1) da1 = x;
   }
   if (__any(sb1)) {
-    const RowV<NV> x = solo_delta<LPR, NV, TEAM>(a, is_item, own, r1, ra1, rb1, 1, l, g1);
+    const RowV<NV> x = solo_delta<LPR, NV, TEAM, GEN>(a, t, is_item, own, r1, ra1, rb1, 1, l, g1);
     if (sb1) db1 = x;
   }
-  STAMP(a.t, k, 6);
+  STAMP(t, k, 6);
   {
     const VSrc src[4] = {ta0, tb0, ta1, tb1};
     RowV<NV>* const dst[4] = {&da0, &db0, &da1, &db1};
     bool ok[4] = {pa0, pb0, pa1, pb1};
-    poll_rows<LPR, NV, 4>(a, src, dst, ok, tag, l);
+    poll_rows<LPR, NV, 4, GEN>(a, src, dst, ok, tag, l);
   }
-  STAMP(a.t, k, 7);
+  STAMP(t, k, 7);
   ra0 = add_row(ra0, da0);
   rb0 = add_row(rb0, db0);
   ra1 = add_row(ra1, da1);
   rb1 = add_row(rb1, db1);
-  occ_term<LPR, NV>(a, is_item, ownp, r0, ra0, rb0, a0, l, a.loss_adv, GA);
-  if (__any(a1)) occ_term<LPR, NV>(a, is_item, ownp, r1, ra1, rb1, a1, l, a.loss_adv, GA);
+  occ_term<LPR, NV>(a, is_item, ownp, r0, ra0, rb0, a0, l, a.loss_adv, GA, nullptr, nullptr, x0);
+  if (__any(a1)) occ_term<LPR, NV>(a, is_item, ownp, r1, ra1, rb1, a1, l, a.loss_adv, GA, nullptr, nullptr, x1);
 }
 
 // One unique row of batch a.t: clean half (utils.py:117, APR.py:180-191), its
@@ -1056,136 +1146,178 @@ __device__ __forceinline__ void stream_adv_pass(const StepArgs& a, int is_item, 
 // adv_slot's, so the bits equal the two-kernel step's.  A slot of at most
 // 2 TEAM occurrences (one pass) keeps its partner rows for the adversarial half;
 // the Adagrad slot is fetched with the first gathers.
-template <int LPR, int NV, int TEAM>
-__device__ __forceinline__ void stream_slot(const StepArgs& a, int k, int m, int l, int leader, uint32_t tag) {
-  STAMP(a.t, k, 0);
-  const SlotRec sr = slot_header<LPR, TEAM>(a, k, m, leader);
+// the clean half's end: batch-summed gradient, delta, delta published; returns own + delta
+template <int LPR, int NV, int TEAM, bool GEN>
+__device__ __forceinline__ RowV<NV> stream_finish_clean(const StreamArgs& a, int32_t t, const SlotHdr& h, int k,
+                                                        int m, int l, uint32_t tag, const RowV<NV>& own,
+                                                        RowV<NV>& Gc) {
+  team_allreduce_wave<LPR, TEAM, NV>(Gc);
+  const RowV<NV> dl = stream_delta<LPR, NV, GEN>(a, t, Gc, h.is_item, h.own_row, l);
+  // a one-occurrence row's delta is never read: its readers form it (solo_delta)
+  if (m == 0 && h.count > 1) store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_d, a, t, k)), a.d, l, dl, tag);
+  STAMP(t, k, 3);
+  return add_row(own, dl);
+}
+
+template <int NV>
+struct HotSums {
+  RowV<NV> G, GA;  // clean and adversarial gradient sums of the member (before the last team reduction of GA)
+};
+
+// A hot row (more than 2 TEAM occurrences; about one batch in forty at the
+// headline shape): its later clean passes, the clean half's end and every
+// adversarial pass, partner rows re-read (versions never change).  G comes in
+// with the first pass's terms.  In line, in a block of its own: as a called
+// function it made the kernel keep what lives across the call in the callee-saved
+// registers, and the one-pass body spilled vector registers to scratch (256 VGPRs,
+// 64 B of scratch, against none in line).
+template <int LPR, int NV, int TEAM, bool GEN>
+__device__ __forceinline__ HotSums<NV> stream_slot_hot(const StreamArgs& a, int32_t t, const SlotHdr& h, int k,
+                                                       int m, int l, uint32_t tag, const RowV<NV>& own,
+                                                       RowV<NV> G) {
+  HotSums<NV> o;
+  o.GA = zero_row<NV>();
+  for (int base = 2 * TEAM; base < h.count; base += 2 * TEAM) {
+    const int i0 = base + m, i1 = base + TEAM + m;
+    const bool b0 = i0 < h.count, b1 = i1 < h.count;
+    RecV q0, q1;
+    if (b0) q0 = occ_rec_mem(a, t, h, k, i0);
+    if (b1) q1 = occ_rec_mem(a, t, h, k, i1);
+    RowV<NV> xa0 = zero_row<NV>(), xb0 = xa0, xa1 = xa0, xb1 = xa0;
+    stream_partners<LPR, NV, GEN>(a, t, h.is_item, q0, q1, b0, b1, tag, l, xa0, xb0, xa1, xb1);
+    occ_term<LPR, NV>(a, h.is_item, own, q0, xa0, xb0, b0, l, a.loss_clean, G);
+    if (__any(b1)) occ_term<LPR, NV>(a, h.is_item, own, q1, xa1, xb1, b1, l, a.loss_clean, G);
+  }
+  const RowV<NV> ownp = stream_finish_clean<LPR, NV, TEAM, GEN>(a, t, h, k, m, l, tag, own, G);
+  for (int base = 0; base < h.count; base += 2 * TEAM) {
+    const int i0 = base + m, i1 = base + TEAM + m;
+    const bool b0 = i0 < h.count, b1 = i1 < h.count;
+    RecV q0, q1;
+    if (b0) q0 = occ_rec_mem(a, t, h, k, i0);
+    if (b1) q1 = occ_rec_mem(a, t, h, k, i1);
+    RowV<NV> xa0 = zero_row<NV>(), xb0 = xa0, xa1 = xa0, xb1 = xa0;
+    stream_partners<LPR, NV, GEN>(a, t, h.is_item, q0, q1, b0, b1, tag, l, xa0, xb0, xa1, xb1);
+    stream_adv_pass<LPR, NV, TEAM, GEN>(a, t, h.is_item, own, ownp, q0, q1, b0, b1, xa0, xb0, xa1, xb1, tag, l, o.GA);
+  }
+  o.G = G;
+  return o;
+}
+
+template <int LPR, int NV, int TEAM, bool GEN>
+__device__ __forceinline__ void stream_slot(const StreamArgs& a, int32_t t, int k, int m, int l, int leader,
+                                            uint32_t tag) {
+  STAMP(t, k, 0);
+  const SlotRec sr = slot_header_at<LPR, TEAM>(a, t, GEN ? a.use_single : 1, k, m, leader);
   const SlotHdr& h = sr.h;
   if (h.count == 0) return;
-  STAMP(a.t, k, 1);
+  STAMP(t, k, 1);
   const int d = a.d;
-  const VSrc own_s = ver_src(a, h.is_item ? a.Q : a.P, a.ver_w, h.own_row, h.own_src);
-  const VSrc acc_s = m == 0 ? ver_src(a, h.is_item ? a.accQ : a.accP, a.ver_a, h.own_row, h.own_src) : 0;
+  const VSrc own_s = ver_src(a, t, h.is_item ? a.Q : a.P, a.ver_w, h.own_row, h.own_src);
+  const VSrc acc_s = m == 0 ? ver_src(a, t, h.is_item ? a.accQ : a.accP, a.ver_a, h.own_row, h.own_src) : 0;
   RowV<NV> own = zero_row<NV>(), acc = own, G = own;
   RowV<NV> ra0 = own, rb0 = own, ra1 = own, rb1 = own;
   RecV r0, r1;
   bool a0 = false, a1 = false;
-  float lc0 = 0.f, lc1 = 0.f, gc0 = 0.f, gc1 = 0.f;
+  // a user occurrence's clipped arguments (clean, adversarial): its losses are
+  // evaluated behind the task's version stores, which is where the next batch waits
+  float xc0 = 0.f, xc1 = 0.f, xa0 = 0.f, xa1 = 0.f, gc0 = 0.f, gc1 = 0.f;
   {  // first pass: own row, Adagrad slot, partners in one wait
     a0 = m < h.count;
     a1 = TEAM + m < h.count;
     if (a0) r0 = occ_rec<TEAM>(a, sr, m, m);
     if (a1) r1 = occ_rec<TEAM>(a, sr, TEAM + m, m);
     const float* ptab = h.is_item ? a.P : a.Q;
-    const VSrc sa0 = a0 ? ver_src(a, ptab, a.ver_w, r0.pa_row(), r0.pa_src()) : 0;
-    const VSrc sb0 = a0 ? ver_src(a, a.Q, a.ver_w, r0.pb_row(), r0.pb_src()) : 0;
-    const VSrc sa1 = a1 ? ver_src(a, ptab, a.ver_w, r1.pa_row(), r1.pa_src()) : 0;
-    const VSrc sb1 = a1 ? ver_src(a, a.Q, a.ver_w, r1.pb_row(), r1.pb_src()) : 0;
+    const VSrc sa0 = a0 ? ver_src(a, t, ptab, a.ver_w, r0.pa_row(), r0.pa_src()) : 0;
+    const VSrc sb0 = a0 ? ver_src(a, t, a.Q, a.ver_w, r0.pb_row(), r0.pb_src()) : 0;
+    const VSrc sa1 = a1 ? ver_src(a, t, ptab, a.ver_w, r1.pa_row(), r1.pa_src()) : 0;
+    const VSrc sb1 = a1 ? ver_src(a, t, a.Q, a.ver_w, r1.pb_row(), r1.pb_src()) : 0;
     {
       const VSrc src[6] = {own_s, acc_s, sa0, sb0, sa1, sb1};
       RowV<NV>* const dst[6] = {&own, &acc, &ra0, &rb0, &ra1, &rb1};
       bool ok[6] = {false, m != 0, !a0, !a0, !a1, !a1};
-      poll_rows<LPR, NV, 6>(a, src, dst, ok, tag, l);
+      poll_rows<LPR, NV, 6, GEN>(a, src, dst, ok, tag, l);
     }
-    STAMP(a.t, k, 2);
-    // clean losses are stored at the end of the task: on gfx950 vmcnt counts
-    // stores too, so a store here would hold up every later wait on a load
-    occ_term<LPR, NV>(a, h.is_item, own, r0, ra0, rb0, a0, l, a.loss_clean, G, &lc0, &gc0);
-    if (__any(a1)) occ_term<LPR, NV>(a, h.is_item, own, r1, ra1, rb1, a1, l, a.loss_clean, G, &lc1, &gc1);
+    STAMP(t, k, 2);
+    occ_term<LPR, NV>(a, h.is_item, own, r0, ra0, rb0, a0, l, a.loss_clean, G, nullptr, &gc0, &xc0);
+    if (__any(a1)) occ_term<LPR, NV>(a, h.is_item, own, r1, ra1, rb1, a1, l, a.loss_clean, G, nullptr, &gc1, &xc1);
   }
-  // the clean half's end: batch-summed gradient, delta, delta published
-  auto finish_clean = [&](RowV<NV>& Gc) -> RowV<NV> {
-    team_allreduce_wave<LPR, TEAM, NV>(Gc);
-    const RowV<NV> dl = make_delta<LPR, NV>(a, Gc, h.is_item, h.own_row, l);
-    // a one-occurrence row's delta is never read: its readers form it (solo_delta)
-    if (m == 0 && h.count > 1) store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_d, a, a.t, k)), d, l, dl, tag);
-    STAMP(a.t, k, 3);
-    return add_row(own, dl);
-  };
   RowV<NV> GA = zero_row<NV>();
-  if (h.count <= 2 * TEAM) {  // one pass (wave-uniform): partner rows kept for the adversarial half
-    const RowV<NV> ownp = finish_clean(G);
-    stream_adv_pass<LPR, NV, TEAM>(a, h.is_item, own, ownp, r0, r1, a0, a1, ra0, rb0, ra1, rb1, tag, l, GA, k, &gc0,
-                                   &gc1);
-  } else {  // hot rows: more passes, partner rows re-read (versions never change)
-    for (int base = 2 * TEAM; base < h.count; base += 2 * TEAM) {
-      const int i0 = base + m, i1 = base + TEAM + m;
-      const bool b0 = i0 < h.count, b1 = i1 < h.count;
-      RecV q0, q1;
-      if (b0) q0 = occ_rec_mem(a, h, k, i0);
-      if (b1) q1 = occ_rec_mem(a, h, k, i1);
-      RowV<NV> xa0 = zero_row<NV>(), xb0 = xa0, xa1 = xa0, xb1 = xa0;
-      stream_partners<LPR, NV>(a, h.is_item, q0, q1, b0, b1, tag, l, xa0, xb0, xa1, xb1);
-      occ_term<LPR, NV>(a, h.is_item, own, q0, xa0, xb0, b0, l, a.loss_clean, G);
-      if (__any(b1)) occ_term<LPR, NV>(a, h.is_item, own, q1, xa1, xb1, b1, l, a.loss_clean, G);
-    }
-    const RowV<NV> ownp = finish_clean(G);
-    for (int base = 0; base < h.count; base += 2 * TEAM) {
-      const int i0 = base + m, i1 = base + TEAM + m;
-      const bool b0 = i0 < h.count, b1 = i1 < h.count;
-      RecV q0, q1;
-      if (b0) q0 = occ_rec_mem(a, h, k, i0);
-      if (b1) q1 = occ_rec_mem(a, h, k, i1);
-      RowV<NV> xa0 = zero_row<NV>(), xb0 = xa0, xa1 = xa0, xb1 = xa0;
-      stream_partners<LPR, NV>(a, h.is_item, q0, q1, b0, b1, tag, l, xa0, xb0, xa1, xb1);
-      stream_adv_pass<LPR, NV, TEAM>(a, h.is_item, own, ownp, q0, q1, b0, b1, xa0, xb0, xa1, xb1, tag, l, GA);
-    }
+  const bool one_pass = h.count <= 2 * TEAM;  // wave-uniform
+  if (one_pass) {  // partner rows kept for the adversarial half
+    const RowV<NV> ownp = stream_finish_clean<LPR, NV, TEAM, GEN>(a, t, h, k, m, l, tag, own, G);
+    stream_adv_pass<LPR, NV, TEAM, GEN>(a, t, h.is_item, own, ownp, r0, r1, a0, a1, ra0, rb0, ra1, rb1, tag, l, GA, k,
+                                        &gc0, &gc1, &xa0, &xa1);
+  } else {  // a hot row: its adversarial losses are stored in there, pass by pass
+    const HotSums<NV> o = stream_slot_hot<LPR, NV, TEAM, GEN>(a, t, h, k, m, l, tag, own, G);
+    G = o.G;
+    GA = o.GA;
   }
-  STAMP(a.t, k, 4);
+  STAMP(t, k, 4);
   team_allreduce_wave<LPR, TEAM, NV>(GA);
   if (m == 0) {
     axpy_row(G, a.reg_adv, GA);
     RowV<NV> wout;
     adagrad_row(a, G, own, acc, h.count, wout);
-    store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_w, a, a.t, k)), d, l, wout, tag);
-    store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_a, a, a.t, k)), d, l, acc, tag);
+    store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_w, a, t, k)), d, l, wout, tag);
+    store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_a, a, t, k)), d, l, acc, tag);
   }
+  // the link to the next batch ends above; the softplus chains (exp, log) of the
+  // user occurrences' losses must not be scheduled back in front of the stores
+  __builtin_amdgcn_sched_barrier(0);
   if (!h.is_item && l == 0) {
-    if (a0) a.loss_clean[r0.e_role()] = lc0;
-    if (a1) a.loss_clean[r1.e_role()] = lc1;
+    if (a0) a.loss_clean[r0.e_role()] = bpr_loss(xc0);
+    if (a1) a.loss_clean[r1.e_role()] = bpr_loss(xc1);
+    if (one_pass) {
+      if (a0) a.loss_adv[r0.e_role()] = bpr_loss(xa0);
+      if (a1) a.loss_adv[r1.e_role()] = bpr_loss(xa1);
+    }
   }
-  STAMP(a.t, k, 5);
+  STAMP(t, k, 5);
 }
 
 // A fused triplet of batch a.t (k_single's APR sequence): rows and Adagrad
 // slots from their versions or the tables, results as versions of its 3 slots.
-template <int LPR, int NV>
-__device__ __forceinline__ void stream_single(const StepArgs& a, int b, int l, uint32_t tag) {
-  const int64_t e = (int64_t)a.t * a.B + b;
+template <int LPR, int NV, bool GEN>
+__device__ __forceinline__ void stream_single(const StreamArgs& a, int32_t t, int b, int l, uint32_t tag) {
+  const int64_t e = (int64_t)t * a.B + b;
   RecV r;
   r.a = r.b = r.c = make_int4(0, 0, 0, -1);
   if (b < a.B) r = load_rec(a.trec + e);
   const bool act = r.c.w == *a.gen_ptr && (r.c.y & 1);
   const int d = a.d;
   const int32_t u = r.a.x, i = r.a.y, j = r.a.z;
-  const VSrc su = act ? ver_src(a, a.P, a.ver_w, u, r.b.z) : 0;
-  const VSrc si = act ? ver_src(a, a.Q, a.ver_w, i, r.b.w) : 0;
-  const VSrc sj = act ? ver_src(a, a.Q, a.ver_w, j, r.c.x) : 0;
-  const VSrc cu_s = act ? ver_src(a, a.accP, a.ver_a, u, r.b.z) : 0;
-  const VSrc ci_s = act ? ver_src(a, a.accQ, a.ver_a, i, r.b.w) : 0;
-  const VSrc cj_s = act ? ver_src(a, a.accQ, a.ver_a, j, r.c.x) : 0;
+  const VSrc su = act ? ver_src(a, t, a.P, a.ver_w, u, r.b.z) : 0;
+  const VSrc si = act ? ver_src(a, t, a.Q, a.ver_w, i, r.b.w) : 0;
+  const VSrc sj = act ? ver_src(a, t, a.Q, a.ver_w, j, r.c.x) : 0;
+  const VSrc cu_s = act ? ver_src(a, t, a.accP, a.ver_a, u, r.b.z) : 0;
+  const VSrc ci_s = act ? ver_src(a, t, a.accQ, a.ver_a, i, r.b.w) : 0;
+  const VSrc cj_s = act ? ver_src(a, t, a.accQ, a.ver_a, j, r.c.x) : 0;
   RowV<NV> p = zero_row<NV>(), qi = p, qj = p, cu = p, ci = p, cj = p;
   {
     const VSrc src[6] = {su, si, sj, cu_s, ci_s, cj_s};
     RowV<NV>* const dst[6] = {&p, &qi, &qj, &cu, &ci, &cj};
     bool ok[6] = {!act, !act, !act, !act, !act, !act};
-    poll_rows<LPR, NV, 6>(a, src, dst, ok, tag, l);
+    poll_rows<LPR, NV, 6, GEN>(a, src, dst, ok, tag, l);
   }
   if (!act) return;
-  float g, loss;
-  bpr_term(dot_row<LPR, NV>(p, qi) - dot_row<LPR, NV>(p, qj), a.clip_lo, a.clip_hi, g, loss);
-  if (l == 0) a.loss_clean[e] = loss;
+  // the two losses are functions of the clipped arguments alone (bpr_term =
+  // bpr_clip, the gradient, bpr_loss): they are evaluated and stored behind the
+  // version stores, where no later batch waits for them
+  float g, loss, ga, la;
+  const float x = dot_row<LPR, NV>(p, qi) - dot_row<LPR, NV>(p, qj);
+  bpr_term(x, a.clip_lo, a.clip_hi, g, loss);
+  const float xc = bpr_clip(x, a.clip_lo, a.clip_hi);
   RowV<NV> Gu = zero_row<NV>(), Gi = zero_row<NV>(), Gj = zero_row<NV>();
   axpy_row(Gu, g, qi);
   axpy_row(Gu, -g, qj);
   axpy_row(Gi, g, p);
   axpy_row(Gj, -g, p);
-  const RowV<NV> pp = add_row(p, make_delta<LPR, NV>(a, Gu, 0, u, l));
-  const RowV<NV> qip = add_row(qi, make_delta<LPR, NV>(a, Gi, 1, i, l));
-  const RowV<NV> qjp = add_row(qj, make_delta<LPR, NV>(a, Gj, 1, j, l));
-  float ga, la;
-  bpr_term(dot_row<LPR, NV>(pp, qip) - dot_row<LPR, NV>(pp, qjp), a.clip_lo, a.clip_hi, ga, la);
-  if (l == 0) a.loss_adv[e] = la;
+  const RowV<NV> pp = add_row(p, stream_delta<LPR, NV, GEN>(a, t, Gu, 0, u, l));
+  const RowV<NV> qip = add_row(qi, stream_delta<LPR, NV, GEN>(a, t, Gi, 1, i, l));
+  const RowV<NV> qjp = add_row(qj, stream_delta<LPR, NV, GEN>(a, t, Gj, 1, j, l));
+  const float xp = dot_row<LPR, NV>(pp, qip) - dot_row<LPR, NV>(pp, qjp);
+  bpr_term(xp, a.clip_lo, a.clip_hi, ga, la);
+  const float xpc = bpr_clip(xp, a.clip_lo, a.clip_hi);
   RowV<NV> Au = zero_row<NV>(), Ai = zero_row<NV>(), Aj = zero_row<NV>();
   axpy_row(Au, ga, qip);
   axpy_row(Au, -ga, qjp);
@@ -1198,12 +1330,17 @@ __device__ __forceinline__ void stream_single(const StepArgs& a, int b, int l, u
   adagrad_row(a, Gu, p, cu, 1, wu);
   adagrad_row(a, Gi, qi, ci, 1, wi);
   adagrad_row(a, Gj, qj, cj, 1, wj);
-  store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_w, a, a.t, r.a.w)), d, l, wu, tag);
-  store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_w, a, a.t, r.b.x)), d, l, wi, tag);
-  store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_w, a, a.t, r.b.y)), d, l, wj, tag);
-  store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_a, a, a.t, r.a.w)), d, l, cu, tag);
-  store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_a, a, a.t, r.b.x)), d, l, ci, tag);
-  store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_a, a, a.t, r.b.y)), d, l, cj, tag);
+  store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_w, a, t, r.a.w)), d, l, wu, tag);
+  store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_w, a, t, r.b.x)), d, l, wi, tag);
+  store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_w, a, t, r.b.y)), d, l, wj, tag);
+  store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_a, a, t, r.a.w)), d, l, cu, tag);
+  store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_a, a, t, r.b.x)), d, l, ci, tag);
+  store_ver<LPR, NV>(const_cast<u64*>(vrow(a.ver_a, a, t, r.b.y)), d, l, cj, tag);
+  __builtin_amdgcn_sched_barrier(0);  // the softplus chains stay behind the stores
+  if (l == 0) {
+    a.loss_clean[e] = bpr_loss(xc);
+    a.loss_adv[e] = bpr_loss(xpc);
+  }
 }
 
 // The end of a streamed call, decided once: thread 0 of the deciding workgroup
@@ -1214,7 +1351,8 @@ __device__ __forceinline__ void stream_single(const StepArgs& a, int b, int l, u
 // the epoch alone: the replay reads the same call counter (random delta) and
 // bumps it as this call would have; the failed launch's granules keep their
 // tag, and the next streamed launch of the context has a later one.
-__device__ __forceinline__ void stream_decided(const StepArgs& a, bool failed) {
+template <class A>
+__device__ __forceinline__ void stream_decided(const A& a, bool failed) {
   uint32_t* ep = const_cast<uint32_t*>(a.epoch);
   if (!failed) {
     atomicAdd(ep, 1u);
@@ -1232,7 +1370,7 @@ __device__ __forceinline__ void stream_decided(const StepArgs& a, bool failed) {
 // Record the outcome of launch a.seq in the decide word unless one is recorded
 // already; returns the recorded outcome (bit 0: failed) and, through *me,
 // whether this call recorded it (the decider runs stream_decided).
-__device__ __forceinline__ int stream_decide(const StepArgs& a, bool failed, bool* me) {
+__device__ __forceinline__ int stream_decide(const StreamArgs& a, bool failed, bool* me) {
   const unsigned long long want = ((unsigned long long)a.seq << 1) | (failed ? 1ull : 0ull);
   // first attempt against the host's guess of the current word (one round trip)
   unsigned long long cur = a.decide_prev;
@@ -1264,16 +1402,17 @@ __device__ __forceinline__ int stream_decide(const StepArgs& a, bool failed, boo
 // Every other workgroup leaves after it has arrived.  The counters come in two
 // sets used by alternate tail launches; each launch's block 0 zeroes the set
 // the previous tail launch used (that launch has ended: kernel boundary).
-template <int LPR>
-__device__ __forceinline__ void stream_tail(const StepArgs& a, uint32_t tag, bool gated, int32_t fcnt) {
+template <int LPR, bool GEN>
+__device__ __forceinline__ void stream_tail(const StreamArgs& a, uint32_t tag, bool gated, int32_t fcnt) {
   __shared__ int s_out;
+  unsigned long long* const tail_diag = GEN ? a.tail_diag : nullptr;
   const int flushers = max(1, min((int)gridDim.x, a.flushers));
   const bool flusher = (int)blockIdx.x < flushers;
   unsigned long long* set = a.arrive + a.tail_par * 144;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) {
-    if (a.tail_diag) atomicMax(a.tail_diag + 1, (unsigned long long)__builtin_amdgcn_s_memrealtime());
+    if (tail_diag) atomicMax(tail_diag + 1, (unsigned long long)__builtin_amdgcn_s_memrealtime());
     const int G = (int)gridDim.x, k = (int)(blockIdx.x & 7);
     const unsigned long long nk = (unsigned long long)(G / 8 + (k < G % 8 ? 1 : 0));
     const unsigned long long nsh = (unsigned long long)min(G, 8);
@@ -1283,13 +1422,13 @@ __device__ __forceinline__ void stream_tail(const StepArgs& a, uint32_t tag, boo
     int out = -1;
     bool me = false;
     if (last) {
-      if (a.tail_diag) a.tail_diag[2] = __builtin_amdgcn_s_memrealtime();
+      if (tail_diag) tail_diag[2] = __builtin_amdgcn_s_memrealtime();
       const bool failed =
           gated || __hip_atomic_load(a.fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int32_t)a.seq;
       out = stream_decide(a, failed, &me);
-      if (a.tail_diag) a.tail_diag[3] = __builtin_amdgcn_s_memrealtime();
+      if (tail_diag) tail_diag[3] = __builtin_amdgcn_s_memrealtime();
       if (me) stream_decided(a, out != 0);
-      if (a.tail_diag) a.tail_diag[4] = __builtin_amdgcn_s_memrealtime();
+      if (tail_diag) tail_diag[4] = __builtin_amdgcn_s_memrealtime();
     }
     if (flusher && out < 0) {
       const int64_t lim = (int64_t)a.spin_limit * 8;
@@ -1306,7 +1445,7 @@ __device__ __forceinline__ void stream_tail(const StepArgs& a, uint32_t tag, boo
       }
     }
     s_out = out;
-    if (a.tail_diag && flusher && blockIdx.x == 0) a.tail_diag[5] = __builtin_amdgcn_s_memrealtime();
+    if (tail_diag && flusher && blockIdx.x == 0) tail_diag[5] = __builtin_amdgcn_s_memrealtime();
   }
   __syncthreads();
   if (!flusher || s_out != 0) return;
@@ -1349,9 +1488,9 @@ __device__ __forceinline__ void stream_tail(const StepArgs& a, uint32_t tag, boo
                       __uint_as_float((uint32_t)c[h][2]), __uint_as_float((uint32_t)c[h][3]));
     }
   }
-  if (a.tail_diag && blockIdx.x == 0) {
+  if (tail_diag && blockIdx.x == 0) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (threadIdx.x == 0) a.tail_diag[6] = __builtin_amdgcn_s_memrealtime();
+    if (threadIdx.x == 0) tail_diag[6] = __builtin_amdgcn_s_memrealtime();
   }
 }
 
@@ -1364,13 +1503,22 @@ __device__ __forceinline__ void stream_tail(const StepArgs& a, uint32_t tag, boo
 // share a position, taking every depth-th batch; a wave loads its next task
 // while it runs the current one.  A gated launch (a failed verified call of the
 // group awaits its replay) runs no task.
-template <int LPR, int NV, int TEAM>
-__global__ void __launch_bounds__(256, 2) k_stream(StepArgs a, int32_t positions) {
+//
+// Two instances.  k_stream runs the default mode -- gradient delta, not zeroed,
+// task lists, fusion on, the default poll sleep, no tail diagnostics -- with
+// those switches folded at compile time: they are fixed for a launch, and tested
+// at run time they sat in every link of the chain of recurring rows.
+// k_stream_any (GEN) tests them as before and runs every other mode; the host
+// picks (run_streamed).  Same operations on the same values in both.
+template <int LPR, int NV, int TEAM, bool GEN>
+__device__ __forceinline__ void stream_body(const StreamArgs& a, int32_t positions) {
   static_assert(TEAM * LPR == 64, "k_stream: one wave per slot");
+  const bool lists = GEN ? a.task_list != nullptr : true;
+  unsigned long long* const tail_diag = GEN ? a.tail_diag : nullptr;
   const Geo<LPR, TEAM> q;
   const int lane = (int)(threadIdx.x & 63);
   int P = positions;
-  if (a.task_list) {
+  if (lists) {
     int mx = 1;
     for (int32_t t = a.first + lane; t < a.t_end; t += 64) mx = max(mx, a.task_cnt[t]);
 #pragma unroll
@@ -1391,38 +1539,46 @@ __global__ void __launch_bounds__(256, 2) k_stream(StepArgs a, int32_t positions
       __hip_atomic_store(a.arrive + (a.tail_par ^ 1) * 144 + 16 * threadIdx.x, 0ull, __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_AGENT);
   }
-  if (a.tail_diag && blockIdx.x == 0 && threadIdx.x == 0) a.tail_diag[0] = __builtin_amdgcn_s_memrealtime();
+  if (tail_diag && blockIdx.x == 0 && threadIdx.x == 0) tail_diag[0] = __builtin_amdgcn_s_memrealtime();
   if (phase < depth && !gated) {
     int32_t t = a.first + phase;
     int32_t nxt = pos, ncnt = positions;
-    if (a.task_list && t < a.t_end) {
+    if (lists && t < a.t_end) {
       nxt = a.task_list[(int64_t)t * a.task_stride + pos];
       ncnt = a.task_cnt[t];
     }
     for (; t < a.t_end; t += depth) {
       const int32_t task = nxt, cnt = ncnt;
-      if (a.task_list && t + depth < a.t_end) {
+      if (lists && t + depth < a.t_end) {
         nxt = a.task_list[(int64_t)(t + depth) * a.task_stride + pos];
         ncnt = a.task_cnt[t + depth];
       }
       if (pos >= cnt) continue;
-      StepArgs b = a;
-      b.t = t;
       if (task < a.S) {
-        stream_slot<LPR, NV, TEAM>(b, task, q.m, q.l, q.leader, tag);
+        stream_slot<LPR, NV, TEAM, GEN>(a, t, task, q.m, q.l, q.leader, tag);
       } else {
         STAMP(t, task, 0);
-        stream_single<LPR, NV>(b, (task - a.S) * (64 / LPR) + lane / LPR, q.l, tag);
+        stream_single<LPR, NV, GEN>(a, t, (task - a.S) * (64 / LPR) + lane / LPR, q.l, tag);
         STAMP(t, task, 5);
       }
     }
   }
   if (a.tail) {
-    stream_tail<LPR>(a, tag, gated, fcnt);
-  } else if (a.tail_diag && (threadIdx.x & 63) == 0) {
+    stream_tail<LPR, GEN>(a, tag, gated, fcnt);
+  } else if (tail_diag && (threadIdx.x & 63) == 0) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    atomicMax(a.tail_diag + 1, (unsigned long long)__builtin_amdgcn_s_memrealtime());
+    atomicMax(tail_diag + 1, (unsigned long long)__builtin_amdgcn_s_memrealtime());
   }
+}
+
+template <int LPR, int NV, int TEAM>
+__global__ void __launch_bounds__(256, 2) k_stream(StreamArgs a, int32_t positions) {
+  stream_body<LPR, NV, TEAM, false>(a, positions);
+}
+
+template <int LPR, int NV, int TEAM>
+__global__ void __launch_bounds__(256, 2) k_stream_any(StreamArgs a, int32_t positions) {
+  stream_body<LPR, NV, TEAM, true>(a, positions);
 }
 
 // After a k_stream launch without a tail (a partial range of the plan, a plan
@@ -2820,7 +2976,8 @@ static StepArgs make_args(acf_apr_ctx* c, const acf_apr_tables* tb, const acf_ap
 // the kernels of the context's geometry and mapping (get_kernels)
 struct Kernels {
   void *clean_apr = nullptr, *clean_bpr = nullptr, *adv = nullptr, *flush = nullptr;
-  void* stream = nullptr;  // k_stream (one wave per slot, d <= 256)
+  void* stream = nullptr;  // k_stream (one wave per slot, d <= 256): the default mode's instance
+  void* stream_any = nullptr;  // k_stream_any: every other mode (run_streamed picks)
   void* stream_flush = nullptr;  // its write-back, k_stream_flush<LPR>
   void *hot_clean = nullptr, *hot_bpr = nullptr, *hot_adv = nullptr;  // k_hot_combine (list kernels)
   // triplet-centric list step (tri plans with fusion): clean (APR / BPR), combine (MODE 0/1/2), adversarial
@@ -2900,6 +3057,7 @@ static void kernel_ptrs(Kernels* k, int packed, int fused, int lists, int tri) {
     kernel_ptrs_team<LPR, NV, OPW>(k, fused);
     if constexpr (NV == 1) {
       k->stream = reinterpret_cast<void*>(&k_stream<LPR, NV, OPW>);
+      k->stream_any = reinterpret_cast<void*>(&k_stream_any<LPR, NV, OPW>);
       k->stream_flush = reinterpret_cast<void*>(&k_stream_flush<LPR>);
     }
     k->slots_per_wave = 1;
@@ -2924,21 +3082,23 @@ enum { KIND_CLEAN = 0, KIND_ADV = 1, KIND_FLUSH = 2, KIND_STREAM = 4, KIND_HOT =
 // Every launch of a step goes through one Launcher per call: `waves` waves in
 // 256-thread workgroups on its stream.  Timing mode (events != nullptr: two
 // events per launch, kinds[] per launch) launches via hipExtLaunchKernelGGL.
-// `tail`: what a kernel takes after its StepArgs (k_stream, k_stream_flush).
+// `tail`: what a kernel takes after its argument struct (k_stream, after its StreamArgs; k_stream_flush).
 struct Launcher {
   hipStream_t s;
   hipEvent_t* events = nullptr;
   int* kinds = nullptr;
   int li = 0;  // launches so far: the next one's events, kind and stamp slot (StepArgs.diag_launch)
 
-  template <typename... Tail>
-  int launch(void* fn, StepArgs& a, int64_t waves, int kind, Tail... tail) {
-    // a step kernel's waves past its slot and piece waves run fused triplets: only when fusion is on
-    if (sizeof...(Tail) == 0 && !a.use_single && a.slot_waves + a.hot_waves < waves)
-      return acf_set_error(ACF_E_STATE, "bad step geometry");
-    typedef void (*Fn)(StepArgs, Tail...);
+  template <typename Args, typename... Tail>
+  int launch(void* fn, Args& a, int64_t waves, int kind, Tail... tail) {
+    typedef void (*Fn)(Args, Tail...);
     const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-    a.diag_launch = li;
+    if constexpr (std::is_same<Args, StepArgs>::value) {
+      // a step kernel's waves past its slot and piece waves run fused triplets: only when fusion is on
+      if (sizeof...(Tail) == 0 && !a.use_single && a.slot_waves + a.hot_waves < waves)
+        return acf_set_error(ACF_E_STATE, "bad step geometry");
+      a.diag_launch = li;
+    }
     if (kinds) kinds[li] = kind;
     if (events)
       hipExtLaunchKernelGGL(reinterpret_cast<Fn>(fn), grid, block, 0, s, events[2 * li], events[2 * li + 1], 0, a,
@@ -3008,15 +3168,18 @@ static int stream_ready(acf_apr_ctx* c, const Kernels& K) {
   if (c->stream_ok >= 0) return c->stream_ok;
   if (!K.stream) return 0;
   if (c->stream_max_waves == 0) {
-    int dev = 0, cus = 0, blocks = 0;
+    int dev = 0, cus = 0, blocks = 0, blocks_any = 0;  // one budget for both instances: the smaller
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reinterpret_cast<const void*>(K.stream), 256, 0) !=
-            hipSuccess) {
+            hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_any, reinterpret_cast<const void*>(K.stream_any), 256,
+                                                     0) != hipSuccess) {
       (void)hipGetLastError();
       c->stream_ok = 0;
       return 0;
     }
+    blocks = std::min(blocks, blocks_any);
     // MI355X guide (residency): 256-thread blocks admitted per CU = min(API, 8,
     // 800 / (ceil(sgpr/16)*16 + 16)); k_stream's SGPR count (< 144) caps it at 5
     c->stream_max_waves = (int64_t)std::max(0, std::min(blocks, 5)) * cus * 4;
@@ -3069,12 +3232,39 @@ static int capturing(hipStream_t s) {
 static bool use_stream(acf_apr_ctx* c, const Kernels& K, const acf_apr_hparams* hp) {
   if (!(c->stream && hp->adver && K.stream && !K.lists && K.slots_per_wave == 1 && c->plan_kind2)) return false;
   if (c->stream_ok != 1) return false;
+  if ((int64_t)3 * c->B * c->d > INT32_MAX) return false;  // StreamArgs.Sd
   return stream_positions(c) <= c->stream_max_waves;
 }
 
 static void prepare_stream(acf_apr_ctx* c, const acf_apr_hparams* hp) {
   Kernels K;
   if (c->stream && hp->adver && c->stream_ok < 0 && get_kernels(c, &K, c->fusion) == ACF_OK) (void)stream_ready(c, K);
+}
+
+// k_stream's arguments: the fields of the call's StepArgs that the streamed step reads
+static StreamArgs stream_args(const StepArgs& a) {
+  StreamArgs s;
+  s.P = a.P; s.Q = a.Q; s.accP = a.accP; s.accQ = a.accQ;
+  s.inl = a.inl; s.urec = a.urec; s.irec = a.irec; s.trec = a.trec;
+  s.loss_clean = a.loss_clean; s.loss_adv = a.loss_adv;
+  s.gen_ptr = a.gen_ptr;
+  s.ver_w = a.ver_w; s.ver_a = a.ver_a; s.ver_d = a.ver_d;
+  s.task_list = a.task_list; s.task_cnt = a.task_cnt;
+  s.fail = a.fail;
+  s.d = a.d; s.B = a.B; s.S = a.S; s.R = a.R; s.kb = a.kb;
+  s.Sd = a.S * a.d;  // use_stream: fits
+  s.first = a.first; s.t_end = a.t_end; s.task_stride = a.task_stride; s.max_depth = a.max_depth;
+  s.spin_limit = a.spin_limit; s.reg_B = a.reg_B;
+  s.seq = a.seq;
+  s.lr = a.lr; s.eps = a.eps; s.reg = a.reg; s.reg_adv = a.reg_adv; s.clip_lo = a.clip_lo; s.clip_hi = a.clip_hi;
+  s.gate = a.gate; s.step_err = a.step_err; s.decide = a.decide; s.decide_prev = a.decide_prev;
+  s.arrive = a.arrive; s.final_list = a.final_list; s.final_cnt = a.final_cnt; s.status = a.status;
+  s.epoch = a.epoch;
+  s.verify = a.verify; s.tail = a.tail; s.tail_par = a.tail_par; s.flushers = a.flushers;
+  s.use_single = a.use_single; s.poll_sleep = a.poll_sleep; s.adv_mode = a.adv_mode; s.zero_delta = a.zero_delta;
+  s.seed = a.seed;
+  s.tail_diag = a.tail_diag;
+  return s;
 }
 
 // Schedule 1, the streamed call (d <= 256, one wave per slot, APR): batches
@@ -3104,7 +3294,7 @@ static int run_streamed(acf_apr_ctx* c, const acf_apr_tables* tb, const acf_apr_
     for (const auto& x : c->grp->q) mine += x.c == c;
     if (mine >= 8) ACF_RET(resolve(c, 1));
   }
-  StepArgs a = make_args(c, tb, hp, first, 0);
+  StepArgs a = make_args(c, tb, hp, first, 0);  // k_stream_flush's; k_stream's own are cut from it
   a.use_single = c->fusion;
   a.slot_waves = S;
   a.first = first;
@@ -3123,7 +3313,11 @@ static int run_streamed(acf_apr_ctx* c, const acf_apr_tables* tb, const acf_apr_
     a.decide_prev = (unsigned long long)c->last_tail_seq << 1;
     c->last_tail_seq = a.seq;
   }
-  ACF_RET(L.launch(K.stream, a, waves, KIND_STREAM, (int32_t)P));
+  StreamArgs sa = stream_args(a);
+  // the default mode has an instance with its switches folded; every other mode the general one
+  const bool general = a.adv_mode != 0 || a.zero_delta != 0 || !a.use_single || !a.task_list ||
+                       a.poll_sleep != ACF_POLL_SLEEP || a.tail_diag != nullptr;
+  ACF_RET(L.launch(general ? K.stream_any : K.stream, sa, waves, KIND_STREAM, (int32_t)P));
   if (!tail)  // one lane-group per slot
     ACF_RET(L.launch(K.stream_flush, a, ((int64_t)n * S * c->lpr + 63) / 64, KIND_FLUSH, c->epoch));
   if (verify) {
@@ -3667,6 +3861,14 @@ extern "C" int acf_apr_set_spin_limit(acf_apr_ctx* c, int32_t polls) {
   ACF_RET(resolve(c, 2));  // settle queued streamed calls first (FailGroup)
   ACF_CHECK(polls >= 0, ACF_E_INVALID, "spin limit must be >= 0, got %d", polls);
   c->spin_limit = polls;
+  return ACF_OK;
+}
+
+extern "C" int acf_apr_set_poll_sleep(acf_apr_ctx* c, int32_t code) {
+  ACF_CHECK(c, ACF_E_INVALID, "ctx is NULL");
+  ACF_RET(resolve(c, 2));  // settle queued streamed calls first (FailGroup)
+  ACF_CHECK(code >= 0 && code <= 6, ACF_E_INVALID, "poll sleep code must be in [0, 6], got %d", code);
+  c->poll_sleep = code;
   return ACF_OK;
 }
 

@@ -141,6 +141,7 @@ static __device__ int g_stamp_cap = 0;
 // ---------------------------------------------------------------------------
 #define ACF_PACKED_MIN_BATCH 4096  // auto slot mapping: packed from this batch size
 #define ACF_SPIN_LIMIT (1 << 16)  // default version polls before a k_stream wait gives up
+#define ACF_POLL_SLEEP 2  // default s_sleep between version polls: what the default k_stream instance has folded in
 
 struct GraphKey {
   const void* ptrs[4];
@@ -221,7 +222,7 @@ struct acf_apr_ctx {
   // streamed step (k_stream): row versions of every batch of a launch
   int32_t stream = 1;        // ACF_STREAM=0 disables
   int32_t stream_depth = 2;  // max waves per position (batches in flight); a constant: nothing sets it
-  int32_t poll_sleep = 2;    // s_sleep between version polls (0-3; 4/5/6 = 8/16/32); a constant: nothing sets it
+  int32_t poll_sleep = ACF_POLL_SLEEP;  // s_sleep between version polls (0-3; 4/5/6 = 8/16/32; acf_apr_set_poll_sleep)
   int32_t spin_limit = ACF_SPIN_LIMIT;  // k_stream version polls before a give-up (acf_apr_set_spin_limit)
   // a replay of a call of this context may still be reading the plan's records:
   // replay_ev was recorded behind it on its stream, and the next plan waits on it

@@ -178,13 +178,21 @@ __device__ __forceinline__ void adagrad_apply(RowV<NV>& w, RowV<NV>& a, const Ro
 // d/dx of softplus(-clip(x)) (APR.py:148-150): TF SoftplusGrad gives
 // 1/(exp(r)+1) on features -r, negated by the Neg; clip_by_value passes the
 // gradient only where lo <= x <= hi.  Also returns the loss term.
+// The loss is a function of the clipped argument alone (bpr_clip, bpr_loss), so a
+// caller may keep xc and evaluate the loss later: same input, same bits.
+__device__ __forceinline__ float bpr_clip(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
+
+__device__ __forceinline__ float bpr_loss(float xc) {
+  float f = -xc;
+  return f > ACF_SOFTPLUS_T ? f : (f < -ACF_SOFTPLUS_T ? expf(f) : logf(expf(f) + 1.0f));
+}
+
 __device__ __forceinline__ void bpr_term(float x, float lo, float hi, float& g, float& loss) {
-  float xc = fminf(fmaxf(x, lo), hi);
+  float xc = bpr_clip(x, lo, hi);
   bool pass = (x >= lo) && (x <= hi);
   float ex = expf(xc);
   g = pass ? -__builtin_amdgcn_rcpf(ex + 1.0f) : 0.0f;  // v_rcp_f32 (1 ulp)
-  float f = -xc;
-  loss = f > ACF_SOFTPLUS_T ? f : (f < -ACF_SOFTPLUS_T ? expf(f) : logf(expf(f) + 1.0f));
+  loss = bpr_loss(xc);
 }
 
 // counter-based RNG (splitmix64 finaliser over a mixed counter)

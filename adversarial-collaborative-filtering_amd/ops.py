@@ -306,6 +306,12 @@ class APRContext:
         0 to force the replay)."""
         call("acf_apr_set_spin_limit", self._ptr, int(polls))
 
+    def set_poll_sleep(self, code: int) -> None:
+        """s_sleep between two version polls of k_stream, as a code (0-3: s_sleep 0-3;
+        4 / 5 / 6: s_sleep 8 / 16 / 32; default 2).  Timing only; a non-default code
+        runs the streamed kernel's general instance."""
+        call("acf_apr_set_poll_sleep", self._ptr, int(code))
+
     def stream_recoveries(self) -> int:
         """Streamed calls replayed on the two-kernel schedule so far."""
         out = ctypes.c_int64(0)

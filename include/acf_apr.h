@@ -216,6 +216,11 @@ int acf_apr_set_stream(acf_apr_ctx* ctx, int32_t on);
  * acf_apr_stream_recoveries: streamed calls replayed so far. */
 int acf_apr_set_failsafe(acf_apr_ctx* ctx, int32_t on);
 int acf_apr_set_spin_limit(acf_apr_ctx* ctx, int32_t polls);
+/* s_sleep between two polls of a row version in k_stream, as a code: 0-3 are
+ * s_sleep 0-3, 4 / 5 / 6 are s_sleep 8 / 16 / 32 (default 2).  Timing only: the
+ * results do not depend on it.  A non-default code runs the general instance of
+ * the streamed kernel (k_stream_any). */
+int acf_apr_set_poll_sleep(acf_apr_ctx* ctx, int32_t code);
 int acf_apr_stream_recoveries(acf_apr_ctx* ctx, int64_t* out);
 /* Settle every queued verified streamed call of the context's group (blocks
  * until they have all reported; replays failed ones, see above). */

@@ -5,7 +5,8 @@ built library (no GPU needed).
 Extracts the clang offload bundle from the library's .hip_fatbin section, takes
 the amdgcn code object and prints, for every kernel whose name matches the
 pattern, the AMDGPU metadata fields .vgpr_count, .agpr_count, .sgpr_count,
-.group_segment_fixed_size (LDS), .private_segment_fixed_size (scratch).
+.group_segment_fixed_size (LDS), .private_segment_fixed_size (scratch), the spill
+counts, and the kernel's code bytes (the size of its symbol).
 
   python3 tools/kernel_resources.py adversarial-collaborative-filtering_amd/lib/libacf_apr.so k_stream
 """
@@ -44,7 +45,15 @@ def main():
             f.write(co)
         out = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", f.name], capture_output=True,
                              text=True).stdout
+        syms = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "-s", "-W", f.name], capture_output=True,
+                              text=True).stdout
         os.unlink(f.name)
+        # code bytes: the size of the kernel's FUNC symbol (functions it calls are symbols of their own)
+        code = {}
+        for line in syms.splitlines():
+            p = line.split()
+            if len(p) >= 8 and p[3] == "FUNC":
+                code[p[7]] = int(p[2])
         for block in out.split("  - .agpr_count")[1:]:
             name = re.search(r"\.name:\s+(\S+)", block)
             if not name or not pat.search(name.group(1)):
@@ -55,7 +64,8 @@ def main():
             agpr = block.split("\n", 1)[0].strip(": ")
             dem = subprocess.run(["c++filt"], input=name.group(1), capture_output=True,
                                  text=True).stdout.strip()
-            print(dem[:90], "agpr", agpr, " ".join(f"{k}={v.group(1)}" for k, v in fields.items() if v))
+            print(dem[:90], "agpr", agpr, " ".join(f"{k}={v.group(1)}" for k, v in fields.items() if v),
+                  f"code_bytes={code.get(name.group(1), '?')}")
 
 
 if __name__ == "__main__":
