@@ -98,6 +98,15 @@ SIGNATURES = {
     "acf_adv_direction": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _P, _I64, _F, _F, _I32, _U64,
                                          ctypes.c_uint32, _I32, _P, _P, _P, ctypes.c_size_t, _I32, _P]),
     "acf_adv_apply": (ctypes.c_int, [_P, _P, _I64, _I32, _F, _P, _P, _P]),
+    "acf_adv_plan_workspace": (ctypes.c_int, [_I64, _I64, _I64, ctypes.POINTER(ctypes.c_size_t),
+                                              ctypes.POINTER(ctypes.c_size_t)]),
+    "acf_adv_plan": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _I64, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _I32,
+                                    _P]),
+    "acf_adv_direction_planned": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _P, _I64, _F, _F, _P,
+                                                 ctypes.c_size_t, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "acf_adv_pgd_workspace": (ctypes.c_int, [_I64, _I64, _I64, _I32, ctypes.POINTER(ctypes.c_size_t)]),
+    "acf_adv_pgd": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _P, _I64, _F, _F, _P, ctypes.c_size_t, _F, _F,
+                                   _I32, _I32, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _I32, _P]),
     "acf_fold_in_users": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _P, _I64, _I32, _I32,
                                          ctypes.POINTER(HParams), _P, _P, _P, _P, _P, _I32, _P]),
     "acf_fold_in_items": (ctypes.c_int, [_P, _I64, _P, _I64, _I32, _P, _I64, _P, _P, _I64, _I32, _I32,

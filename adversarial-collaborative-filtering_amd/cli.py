@@ -67,6 +67,11 @@ def parse_args(argv=None, flavor="ori"):
                    help="After training, evaluate under perturbed tables at these eps (comma separated, e.g. "
                         "\"0.5,1,2\"), gradient and random directions over the last epoch's triplets, and write "
                         "<out>/<runName>.robust (empty: off).")
+    p.add_argument("--robust_iters", type=parse_robust_iters, default=0,
+                   help="With --robust_eps: also an iterated gradient attack of this many projected steps per eps "
+                        "(1 to 1024), written as 'pgd' rows after the others (0: off).")
+    p.add_argument("--robust_step", type=parse_robust_step, default=None,
+                   help="Step size of --robust_iters (default: 2.5 * eps / iters).")
     p.add_argument("--certify_eps", type=parse_eps_list, default=[],
                    help="After training, certify the ranking at these eps (comma separated, e.g. \"0.1,0.5,1\"): "
                         "lower bounds of HR@K, NDCG@K and AUC (all-items evaluation) under EVERY perturbation of "
@@ -128,6 +133,28 @@ def parse_eps_list(text):
             raise argparse.ArgumentTypeError(f"eps must be finite and >= 0, got {tok!r}")
         out.append(v)
     return out
+
+
+def parse_robust_iters(text):
+    """--robust_iters: an integer in [0, 1024] (0: off)."""
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not an integer: {text!r}")
+    if not 0 <= v <= 1024:
+        raise argparse.ArgumentTypeError(f"robust_iters must lie in [0, 1024], got {text!r}")
+    return v
+
+
+def parse_robust_step(text):
+    """--robust_step: a finite step size >= 0."""
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+    if not v >= 0 or v == float("inf"):
+        raise argparse.ArgumentTypeError(f"robust_step must be finite and >= 0, got {text!r}")
+    return v
 
 
 def parse_cutoffs(text):
@@ -415,8 +442,9 @@ def main(argv=None, flavor="ori"):
         if trip is None:
             print("--robust_eps: no epoch was trained, nothing to evaluate on", file=sys.stderr)
         else:
-            rows = robustness(final, dataset, init_eval_model(dataset, args), trip, args.robust_eps,
-                              seed=args.seed)
+            modes = ("grad", "random", "pgd") if args.robust_iters > 0 else ("grad", "random")
+            rows = robustness(final, dataset, init_eval_model(dataset, args), trip, args.robust_eps, modes=modes,
+                              seed=args.seed, iters=args.robust_iters or 10, step=args.robust_step)
             write_robust(out, runName + ".robust", rows)
     if args.certify_eps:
         from .evaluate import certified, init_eval_model

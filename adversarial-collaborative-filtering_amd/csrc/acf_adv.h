@@ -11,8 +11,8 @@
 //   e in [2n, 3n)  row ipos[e-2n]    of Q:  +g   * P[user[e-2n]]
 //   e in [3n, 4n)  row ineg[e-3n]    of Q:  -g   * P[user[e-3n]]
 // A row's terms are summed in ascending e: the sum never depends on scheduling.
-//   1. k_adv_stage: g per triplet (seq_dot scores, the step's bpr_term), the
-//      term keys (user row r -> r, item row r -> U1 + r) and values e;
+//   1. k_adv_keys: the term keys (user row r -> r, item row r -> U1 + r) and
+//      values e; k_adv_coef: g per triplet (seq_dot scores, the step's bpr_term);
 //   2. a stable LSD radix sort of (key, e) on 8-bit digits (k_adv_hist, the
 //      three k_adv_scan* passes, k_adv_reorder), so the terms of a row lie
 //      together in ascending e;
@@ -24,6 +24,9 @@
 //   5. k_adv_combine: one lane-group per long row adds its chunk sums in chunk
 //      order, normalises and writes.
 // No float atomics anywhere (the histogram's integer LDS atomics give counts).
+// Stages 1 (keys), 2 and k_adv_offsets read the triplets alone: acf_adv_plan keeps
+// their result (sorted e, offsets, error word), acf_adv_direction_planned runs the
+// rest on it, acf_adv_pgd iterates that with k_adv_pgd_step.  DESIGN.md §4k.
 #pragma once
 
 #include <rocprim/block/block_reduce.hpp>
@@ -37,25 +40,19 @@ constexpr int ADV_SCAN_TILE = 256 * ADV_SCAN_IPT;  // counters per k_adv_scan1/3
 
 __device__ __forceinline__ int32_t adv_clamp(int32_t x, int64_t rows) { return (x < 0 || x >= rows) ? 0 : x; }
 
-// ---- 1. per-triplet coefficient, term keys ---------------------------------
-__global__ void __launch_bounds__(256) k_adv_stage(const float* __restrict__ P, const float* __restrict__ Q, int d,
-                                                   const int32_t* __restrict__ user,
-                                                   const int32_t* __restrict__ ipos,
-                                                   const int32_t* __restrict__ ineg, int64_t n, int64_t U1,
-                                                   int64_t I1, float lo, float hi, float* __restrict__ coef,
-                                                   uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
-                                                   int32_t* __restrict__ err) {
+// ---- 1. term keys (the plan's part), per-triplet coefficient -------------------
+// Reads the triplets only: whatever the tables hold, the keys, the sort and the
+// offsets are the same, so a plan (acf_adv_plan) serves every table pair.
+__global__ void __launch_bounds__(256) k_adv_keys(const int32_t* __restrict__ user, const int32_t* __restrict__ ipos,
+                                                  const int32_t* __restrict__ ineg, int64_t n, int64_t U1, int64_t I1,
+                                                  uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                  int32_t* __restrict__ err) {
   const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (t >= n) return;
   int32_t u = user[t], i = ipos[t], j = ineg[t];
   if (u < 0 || u >= U1) { atomicOr(err, 1); u = 0; }
   if (i < 0 || i >= I1) { atomicOr(err, 2); i = 0; }
   if (j < 0 || j >= I1) { atomicOr(err, 2); j = 0; }
-  const float* p = P + (int64_t)u * d;
-  const float x = seq_dot(p, Q + (int64_t)i * d, d) - seq_dot(p, Q + (int64_t)j * d, d);
-  float g, loss;
-  bpr_term(x, lo, hi, g, loss);
-  coef[t] = g;
   keys[t] = (uint32_t)u;
   keys[n + t] = (uint32_t)u;
   keys[2 * n + t] = (uint32_t)(U1 + i);
@@ -64,6 +61,52 @@ __global__ void __launch_bounds__(256) k_adv_stage(const float* __restrict__ P, 
   vals[n + t] = (uint32_t)(n + t);
   vals[2 * n + t] = (uint32_t)(2 * n + t);
   vals[3 * n + t] = (uint32_t)(3 * n + t);
+}
+
+// g per triplet (seq_dot scores, the step's bpr_term; an index outside its table
+// is read as row 0).  With lpart, also the workgroup's loss: every thread's term as
+// a double (0 past n), added by a fixed tree over the 256 threads, to lpart[block].
+__global__ void __launch_bounds__(256) k_adv_coef(const float* __restrict__ P, const float* __restrict__ Q, int d,
+                                                  const int32_t* __restrict__ user, const int32_t* __restrict__ ipos,
+                                                  const int32_t* __restrict__ ineg, int64_t n, int64_t U1, int64_t I1,
+                                                  float lo, float hi, float* __restrict__ coef,
+                                                  double* __restrict__ lpart) {
+  __shared__ double sm[256];
+  const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  double mine = 0.0;
+  if (t < n) {
+    const int32_t u = adv_clamp(user[t], U1), i = adv_clamp(ipos[t], I1), j = adv_clamp(ineg[t], I1);
+    const float* p = P + (int64_t)u * d;
+    const float x = seq_dot(p, Q + (int64_t)i * d, d) - seq_dot(p, Q + (int64_t)j * d, d);
+    float g, loss;
+    bpr_term(x, lo, hi, g, loss);
+    coef[t] = g;
+    mine = (double)loss;
+  }
+  if (!lpart) return;  // uniform: the whole grid or none of it
+  sm[threadIdx.x] = mine;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sm[threadIdx.x] += sm[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) lpart[blockIdx.x] = sm[0];
+}
+
+// out[0] = the sum of lpart[0, nb): thread x adds lpart[x], lpart[x + 256], ... in
+// that order, then the same tree.  One workgroup: a fixed order whatever the device.
+__global__ void __launch_bounds__(256) k_adv_loss_sum(const double* __restrict__ lpart, int64_t nb,
+                                                      double* __restrict__ out) {
+  __shared__ double sm[256];
+  double s = 0.0;
+  for (int64_t x = threadIdx.x; x < nb; x += 256) s += lpart[x];
+  sm[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sm[threadIdx.x] += sm[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = sm[0];
 }
 
 // ---- 2. stable radix sort pass on bits [shift, shift + 8) -------------------
@@ -309,6 +352,28 @@ __global__ void __launch_bounds__(256) k_adv_apply(const float* __restrict__ W, 
   if (sum) sum[x] = W[x] + dl;
 }
 
+// ---- acf_adv_pgd: one projected step on every row of one table ------------------
+// v = delta + alpha * n (the product rounded, then the sum), s = sqrt(dot_row(v, v))
+// in fp32 (per-lane partial sums of rounded squares, then group_sum's order),
+// delta' = v when s <= eps (s = 0 included: eps >= 0), else v * (eps / s): one
+// division per row, one product per element; sum = W + delta'.  delta NULL: zeros;
+// n NULL: no step, the projection alone.  delta_out may be delta (a lane reads its
+// own elements before it writes them).
+template <int LPR, int NV>
+__global__ void __launch_bounds__(256) k_adv_pgd_step(const float* __restrict__ W, const float* delta, const float* n,
+                                                      int64_t rows, int d, float alpha, float eps, float* delta_out,
+                                                      float* __restrict__ sum_out) {
+  const int64_t r = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / LPR;
+  const int l = threadIdx.x & (LPR - 1);
+  if (r >= rows) return;
+  RowV<NV> v = delta ? load_row<LPR, NV>(delta, r, d, l) : zero_row<NV>();
+  if (n) v = add_row(v, scale_row(load_row<LPR, NV>(n, r, d, l), alpha));
+  const float s = sqrtf(dot_row<LPR, NV>(v, v));
+  if (!(s <= eps)) v = scale_row(v, eps / s);
+  store_row<LPR, NV>(delta_out, r, d, l, v);
+  store_row<LPR, NV>(sum_out, r, d, l, add_row(load_row<LPR, NV>(W, r, d, l), v));
+}
+
 // ---- host: workspace layout --------------------------------------------------
 struct AdvLayout {
   size_t coef, k0, v0, k1, v1, counts, tsum, off, part, err, total;
@@ -346,5 +411,20 @@ static AdvLayout adv_layout(int64_t n, int64_t U1, int64_t I1, int32_t d) {
   L.part = take((size_t)2 * (L.N / ADV_CHUNK + 1) * d * sizeof(float));
   L.err = take(sizeof(int32_t));
   L.total = at;
+  return L;
+}
+
+// A plan (acf_adv_plan): what stages 1 (keys), 2 and k_adv_offsets leave, in one
+// caller-owned buffer: the sorted term values, the row offsets, the error word.
+struct AdvPlanLayout {
+  size_t vals, off, err, total;
+};
+
+static AdvPlanLayout adv_plan_layout(int64_t n, int64_t U1, int64_t I1) {
+  AdvPlanLayout L;
+  L.vals = 0;
+  L.off = adv_up((size_t)4 * n * 4);
+  L.err = L.off + adv_up((size_t)(U1 + I1 + 1) * 4);
+  L.total = L.err + adv_up(sizeof(int32_t));
   return L;
 }

@@ -530,6 +530,65 @@ static void launch_adv_sum(const float* P, const float* Q, int d, int64_t U1, in
   k_adv_combine<LPR, NV><<<grid_for(R * LPR), 256, 0, s>>>(d, U1, R, off, part, nP, nQ);
 }
 
+// The plan's part (stages 1 keys, 2, k_adv_offsets) in a workspace laid out by adv_layout:
+// zeroes *err, range-checks when `check` is set, leaves the offsets in `off` and the sorted
+// term values in *sorted: `vals_dst` when given (the last pass writes there), else the
+// workspace's pair *end, whose other pair is then free.  n > 0.
+static int adv_plan_run(const int32_t* user, const int32_t* ipos, const int32_t* ineg, int64_t n, int64_t U1,
+                        int64_t I1, const AdvLayout& L, char* ws, uint32_t* vals_dst, int32_t* off, int32_t* err,
+                        int32_t check, hipStream_t s, const uint32_t** sorted, int* end) {
+  uint32_t* kb[2] = {reinterpret_cast<uint32_t*>(ws + L.k0), reinterpret_cast<uint32_t*>(ws + L.k1)};
+  uint32_t* vb[2] = {reinterpret_cast<uint32_t*>(ws + L.v0), reinterpret_cast<uint32_t*>(ws + L.v1)};
+  uint32_t* counts = reinterpret_cast<uint32_t*>(ws + L.counts);
+  uint32_t* tsum = reinterpret_cast<uint32_t*>(ws + L.tsum);
+  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+  k_adv_keys<<<grid_for(n), 256, 0, s>>>(user, ipos, ineg, n, U1, I1, kb[0], vb[0], err);
+  HIP_TRY(hipGetLastError());
+  if (check) {  // before anything is built on the indices
+    int32_t herr = 0;
+    ACF_RET(read_error_word(err, s, &herr));
+    ACF_CHECK(herr == 0, ACF_E_RANGE, "triplet index out of range (%s%s)",
+              (herr & 1) ? "user >= num_user_rows " : "", (herr & 2) ? "item >= num_item_rows" : "");
+  }
+  int cur = 0;
+  const uint32_t* out = vb[0];
+  for (int p = 0; p < L.passes; ++p, cur ^= 1) {
+    uint32_t* vout = (vals_dst && p == L.passes - 1) ? vals_dst : vb[cur ^ 1];
+    k_adv_hist<<<(unsigned)L.ntiles, ADV_SORT_BS, 0, s>>>(kb[cur], L.N, 8 * p, L.ntiles, counts);
+    k_adv_scan1<<<(unsigned)L.T, 256, 0, s>>>(counts, L.M, tsum);
+    k_adv_scan2<<<1, 1024, 0, s>>>(tsum, L.T);
+    k_adv_scan3<<<(unsigned)L.T, 256, 0, s>>>(counts, L.M, tsum);
+    k_adv_reorder<<<(unsigned)L.ntiles, ADV_SORT_BS, 0, s>>>(kb[cur], vb[cur], kb[cur ^ 1], vout, L.N, 8 * p, L.ntiles,
+                                                            counts);
+    HIP_TRY(hipGetLastError());
+    out = vout;
+  }
+  k_adv_offsets<<<grid_for(U1 + I1 + 1), 256, 0, s>>>(kb[cur], L.N, U1 + I1, off);
+  HIP_TRY(hipGetLastError());
+  *sorted = out;
+  *end = cur;
+  return ACF_OK;
+}
+
+// The tables' part: coefficients at (P, Q) (with lpart: the stream's loss to *loss), the
+// records from the sorted values, chunk sums, combine.  coef [n], rec [4n], part as adv_layout.
+static int adv_planned_run(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d, const int32_t* user,
+                           const int32_t* ipos, const int32_t* ineg, int64_t n, float lo, float hi,
+                           const uint32_t* vals, const int32_t* off, float* coef, int2* rec, float* part,
+                           double* lpart, double* loss, float* nP, float* nQ, hipStream_t s) {
+  const int64_t N = 4 * n, R = U1 + I1;
+  k_adv_coef<<<grid_for(n), 256, 0, s>>>(P, Q, d, user, ipos, ineg, n, U1, I1, lo, hi, coef, lpart);
+  if (lpart) k_adv_loss_sum<<<1, 256, 0, s>>>(lpart, (int64_t)grid_for(n), loss);
+  HIP_TRY(hipGetLastError());
+  if (!nP) return ACF_OK;  // the loss alone
+  k_adv_records<<<grid_for(N), 256, 0, s>>>(vals, N, n, user, ipos, ineg, U1, I1, coef, rec);
+  HIP_TRY(hipGetLastError());
+  const int64_t units = N / ADV_CHUNK + R + 1;
+  ACF_RET(DISPATCH_GEOM(d, launch_adv_sum, P, Q, d, U1, R, off, rec, part, nP, nQ, units, s));
+  HIP_TRY(hipGetLastError());
+  return ACF_OK;
+}
+
 extern "C" int acf_adv_direction(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
                                  const int32_t* user, const int32_t* ipos, const int32_t* ineg, int64_t n,
                                  float clip_lo, float clip_hi, int32_t adv_mode, uint64_t seed, uint32_t call,
@@ -555,41 +614,207 @@ extern "C" int acf_adv_direction(const float* P, const float* Q, int64_t U1, int
   const AdvLayout L = adv_layout(n, U1, I1, d);
   ACF_RET(check_workspace(workspace, workspace_bytes, L.total, 16));
   char* ws = static_cast<char*>(workspace);
-  float* coef = reinterpret_cast<float*>(ws + L.coef);
-  uint32_t* kb[2] = {reinterpret_cast<uint32_t*>(ws + L.k0), reinterpret_cast<uint32_t*>(ws + L.k1)};
-  uint32_t* vb[2] = {reinterpret_cast<uint32_t*>(ws + L.v0), reinterpret_cast<uint32_t*>(ws + L.v1)};
-  uint32_t* counts = reinterpret_cast<uint32_t*>(ws + L.counts);
-  uint32_t* tsum = reinterpret_cast<uint32_t*>(ws + L.tsum);
+  const uint32_t* vals = nullptr;
+  int end = 0;
   int32_t* off = reinterpret_cast<int32_t*>(ws + L.off);
-  float* part = reinterpret_cast<float*>(ws + L.part);
-  int32_t* err = reinterpret_cast<int32_t*>(ws + L.err);
-  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
-  k_adv_stage<<<grid_for(n), 256, 0, s>>>(P, Q, d, user, ipos, ineg, n, U1, I1, clip_lo, clip_hi, coef, kb[0], vb[0],
-                                           err);
-  HIP_TRY(hipGetLastError());
-  if (check) {  // before anything is built on the indices
+  ACF_RET(adv_plan_run(user, ipos, ineg, n, U1, I1, L, ws, nullptr, off, reinterpret_cast<int32_t*>(ws + L.err), check,
+                       s, &vals, &end));
+  int2* rec = reinterpret_cast<int2*>(ws + (end ? L.k0 : L.k1));  // the free (keys, values) pair: N * 8 bytes
+  return adv_planned_run(P, Q, U1, I1, d, user, ipos, ineg, n, clip_lo, clip_hi, vals, off,
+                         reinterpret_cast<float*>(ws + L.coef), rec, reinterpret_cast<float*>(ws + L.part), nullptr,
+                         nullptr, nP, nQ, s);
+}
+
+// ---- a plan that outlives the call, the planned direction, the iterated attack: DESIGN.md §4k ----
+extern "C" int acf_adv_plan_workspace(int64_t n, int64_t U1, int64_t I1, size_t* plan_bytes, size_t* bytes) {
+  ACF_CHECK(plan_bytes && bytes, ACF_E_INVALID, "NULL argument");
+  ACF_RET(adv_check(n, U1, I1, 4));
+  *plan_bytes = adv_plan_layout(n, U1, I1).total;
+  *bytes = n ? adv_layout(n, U1, I1, 4).part : 0;  // the sort's buffers: everything below the chunk sums
+  return ACF_OK;
+}
+
+static int adv_plan_pointers(void* plan, size_t plan_bytes, int64_t n, int64_t U1, int64_t I1, uint32_t** vals,
+                             int32_t** off, int32_t** err) {
+  const AdvPlanLayout PL = adv_plan_layout(n, U1, I1);
+  ACF_CHECK(plan, ACF_E_INVALID, "NULL argument");
+  ACF_CHECK(reinterpret_cast<uintptr_t>(plan) % 16 == 0, ACF_E_INVALID, "plan must be 16-byte aligned");
+  ACF_CHECK(plan_bytes >= PL.total, ACF_E_INVALID, "plan too small: %zu < %zu bytes", plan_bytes, PL.total);
+  char* pb = static_cast<char*>(plan);
+  *vals = reinterpret_cast<uint32_t*>(pb + PL.vals);
+  *off = reinterpret_cast<int32_t*>(pb + PL.off);
+  *err = reinterpret_cast<int32_t*>(pb + PL.err);
+  return ACF_OK;
+}
+
+extern "C" int acf_adv_plan(const int32_t* user, const int32_t* ipos, const int32_t* ineg, int64_t n, int64_t U1,
+                            int64_t I1, void* plan, size_t plan_bytes, void* workspace, size_t workspace_bytes,
+                            int32_t check, void* stream_) {
+  ACF_RET(adv_check(n, U1, I1, 4));
+  uint32_t* vals;
+  int32_t *off, *err;
+  ACF_RET(adv_plan_pointers(plan, plan_bytes, n, U1, I1, &vals, &off, &err));
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  if (n == 0) {  // no terms: every row starts and ends at 0
+    HIP_TRY(hipMemsetAsync(off, 0, (size_t)(U1 + I1 + 1) * sizeof(int32_t), s));
+    HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+    return ACF_OK;
+  }
+  ACF_CHECK(user && ipos && ineg && workspace, ACF_E_INVALID, "NULL argument");
+  const AdvLayout L = adv_layout(n, U1, I1, 4);
+  ACF_RET(check_workspace(workspace, workspace_bytes, L.part, 16));
+  const uint32_t* sorted = nullptr;
+  int end = 0;
+  return adv_plan_run(user, ipos, ineg, n, U1, I1, L, static_cast<char*>(workspace), vals, off, err, check, s, &sorted,
+                      &end);
+}
+
+// The planned direction in a workspace of acf_adv_direction_workspace(n, ...) bytes: the
+// coefficients, the records where the sort's first pair lay, the loss partials in its second.
+static int adv_planned_in(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d, const int32_t* user,
+                          const int32_t* ipos, const int32_t* ineg, int64_t n, float lo, float hi, const uint32_t* vals,
+                          const int32_t* off, char* ws, double* loss, float* nP, float* nQ, hipStream_t s) {
+  const AdvLayout L = adv_layout(n, U1, I1, d);
+  return adv_planned_run(P, Q, U1, I1, d, user, ipos, ineg, n, lo, hi, vals, off,
+                         reinterpret_cast<float*>(ws + L.coef), reinterpret_cast<int2*>(ws + L.k0),
+                         reinterpret_cast<float*>(ws + L.part), loss ? reinterpret_cast<double*>(ws + L.k1) : nullptr,
+                         loss, nP, nQ, s);
+}
+
+extern "C" int acf_adv_direction_planned(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d,
+                                         const int32_t* user, const int32_t* ipos, const int32_t* ineg, int64_t n,
+                                         float clip_lo, float clip_hi, const void* plan, size_t plan_bytes, float* nP,
+                                         float* nQ, double* loss_out, void* workspace, size_t workspace_bytes,
+                                         void* stream_) {
+  ACF_RET(adv_check(n, U1, I1, d));
+  ACF_CHECK(P && Q && nP && nQ, ACF_E_INVALID, "NULL argument");
+  uint32_t* vals;
+  int32_t *off, *err;
+  ACF_RET(adv_plan_pointers(const_cast<void*>(plan), plan_bytes, n, U1, I1, &vals, &off, &err));
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  if (n == 0) {
+    HIP_TRY(hipMemsetAsync(nP, 0, (size_t)U1 * d * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(nQ, 0, (size_t)I1 * d * sizeof(float), s));
+    if (loss_out) HIP_TRY(hipMemsetAsync(loss_out, 0, sizeof(double), s));
+    return ACF_OK;
+  }
+  ACF_CHECK(user && ipos && ineg && workspace, ACF_E_INVALID, "NULL argument");
+  ACF_RET(check_workspace(workspace, workspace_bytes, adv_layout(n, U1, I1, d).total, 16));
+  return adv_planned_in(P, Q, U1, I1, d, user, ipos, ineg, n, clip_lo, clip_hi, vals, off,
+                        static_cast<char*>(workspace), loss_out, nP, nQ, s);
+}
+
+template <int LPR, int NV>
+static void launch_adv_pgd_step(const float* W, const float* delta, const float* n, int64_t rows, int d, float alpha,
+                                float eps, float* delta_out, float* sum_out, hipStream_t s) {
+  k_adv_pgd_step<LPR, NV><<<grid_for(rows * LPR), 256, 0, s>>>(W, delta, n, rows, d, alpha, eps, delta_out, sum_out);
+}
+
+// acf_adv_pgd's workspace: the perturbed tables, the direction tables, a plan of its own, the
+// planned direction's workspace.
+struct PgdLayout {
+  size_t sumP, sumQ, nP, nQ, plan, dir, total;
+};
+
+static PgdLayout pgd_layout(int64_t n, int64_t U1, int64_t I1, int32_t d) {
+  PgdLayout L;
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    const size_t a = at;
+    at += adv_up(bytes);
+    return a;
+  };
+  const size_t tp = (size_t)U1 * d * sizeof(float), tq = (size_t)I1 * d * sizeof(float);
+  L.sumP = take(tp);
+  L.sumQ = take(tq);
+  L.nP = take(tp);
+  L.nQ = take(tq);
+  L.plan = take(adv_plan_layout(n, U1, I1).total);
+  L.dir = take(n ? adv_layout(n, U1, I1, d).total : 0);
+  L.total = at;
+  return L;
+}
+
+extern "C" int acf_adv_pgd_workspace(int64_t n, int64_t U1, int64_t I1, int32_t d, size_t* bytes) {
+  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
+  ACF_RET(adv_check(n, U1, I1, d));
+  *bytes = pgd_layout(n, U1, I1, d).total;
+  return ACF_OK;
+}
+
+extern "C" int acf_adv_pgd(const float* P, const float* Q, int64_t U1, int64_t I1, int32_t d, const int32_t* user,
+                           const int32_t* ipos, const int32_t* ineg, int64_t n, float clip_lo, float clip_hi,
+                           const void* plan, size_t plan_bytes, float eps, float alpha, int32_t iters, int32_t side,
+                           const float* dP0, const float* dQ0, float* dP, float* dQ, double* loss, void* workspace,
+                           size_t workspace_bytes, int32_t check, void* stream_) {
+  ACF_RET(adv_check(n, U1, I1, d));
+  ACF_CHECK(iters >= 1 && iters <= ACF_ADV_PGD_MAX_ITERS, ACF_E_INVALID, "iters must lie in [1, %d], got %d",
+            ACF_ADV_PGD_MAX_ITERS, iters);
+  ACF_CHECK(std::isfinite(eps) && eps >= 0.f, ACF_E_INVALID, "eps must be finite and >= 0");
+  ACF_CHECK(std::isfinite(alpha) && alpha >= 0.f, ACF_E_INVALID, "alpha must be finite and >= 0");
+  ACF_CHECK(side >= ACF_ADV_SIDE_BOTH && side <= ACF_ADV_SIDE_ITEM, ACF_E_INVALID,
+            "side must be 0 (both), 1 (user) or 2 (item), got %d", side);
+  ACF_CHECK(P && Q && dP && dQ && loss && workspace, ACF_E_INVALID, "NULL argument");
+  ACF_CHECK(n == 0 || (user && ipos && ineg), ACF_E_INVALID, "NULL argument");
+  const PgdLayout L = pgd_layout(n, U1, I1, d);
+  ACF_RET(check_workspace(workspace, workspace_bytes, L.total, 16));
+  char* ws = static_cast<char*>(workspace);
+  uint32_t* vals;
+  int32_t *off, *err;
+  if (plan) ACF_RET(adv_plan_pointers(const_cast<void*>(plan), plan_bytes, n, U1, I1, &vals, &off, &err));
+  else ACF_RET(adv_plan_pointers(ws + L.plan, adv_plan_layout(n, U1, I1).total, n, U1, I1, &vals, &off, &err));
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  float* sumP = reinterpret_cast<float*>(ws + L.sumP);
+  float* sumQ = reinterpret_cast<float*>(ws + L.sumQ);
+  float* nP = reinterpret_cast<float*>(ws + L.nP);
+  float* nQ = reinterpret_cast<float*>(ws + L.nQ);
+  char* dir = ws + L.dir;
+  if (n > 0 && !plan) {  // plan once; the direction's workspace is free until the first iteration
+    const uint32_t* sorted = nullptr;
+    int end = 0;
+    ACF_RET(adv_plan_run(user, ipos, ineg, n, U1, I1, adv_layout(n, U1, I1, d), dir, vals, off, err, check, s, &sorted,
+                         &end));
+  } else if (n > 0 && check) {  // the word the plan's own call left
     int32_t herr = 0;
     ACF_RET(read_error_word(err, s, &herr));
     ACF_CHECK(herr == 0, ACF_E_RANGE, "triplet index out of range (%s%s)",
               (herr & 1) ? "user >= num_user_rows " : "", (herr & 2) ? "item >= num_item_rows" : "");
   }
-  int cur = 0;
-  for (int p = 0; p < L.passes; ++p, cur ^= 1) {
-    k_adv_hist<<<(unsigned)L.ntiles, ADV_SORT_BS, 0, s>>>(kb[cur], L.N, 8 * p, L.ntiles, counts);
-    k_adv_scan1<<<(unsigned)L.T, 256, 0, s>>>(counts, L.M, tsum);
-    k_adv_scan2<<<1, 1024, 0, s>>>(tsum, L.T);
-    k_adv_scan3<<<(unsigned)L.T, 256, 0, s>>>(counts, L.M, tsum);
-    k_adv_reorder<<<(unsigned)L.ntiles, ADV_SORT_BS, 0, s>>>(kb[cur], vb[cur], kb[cur ^ 1], vb[cur ^ 1], L.N, 8 * p,
-                                                            L.ntiles, counts);
+  // iterate 0: the start as given (not projected: a chained call continues bit for bit), W + start
+  struct Side {
+    const float* W;
+    const float* d0;
+    float *dl, *sum, *dirn;
+    int64_t rows;
+    bool moves;
+  } sides[2] = {{P, dP0, dP, sumP, nP, U1, side != ACF_ADV_SIDE_ITEM}, {Q, dQ0, dQ, sumQ, nQ, I1, side != ACF_ADV_SIDE_USER}};
+  for (const Side& t : sides) {
+    const size_t bytes = (size_t)t.rows * d * sizeof(float);
+    if (!t.d0) {
+      HIP_TRY(hipMemsetAsync(t.dl, 0, bytes, s));
+      HIP_TRY(hipMemcpyAsync(t.sum, t.W, bytes, hipMemcpyDeviceToDevice, s));
+    } else {
+      if (t.d0 != t.dl) HIP_TRY(hipMemcpyAsync(t.dl, t.d0, bytes, hipMemcpyDeviceToDevice, s));
+      k_adv_apply<<<grid_for(t.rows * (int64_t)d), 256, 0, s>>>(t.W, t.d0, t.rows * (int64_t)d, 1.0f, nullptr, t.sum);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  if (n == 0) {  // no gradient: the projection of the start, once; no loss
+    for (const Side& t : sides)
+      if (t.moves) ACF_RET(DISPATCH_GEOM(d, launch_adv_pgd_step, t.W, t.dl, nullptr, t.rows, d, 0.f, eps, t.dl, t.sum, s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(loss, 0, (size_t)(iters + 1) * sizeof(double), s));
+    return ACF_OK;
+  }
+  for (int k = 0; k <= iters; ++k) {
+    const bool last = k == iters;  // one more coefficient pass: the loss at the final iterate
+    ACF_RET(adv_planned_in(sumP, sumQ, U1, I1, d, user, ipos, ineg, n, clip_lo, clip_hi, vals, off, dir, loss + k,
+                           last ? nullptr : nP, last ? nullptr : nQ, s));
+    if (last) break;
+    for (const Side& t : sides)
+      if (t.moves) ACF_RET(DISPATCH_GEOM(d, launch_adv_pgd_step, t.W, t.dl, t.dirn, t.rows, d, alpha, eps, t.dl, t.sum, s));
     HIP_TRY(hipGetLastError());
   }
-  int2* rec = reinterpret_cast<int2*>(kb[cur ^ 1]);  // the free (keys, values) pair: N * 8 bytes
-  k_adv_offsets<<<grid_for(R + 1), 256, 0, s>>>(kb[cur], L.N, R, off);
-  k_adv_records<<<grid_for(L.N), 256, 0, s>>>(vb[cur], L.N, n, user, ipos, ineg, U1, I1, coef, rec);
-  HIP_TRY(hipGetLastError());
-  const int64_t units = L.N / ADV_CHUNK + R + 1;
-  ACF_RET(DISPATCH_GEOM(d, launch_adv_sum, P, Q, d, U1, R, off, rec, part, nP, nQ, units, s));
-  HIP_TRY(hipGetLastError());
   return ACF_OK;
 }
 

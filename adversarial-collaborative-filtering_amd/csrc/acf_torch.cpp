@@ -17,6 +17,7 @@
 //   acf::recommend_topk        the k best items per user and their scores (no reference counterpart)
 //   acf::adv_direction         adv_update's direction over a whole triplet stream (utils.py:145-154)
 //   acf::adv_apply             delta = N * eps and W + delta (APR.py:130-141,190)
+//   acf::adv_pgd               iterated projected gradient attack on the whole stream
 //   acf::fold_in_users         rows for new users against a frozen Q (no reference counterpart)
 //   acf::fold_in_items         rows for new items against frozen P and Q (no reference counterpart)
 //   acf::eval_positions_multi  positions of several held-out items per user, one sweep per user
@@ -410,6 +411,50 @@ std::tuple<at::Tensor, at::Tensor> adv_apply(const at::Tensor& W, const at::Tens
   return {sum, delta};
 }
 
+// `iters` projected gradient steps on the whole stream's clean loss (acf_adv_pgd, planned once
+// inside the call, indices range-checked): (delta_P, delta_Q, losses float64 [iters + 1])
+std::tuple<at::Tensor, at::Tensor, at::Tensor> adv_pgd(const at::Tensor& P, const at::Tensor& Q,
+                                                       const at::Tensor& user_, const at::Tensor& item_pos_,
+                                                       const at::Tensor& item_neg_, double eps, int64_t iters,
+                                                       c10::optional<double> alpha_, c10::string_view side,
+                                                       const c10::optional<at::Tensor>& dP0,
+                                                       const c10::optional<at::Tensor>& dQ0, double clip_lo,
+                                                       double clip_hi) {
+  need_table(P, "embedding_P", P);
+  need_table(Q, "embedding_Q", P);
+  TORCH_CHECK(P.size(1) == Q.size(1), "embedding_P and embedding_Q dims differ");
+  TORCH_CHECK(iters >= 1 && iters <= ACF_ADV_PGD_MAX_ITERS, "iters must lie in [1, ", ACF_ADV_PGD_MAX_ITERS, "]");
+  TORCH_CHECK(std::isfinite(eps) && eps >= 0, "eps must be finite and >= 0");
+  const double alpha = alpha_.has_value() ? *alpha_ : 2.5 * eps / (double)iters;
+  TORCH_CHECK(std::isfinite(alpha) && alpha >= 0, "alpha must be finite and >= 0");
+  TORCH_CHECK(side == "both" || side == "user" || side == "item", "side must be 'both', 'user' or 'item'");
+  const int32_t sd = side == "both" ? ACF_ADV_SIDE_BOTH : side == "user" ? ACF_ADV_SIDE_USER : ACF_ADV_SIDE_ITEM;
+  auto need_start = [&](const c10::optional<at::Tensor>& t, const at::Tensor& w, const char* name) {
+    if (!t.has_value()) return;
+    need_table(*t, name, P);
+    TORCH_CHECK(t->sizes() == w.sizes(), name, " must have its table's shape");
+  };
+  need_start(dP0, P, "delta_P0");
+  need_start(dQ0, Q, "delta_Q0");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(P.device());
+  at::Tensor u = idx32(user_, "user", P), i = idx32(item_pos_, "item_pos", P), j = idx32(item_neg_, "item_neg", P);
+  const int64_t n = u.numel();
+  TORCH_CHECK(i.numel() == n && j.numel() == n, "user, item_pos and item_neg must have equal lengths");
+  size_t ws = 0;
+  ok(acf_adv_pgd_workspace(n, P.size(0), Q.size(0), (int32_t)P.size(1), &ws), "acf_adv_pgd_workspace");
+  at::Tensor work = at::empty({(int64_t)((ws + 7) / 8)}, u.options().dtype(at::kLong));
+  at::Tensor dP = at::empty_like(P), dQ = at::empty_like(Q);
+  at::Tensor losses = at::empty({iters + 1}, P.options().dtype(at::kDouble));
+  ok(acf_adv_pgd(P.data_ptr<float>(), Q.data_ptr<float>(), P.size(0), Q.size(0), (int32_t)P.size(1),
+                 n ? u.data_ptr<int32_t>() : nullptr, n ? i.data_ptr<int32_t>() : nullptr,
+                 n ? j.data_ptr<int32_t>() : nullptr, n, (float)clip_lo, (float)clip_hi, nullptr, 0, (float)eps,
+                 (float)alpha, (int32_t)iters, sd, dP0.has_value() ? dP0->data_ptr<float>() : nullptr,
+                 dQ0.has_value() ? dQ0->data_ptr<float>() : nullptr, dP.data_ptr<float>(), dQ.data_ptr<float>(),
+                 losses.data_ptr<double>(), work.data_ptr(), ws, 1, stream_of(P)),
+     "acf_adv_pgd");
+  return {dP, dQ, losses};
+}
+
 // a CSR's offsets: int64 [n + 1] on `like`'s device, 0 = off[0] <= ... <= off[n] = total (read back once)
 void need_csr(const at::Tensor& off, const char* name, int64_t n, int64_t total, const at::Tensor& like) {
   need(off, name, at::kLong, 1);
@@ -682,6 +727,9 @@ TORCH_LIBRARY(acf, m) {
   m.def("adv_direction(Tensor P, Tensor Q, Tensor user, Tensor item_pos, Tensor item_neg, str adv=\"grad\", "
         "int seed=0, int call=1, int t=0, float clip_lo=-80.0, float clip_hi=1e8) -> (Tensor nP, Tensor nQ)");
   m.def("adv_apply(Tensor W, Tensor N, float eps) -> (Tensor sum, Tensor delta)");
+  m.def("adv_pgd(Tensor P, Tensor Q, Tensor user, Tensor item_pos, Tensor item_neg, float eps, int iters=10, "
+        "float? alpha=None, str side=\"both\", Tensor? delta_P0=None, Tensor? delta_Q0=None, float clip_lo=-80.0, "
+        "float clip_hi=1e8) -> (Tensor delta_P, Tensor delta_Q, Tensor losses)");
   m.def("fold_in_users(Tensor Q, Tensor user_off, Tensor item_pos, Tensor item_neg, int epochs, int batch=512, "
         "Tensor? init=None, Tensor? acc_init=None, float lr=0.05, float eps=0.5, float reg=0., float reg_adv=1., "
         "bool adver=True, float clip_lo=-80., float clip_hi=100000000.) -> (Tensor P_new, Tensor acc_new, Tensor loss)");
@@ -711,6 +759,7 @@ TORCH_LIBRARY_IMPL(acf, CUDA, m) {
   m.impl("recommend_topk", &recommend_topk);
   m.impl("adv_direction", &adv_direction);
   m.impl("adv_apply", &adv_apply);
+  m.impl("adv_pgd", &adv_pgd);
   m.impl("fold_in_users", &fold_in_users);
   m.impl("fold_in_items", &fold_in_items);
   m.impl("eval_positions_multi", &eval_positions_multi);

@@ -195,31 +195,107 @@ def triplet_arrays(triplets):
     return cat(u), cat(i), cat(j)
 
 
-def robustness(model, dataset, plan: EvalPlan, triplets, eps_list, modes=("grad", "random"), seed=0):
+def _metrics_row(mode, eps, pos, plan):
+    raw = metrics_from_positions(pos, plan.n_neg, plan.K)
+    hr, ndcg, auc = raw.mean(axis=0)[:, -1].tolist() if len(pos) else (0.0, 0.0, 0.0)
+    return (mode, eps, hr, ndcg, auc)
+
+
+def robustness(model, dataset, plan: EvalPlan, triplets, eps_list, modes=("grad", "random"), seed=0, iters=10,
+               step=None, side="both"):
     """HR@K, NDCG@K and AUC (K = plan.K) under a perturbation of both tables, per
-    mode and eps: rows (mode, eps, hr, ndcg, auc).  One direction per mode over
-    ALL the triplets as one batch (ops.adv_direction; "random": the draw of
-    (seed, call 1, t 0)), then per eps one ops.adv_apply per table and one
-    positions() on the perturbed tables.  eps = 0 reproduces
+    mode and eps: rows (mode, eps, hr, ndcg, auc).  "grad" / "random": one
+    direction per mode over ALL the triplets as one batch (ops.adv_direction;
+    "random": the draw of (seed, call 1, t 0)), then per eps one ops.adv_apply per
+    table and one positions() on the perturbed tables.  "pgd": per eps > 0 one
+    ops.adv_pgd from zeros (`iters` steps of size `step`, None: 2.5 * eps / iters,
+    moving `side`), every eps on one shared ops.adv_plan, then positions() on
+    (P + delta_P, Q + delta_Q); it needs at least one triplet.  eps = 0 reproduces
     evaluate(output_adv=0).  The model's tables and delta_P / delta_Q are left
     as they are."""
     for mode in modes:
-        if mode not in ops.ADV_MODES:
-            raise ValueError(f"mode must be one of {sorted(ops.ADV_MODES)}, got {mode!r}")
+        if mode not in ops.ADV_MODES and mode != "pgd":
+            raise ValueError(f"mode must be one of {sorted(ops.ADV_MODES) + ['pgd']}, got {mode!r}")
     eps_list = [float(e) for e in eps_list]
     if any(e < 0 for e in eps_list):
         raise ValueError("eps must be >= 0")
+    pgd = "pgd" in modes
+    if pgd:
+        for e in eps_list:
+            ops.pgd_arguments(e, iters, step, side)
     u, i, j = triplet_arrays(triplets)
+    if pgd:
+        if not len(u) == len(i) == len(j):
+            raise ValueError("user, item_pos and item_neg must have equal lengths")
+        if len(u) == 0:
+            raise ValueError("the 'pgd' mode must be given at least one triplet: without a stream there is no "
+                             "gradient to iterate on")
     P, Q = model.embedding_P, model.embedding_Q
     rows = []
+    adv_plan = None
     for mode in modes:
+        if mode == "pgd":
+            if adv_plan is None:
+                adv_plan = ops.adv_plan(u, i, j, P.shape[0], Q.shape[0], device=P.device)
+            for eps in eps_list:
+                Pa, Qa = P, Q
+                if eps > 0:
+                    dP, dQ, _ = ops.adv_pgd(P, Q, u, i, j, eps, iters=iters, alpha=step, side=side, plan=adv_plan)
+                    Pa, Qa = ops.adv_apply(P, dP, 1.0), ops.adv_apply(Q, dQ, 1.0)
+                rows.append(_metrics_row(mode, eps, positions(Pa, Qa, plan).cpu().numpy(), plan))
+            continue
         nP, nQ = ops.adv_direction(P, Q, u, i, j, adv=mode, seed=int(seed or 0), call=1, t=0)
         for eps in eps_list:
             pos = positions(ops.adv_apply(P, nP, eps), ops.adv_apply(Q, nQ, eps), plan).cpu().numpy()
-            raw = metrics_from_positions(pos, plan.n_neg, plan.K)
-            hr, ndcg, auc = raw.mean(axis=0)[:, -1].tolist() if len(pos) else (0.0, 0.0, 0.0)
-            rows.append((mode, eps, hr, ndcg, auc))
+            rows.append(_metrics_row(mode, eps, pos, plan))
     return rows
+
+
+def pgd_host(P, Q, u, i, j, eps, iters=10, alpha=None, side="both", start=None, lo=-80.0, hi=1e8):
+    """ops.adv_pgd restated in float64 numpy, the tests' yardstick: (delta_P,
+    delta_Q, losses [iters + 1]).  Per iteration the clean BPR gradient of all the
+    triplets at (P + delta_P, Q + delta_Q), summed per row and l2-normalised with the
+    1e-12 floor; on every moving side v = delta + alpha * n, rows with |v| > eps
+    scaled by eps / |v|.  start: None (zeros) or (delta_P0, delta_Q0), taken as given.
+    alpha None: 2.5 * eps / iters."""
+    eps, iters, alpha, _ = ops.pgd_arguments(eps, iters, alpha, side)
+    P, Q = np.asarray(P, dtype=np.float64), np.asarray(Q, dtype=np.float64)
+    u, i, j = (np.asarray(x, dtype=np.int64).reshape(-1) for x in (u, i, j))
+    if not len(u) == len(i) == len(j):
+        raise ValueError("user, item_pos and item_neg must have equal lengths")
+    if start is None:
+        dP, dQ = np.zeros_like(P), np.zeros_like(Q)
+    else:
+        dP, dQ = np.array(start[0], dtype=np.float64), np.array(start[1], dtype=np.float64)
+        if dP.shape != P.shape or dQ.shape != Q.shape:
+            raise ValueError("start must be (delta_P0, delta_Q0) with the tables' shapes")
+
+    def grad(Pa, Qa):
+        p, qi, qj = Pa[u], Qa[i], Qa[j]
+        x = (p * qi).sum(1) - (p * qj).sum(1)
+        g = -1.0 / (np.exp(np.clip(x, lo, hi)) + 1.0) * ((x >= lo) & (x <= hi))
+        gP, gQ = np.zeros_like(Pa), np.zeros_like(Qa)
+        np.add.at(gP, u, g[:, None] * qi)
+        np.add.at(gP, u, -g[:, None] * qj)
+        np.add.at(gQ, i, g[:, None] * p)
+        np.add.at(gQ, j, -g[:, None] * p)
+        unit = lambda t: t / np.sqrt(np.maximum((t * t).sum(1, keepdims=True), 1e-12))  # noqa: E731
+        return unit(gP), unit(gQ), float(np.logaddexp(0.0, -np.clip(x, lo, hi)).sum())
+
+    def step(delta, n):
+        v = delta + alpha * n
+        s = np.sqrt((v * v).sum(1, keepdims=True))
+        return np.where(s <= eps, v, v * (eps / np.where(s > 0, s, 1.0)))
+
+    losses = np.zeros(iters + 1)
+    for k in range(iters):
+        nP, nQ, losses[k] = grad(P + dP, Q + dQ)
+        if side != "item":
+            dP = step(dP, nP)
+        if side != "user":
+            dQ = step(dQ, nQ)
+    losses[iters] = grad(P + dP, Q + dQ)[2]
+    return dP, dQ, losses
 
 
 # ---- certified robustness: worst-case positions under an eps attack -----------

@@ -254,11 +254,13 @@ class MF:
         from .train import adv_update
         return adv_update(self, None, train_batches, adv=adv)
 
-    def robustness(self, dataset, plan, triplets, eps_list, modes=("grad", "random"), seed=0):
+    def robustness(self, dataset, plan, triplets, eps_list, modes=("grad", "random"), seed=0, iters=10, step=None,
+                   side="both"):
         """evaluate.robustness: rows (mode, eps, hr@K, ndcg@K, auc) under a
-        perturbation of both tables."""
+        perturbation of both tables; iters, step and side are the "pgd" mode's."""
         from .evaluate import robustness
-        return robustness(self, dataset, plan, triplets, eps_list, modes=modes, seed=seed)
+        return robustness(self, dataset, plan, triplets, eps_list, modes=modes, seed=seed, iters=iters, step=step,
+                          side=side)
 
     def certified(self, plan, eps_list, side="user", cutoffs=None):
         """evaluate.certified: rows (side, eps, K, hr_lb, ndcg_lb, auc_lb), lower

@@ -1199,8 +1199,83 @@ def adv_direction_workspace(n: int, num_user_rows: int, num_item_rows: int, dim:
     return _workspace_bytes("acf_adv_direction_workspace", n, num_user_rows, num_item_rows, dim)
 
 
+class AdvPlan:
+    """What adv_plan returns: the part of the gradient direction that depends on
+    the triplets alone (sorted term values, row offsets, range-error word) in a
+    device buffer it owns, with the index tensors it was built from."""
+
+    def __init__(self, user, item_pos, item_neg, num_user_rows: int, num_item_rows: int, buf, nbytes: int):
+        self.user, self.item_pos, self.item_neg = user, item_pos, item_neg
+        self.n = int(user.numel())
+        self.num_user_rows, self.num_item_rows = int(num_user_rows), int(num_item_rows)
+        self.buf, self.nbytes = buf, int(nbytes)
+
+    @property
+    def device(self):
+        return self.buf.device
+
+    def fits(self, P, Q) -> None:
+        """ValueError unless the plan was built for tables of P's and Q's rows on their device."""
+        if (P.shape[0], Q.shape[0]) != (self.num_user_rows, self.num_item_rows):
+            raise ValueError(f"plan was built for {self.num_user_rows} x {self.num_item_rows} table rows, "
+                             f"got {P.shape[0]} x {Q.shape[0]}")
+        if P.device != self.device:
+            raise ValueError(f"plan is on {self.device}, the tables on {P.device}")
+
+
+def _triplet_lengths(user, item_pos, item_neg) -> int:
+    n = len(user)
+    if len(item_pos) != n or len(item_neg) != n:
+        raise ValueError("user, item_pos and item_neg must have equal lengths")
+    if n > ADV_MAX_TRIPLETS:
+        raise ValueError(f"at most {ADV_MAX_TRIPLETS} triplets, got {n}")
+    return n
+
+
+def adv_plan(user, item_pos, item_neg, num_user_rows: int, num_item_rows: int, device=None, check: bool = True):
+    """Plan the whole-stream gradient direction once (acf_adv_plan): the stable
+    sort of the 4n terms by row and the row offsets, which depend on the triplets
+    alone.  The AdvPlan serves adv_direction(plan=...) and adv_pgd(plan=...) for
+    every table pair of these row counts.  device: default the index tensors'
+    HIP device.  check: an index outside its table raises NativeIndexError."""
+    n = _triplet_lengths(user, item_pos, item_neg)
+    U1, I1 = int(num_user_rows), int(num_item_rows)
+    if U1 <= 0 or I1 <= 0:
+        raise ValueError("num_user_rows and num_item_rows must be positive")
+    if device is None:
+        if not isinstance(user, torch.Tensor) or user.device.type != "cuda":
+            raise ValueError("adv_plan needs a HIP device: pass device= or device index tensors; there is no CPU path")
+        device = user.device
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError(f"adv_plan needs a HIP device (got {dev}); there is no CPU path")
+    u, i, j = (_idx(x, nm, dev) for x, nm in ((user, "user"), (item_pos, "item_pos"), (item_neg, "item_neg")))
+    if not (u.numel() == i.numel() == j.numel() == n):
+        raise ValueError("user, item_pos and item_neg must have equal lengths")
+    pb, wb = ctypes.c_size_t(), ctypes.c_size_t()
+    _native.call("acf_adv_plan_workspace", n, U1, I1, ctypes.byref(pb), ctypes.byref(wb))
+    buf = _workspace(pb.value, 8, dev)
+    work = _workspace(wb.value, 8, dev) if wb.value else None
+    with _on(dev):
+        _native.call("acf_adv_plan", u.data_ptr() if n else None, i.data_ptr() if n else None,
+                     j.data_ptr() if n else None, n, U1, I1, buf.data_ptr(), pb.value, _ptr(work), wb.value,
+                     int(bool(check)), _stream_ptr(dev))
+    return AdvPlan(u, i, j, U1, I1, buf, pb.value)
+
+
+def _plan_type(plan) -> None:
+    if not isinstance(plan, AdvPlan):
+        raise TypeError(f"plan must be an AdvPlan (ops.adv_plan), got {type(plan).__name__}")
+
+
+def _plan_matches(plan, P, Q, n: int) -> None:
+    plan.fits(P, Q)
+    if plan.n != n:
+        raise ValueError(f"plan was built for {plan.n} triplets, got {n}")
+
+
 def adv_direction(P, Q, user, item_pos, item_neg, adv: str = "grad", seed: int = 0, call: int = 1, t: int = 0,
-                  clip_lo=CLIP_LO, clip_hi=CLIP_HI, check: bool = True):
+                  clip_lo=CLIP_LO, clip_hi=CLIP_HI, check: bool = True, plan=None):
     """The adversarial direction of the WHOLE triplet stream as one batch
     (utils.py:145-154): dense unit-direction tables (nP [rows of P, d], nQ [rows of
     Q, d]); delta = direction * eps is adv_apply's job, so one direction serves
@@ -1210,9 +1285,18 @@ def adv_direction(P, Q, user, item_pos, item_neg, adv: str = "grad", seed: int =
     order, so equal inputs give equal bits.  adv="random" (APR.py:170-177): every
     row is the step's l2-normalised truncated-normal draw for (seed, call, t,
     table, row); the triplets are not read.  P and Q are never written.
-    check: an index outside its table raises NativeIndexError."""
+    check: an index outside its table raises NativeIndexError.
+    plan: an AdvPlan of these triplets (adv_plan): grad mode skips the sort and
+    takes acf_adv_direction_planned, the same bits; the indices are the plan's
+    own (range-checked when it was built)."""
     if adv not in ADV_MODES:
         raise ValueError(f"adv must be one of {sorted(ADV_MODES)}, got {adv!r}")
+    if plan is not None and adv == "grad":
+        _plan_type(plan)
+        n = _triplet_lengths(user, item_pos, item_neg)
+        _table_pair(P, Q)
+        _plan_matches(plan, P, Q, n)
+        return _adv_direction_planned(P, Q, plan, clip_lo, clip_hi)[:2]
     n = len(user)
     if len(item_pos) != n or len(item_neg) != n:
         raise ValueError("user, item_pos and item_neg must have equal lengths")
@@ -1235,6 +1319,113 @@ def adv_direction(P, Q, user, item_pos, item_neg, adv: str = "grad", seed: int =
                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF, int(t),
                      nP.data_ptr(), nQ.data_ptr(), _ptr(work), nbytes, int(bool(check)), _stream_ptr(dev))
     return nP, nQ
+
+
+def _adv_direction_planned(P, Q, plan: AdvPlan, clip_lo=CLIP_LO, clip_hi=CLIP_HI, want_loss: bool = False):
+    """(nP, nQ, loss float64 [1] or None) of acf_adv_direction_planned; arguments already checked."""
+    dev = P.device
+    settle_tables()
+    U1, I1, d, n = P.shape[0], Q.shape[0], P.shape[1], plan.n
+    nP = torch.empty((U1, d), dtype=torch.float32, device=dev)
+    nQ = torch.empty((I1, d), dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float64, device=dev) if want_loss else None
+    nbytes = adv_direction_workspace(n, U1, I1, d) if n else 0
+    work = _workspace(nbytes, 8, dev) if nbytes else None
+    with _on(dev):
+        _native.call("acf_adv_direction_planned", P.data_ptr(), Q.data_ptr(), U1, I1, d,
+                     plan.user.data_ptr() if n else None, plan.item_pos.data_ptr() if n else None,
+                     plan.item_neg.data_ptr() if n else None, n, clip_lo, clip_hi, plan.buf.data_ptr(), plan.nbytes,
+                     nP.data_ptr(), nQ.data_ptr(), _ptr(loss), _ptr(work), nbytes, _stream_ptr(dev))
+    return nP, nQ, loss
+
+
+PGD_SIDES = {"both": 0, "user": 1, "item": 2}  # ACF_ADV_SIDE_*
+PGD_MAX_ITERS = 1024                           # ACF_ADV_PGD_MAX_ITERS
+
+
+def pgd_arguments(eps, iters, alpha, side):
+    """(eps, iters, alpha, side id) of adv_pgd after its checks (ValueError / TypeError);
+    alpha None is 2.5 * eps / iters."""
+    if isinstance(iters, bool) or not isinstance(iters, int):
+        raise TypeError(f"iters must be an int, got {type(iters).__name__}")
+    if not 1 <= iters <= PGD_MAX_ITERS:
+        raise ValueError(f"iters must lie in [1, {PGD_MAX_ITERS}], got {iters}")
+    eps = float(eps)
+    if not (math.isfinite(eps) and eps >= 0):
+        raise ValueError(f"eps must be finite and >= 0, got {eps}")
+    alpha = 2.5 * eps / iters if alpha is None else float(alpha)
+    if not (math.isfinite(alpha) and alpha >= 0):
+        raise ValueError(f"alpha must be finite and >= 0, got {alpha}")
+    if side not in PGD_SIDES:
+        raise ValueError(f"side must be one of {sorted(PGD_SIDES)}, got {side!r}")
+    return eps, iters, alpha, PGD_SIDES[side]
+
+
+def adv_pgd_workspace(n: int, num_user_rows: int, num_item_rows: int, dim: int) -> int:
+    """Bytes of device workspace acf_adv_pgd needs for n triplets (a host-only query)."""
+    if not 0 <= int(n) <= ADV_MAX_TRIPLETS:
+        raise ValueError(f"n must lie in [0, {ADV_MAX_TRIPLETS}], got {n}")
+    return _workspace_bytes("acf_adv_pgd_workspace", n, num_user_rows, num_item_rows, dim)
+
+
+def adv_pgd(P, Q, user, item_pos, item_neg, eps: float, iters: int = 10, alpha=None, side: str = "both", start=None,
+            plan=None, check: bool = True, seed: int = 0, clip_lo=CLIP_LO, clip_hi=CLIP_HI):
+    """An iterated gradient attack on the clean loss of the WHOLE triplet stream
+    (acf_adv_pgd): (delta_P, delta_Q, losses).  From delta_0 = start, `iters` times:
+    the l2-normalised per-row gradient direction n at (P + delta_P, Q + delta_Q)
+    (adv_direction's, planned once), then on every moving side per row
+    delta <- project(delta + alpha * n) onto the L2 ball of radius eps.
+    alpha=None: 2.5 * eps / iters.  side: "both", or "user" / "item" to move only
+    that table's delta (both tables always enter the gradient; the other delta
+    stays at its start).  start: None (zeros), "random" (eps x adv_direction's
+    random draw for (seed, call 1, t 0)) or (delta_P0, delta_Q0), taken as given.
+    losses: float64 [iters + 1] on the device, losses[k] the stream's summed clean
+    loss at iterate k.  plan: an AdvPlan of these triplets (adv_plan), else the
+    call plans once.  Equal inputs give equal bits; P and Q are never written.
+    Bad arguments raise ValueError / TypeError before any native call; check: an
+    index outside its table raises NativeIndexError."""
+    eps, iters, alpha, sd = pgd_arguments(eps, iters, alpha, side)
+    n = _triplet_lengths(user, item_pos, item_neg)
+    if plan is not None:
+        _plan_type(plan)
+    if isinstance(start, str):
+        if start != "random":
+            raise ValueError(f"start must be None, 'random' or (delta_P0, delta_Q0), got {start!r}")
+    elif start is not None:
+        if not isinstance(start, (tuple, list)) or len(start) != 2:
+            raise TypeError("start must be None, 'random' or a (delta_P0, delta_Q0) pair")
+        for t, w, nm in ((start[0], P, "delta_P0"), (start[1], Q, "delta_Q0")):
+            if isinstance(t, torch.Tensor) and isinstance(w, torch.Tensor) and t.shape != w.shape:
+                raise ValueError(f"{nm} {tuple(t.shape)} must have its table's shape {tuple(w.shape)}")
+    dev = _table_pair(P, Q)
+    if plan is not None:
+        _plan_matches(plan, P, Q, n)
+        u, i, j = plan.user, plan.item_pos, plan.item_neg
+    else:
+        u, i, j = (_idx(x, nm, dev) for x, nm in ((user, "user"), (item_pos, "item_pos"), (item_neg, "item_neg")))
+        if not (u.numel() == i.numel() == j.numel() == n):
+            raise ValueError("user, item_pos and item_neg must have equal lengths")
+    if isinstance(start, (tuple, list)):
+        _require(start[0], "delta_P0", torch.float32, dev, 2)
+        _require(start[1], "delta_Q0", torch.float32, dev, 2)
+    settle_tables()
+    U1, I1, d = P.shape[0], Q.shape[0], P.shape[1]
+    if isinstance(start, str):  # "random"
+        rP, rQ = adv_direction(P, Q, u[:0], i[:0], j[:0], adv="random", seed=seed, call=1, t=0)
+        start = (adv_apply(P, rP, eps, want_delta=True)[1], adv_apply(Q, rQ, eps, want_delta=True)[1])
+    dP = torch.empty((U1, d), dtype=torch.float32, device=dev)
+    dQ = torch.empty((I1, d), dtype=torch.float32, device=dev)
+    losses = torch.empty(iters + 1, dtype=torch.float64, device=dev)
+    nbytes = adv_pgd_workspace(n, U1, I1, d)
+    work = _workspace(nbytes, 8, dev)
+    with _on(dev):
+        _native.call("acf_adv_pgd", P.data_ptr(), Q.data_ptr(), U1, I1, d, u.data_ptr() if n else None,
+                     i.data_ptr() if n else None, j.data_ptr() if n else None, n, clip_lo, clip_hi,
+                     plan.buf.data_ptr() if plan is not None else None, plan.nbytes if plan is not None else 0,
+                     eps, alpha, iters, sd, start[0].data_ptr() if start is not None else None,
+                     start[1].data_ptr() if start is not None else None, dP.data_ptr(), dQ.data_ptr(),
+                     losses.data_ptr(), work.data_ptr(), nbytes, int(bool(check)), _stream_ptr(dev))
+    return dP, dQ, losses
 
 
 def adv_apply(W, N, eps: float, want_delta: bool = False):

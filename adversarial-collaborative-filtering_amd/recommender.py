@@ -295,12 +295,13 @@ class APR(Recommender):
         self._ensure()
         return self.model.adv_update((([x_train[0]], [x_train[1]], [x_train[2]])), adv=adv)
 
-    def robustness(self, dataset, plan, x_train, eps_list, modes=("grad", "random"), seed=0):
+    def robustness(self, dataset, plan, x_train, eps_list, modes=("grad", "random"), seed=0, iters=10, step=None,
+                   side="both"):
         """evaluate.robustness on the triplets of get_train_instances: rows
-        (mode, eps, hr@K, ndcg@K, auc)."""
+        (mode, eps, hr@K, ndcg@K, auc); iters, step and side are the "pgd" mode's."""
         self._ensure()
         return self.model.robustness(dataset, plan, ([x_train[0]], [x_train[1]], [x_train[2]]), eps_list,
-                                     modes=modes, seed=seed)
+                                     modes=modes, seed=seed, iters=iters, step=step, side=side)
 
     def certified(self, plan, eps_list, side="user", cutoffs=None):
         """evaluate.certified against an all-items plan: rows (side, eps, K, hr_lb,

@@ -18,6 +18,9 @@ SURVEY.md §8(b) proposes:
 - ``adv_direction(P, Q, user, item_pos, item_neg, adv, seed, call, t, clip_lo, clip_hi) -> (nP, nQ)``
   and ``adv_apply(W, N, eps) -> (sum, delta)``: the whole-stream adversarial direction and
   the perturbed table (``ops.adv_direction`` / ``ops.adv_apply``);
+- ``adv_pgd(P, Q, user, item_pos, item_neg, eps, iters, alpha, side, delta_P0, delta_Q0, clip_lo, clip_hi)
+  -> (delta_P, delta_Q, losses)``: the iterated projected gradient attack (``ops.adv_pgd``, the same bits;
+  the op plans inside the call and always range-checks);
 - ``fold_in_users(Q, user_off, item_pos, item_neg, epochs, batch, init, acc_init, lr, eps, reg, reg_adv,
   adver, clip_lo, clip_hi) -> (P_new, acc_new, loss)``: rows for new users against a frozen
   item table (``ops.fold_in_users``, the same bits).  The op always synchronises with the host:
@@ -62,6 +65,7 @@ from . import build_native
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libacf_torch.so")
 OPS = ("bpr_apr_step", "apr_train", "gather_bpr_fwd_bwd", "row_segment_sum", "l2norm_perturb",
        "sparse_adagrad_apply", "score_rank", "score_rank_all", "recommend_topk", "adv_direction", "adv_apply",
+       "adv_pgd",
        "fold_in_users", "fold_in_items", "eval_positions_multi", "rank_metrics", "eval_positions_worst", "eval_radius",
        "release_contexts")
 _lock = threading.Lock()

@@ -618,6 +618,62 @@ int acf_adv_direction(const float* P, const float* Q, int64_t num_user_rows, int
 int acf_adv_apply(const float* W, const float* N, int64_t rows, int32_t dim, float eps, float* delta_out,
                   float* sum_out, void* stream);
 
+/* ---- robustness evaluation: a kept plan, the planned direction, an iterated attack
+ * (no reference counterpart).  As above: no context, P and Q
+ * never written, everything on `stream`, no float atomics, every size from a
+ * host-only query, buffers 16-byte aligned, a short one is ACF_E_INVALID.
+ * acf_adv_plan: everything of acf_adv_direction's grad mode that depends on the
+ *   triplets alone -- the 4n term values sorted stably by row, the row offsets and
+ *   the range-error word -- written to the caller's `plan` (device memory of
+ *   plan_bytes from acf_adv_plan_workspace, which also gives the call's scratch
+ *   `workspace` size).  The tables are not read, so one plan serves every (P, Q)
+ *   of num_user_rows x num_item_rows; it is valid for exactly the (user, item_pos,
+ *   item_neg, n, num_user_rows, num_item_rows) it was built from.  check as in
+ *   acf_adv_direction (one sync after the first kernel).
+ * acf_adv_direction_planned: nP, nQ of acf_adv_direction's grad mode, the same
+ *   bits, from a plan and the same triplets: coefficients, term records, chunk
+ *   sums, combine; no sort.  workspace: acf_adv_direction_workspace(n, ...) bytes.
+ *   loss_out (device, may be NULL): the stream's clean loss sum_t softplus(-clip(x_t))
+ *   at (P, Q), each fp32 term widened to fp64 and added in a fixed order (a tree over
+ *   the 256 triplets of a block, then blocks b, b + 256, ... per lane and the same
+ *   tree): the same bits every run.  Never synchronises.
+ * acf_adv_pgd: `iters` projected gradient steps.  delta_0 = (dP0, dQ0) (NULL:
+ *   zeros; taken as given, not projected); for k = 0..iters-1: (nP, nQ) = the
+ *   planned direction at (P + dP_k, Q + dQ_k), and on every moving side, per row,
+ *   v = delta_k + alpha * n (two rounded operations), s = |v|_2 in fp32 (per-lane
+ *   sums of rounded squares over the row's float4 chunks lane, lane + LPR, ..., then
+ *   the row-group's butterfly: xor 1, 2, 4, 8, 16, 32), delta_{k+1} = v if s <= eps
+ *   else v * (eps / s) (one division per row), P + delta_{k+1} one rounded add.
+ *   side: ACF_ADV_SIDE_BOTH, _USER (dQ stays dQ0) or _ITEM (dP stays dP0); both
+ *   tables always enter the gradient.  dP, dQ: the final delta tables (may alias
+ *   dP0, dQ0); loss (device, fp64 [iters + 1]): loss[k] the clean loss at iterate k,
+ *   loss[iters] from one more coefficient pass.  plan: NULL (the call plans once in
+ *   its workspace) or an acf_adv_plan of the same triplets; with check != 0 the
+ *   call synchronises once and returns ACF_E_RANGE when the plan's error word is
+ *   set.  n = 0: every moving row is projected once, loss is all zero.
+ *   ACF_E_INVALID before any launch: iters outside [1, ACF_ADV_PGD_MAX_ITERS], eps
+ *   or alpha negative or not finite, an unknown side, a short workspace or plan. */
+#define ACF_ADV_PGD_MAX_ITERS 1024
+#define ACF_ADV_SIDE_BOTH 0
+#define ACF_ADV_SIDE_USER 1
+#define ACF_ADV_SIDE_ITEM 2
+int acf_adv_plan_workspace(int64_t n, int64_t num_user_rows, int64_t num_item_rows, size_t* plan_bytes,
+                           size_t* bytes);
+int acf_adv_plan(const int32_t* user, const int32_t* item_pos, const int32_t* item_neg, int64_t n,
+                 int64_t num_user_rows, int64_t num_item_rows, void* plan, size_t plan_bytes, void* workspace,
+                 size_t workspace_bytes, int32_t check, void* stream);
+int acf_adv_direction_planned(const float* P, const float* Q, int64_t num_user_rows, int64_t num_item_rows,
+                              int32_t dim, const int32_t* user, const int32_t* item_pos, const int32_t* item_neg,
+                              int64_t n, float clip_lo, float clip_hi, const void* plan, size_t plan_bytes,
+                              float* nP, float* nQ, double* loss_out, void* workspace, size_t workspace_bytes,
+                              void* stream);
+int acf_adv_pgd_workspace(int64_t n, int64_t num_user_rows, int64_t num_item_rows, int32_t dim, size_t* bytes);
+int acf_adv_pgd(const float* P, const float* Q, int64_t num_user_rows, int64_t num_item_rows, int32_t dim,
+                const int32_t* user, const int32_t* item_pos, const int32_t* item_neg, int64_t n, float clip_lo,
+                float clip_hi, const void* plan, size_t plan_bytes, float eps, float alpha, int32_t iters,
+                int32_t side, const float* dP0, const float* dQ0, float* dP, float* dQ, double* loss,
+                void* workspace, size_t workspace_bytes, int32_t check, void* stream);
+
 /* ---- fold-in: new users against a frozen item table --------------------------
  * (no reference counterpart: the reference can only retrain.)  User r of the CSR
  * user_off int64 [n + 1] / item_pos [T] gets a row fitted to its list while Q
