@@ -72,6 +72,12 @@ def parse_args(argv=None, flavor="ori"):
                         "(1 to 1024), written as 'pgd' rows after the others (0: off).")
     p.add_argument("--robust_step", type=parse_robust_step, default=None,
                    help="Step size of --robust_iters (default: 2.5 * eps / iters).")
+    p.add_argument("--robust_lists", type=parse_radius_cutoffs, default=[],
+                   help="With --robust_eps: also how far each attack moves the users' top-K lists, at these K "
+                        "(comma separated, e.g. \"1,10,100\"; 1 to 8 integers in [1, 128]; the lists are as long "
+                        "as the largest): Jaccard, rank-biased overlap and overlap against the clean lists, and "
+                        "coverage, Gini, entropy, average popularity and long-tail share of what is recommended, "
+                        "to <out>/<runName>.lists (empty: off).")
     p.add_argument("--certify_eps", type=parse_eps_list, default=[],
                    help="After training, certify the ranking at these eps (comma separated, e.g. \"0.1,0.5,1\"): "
                         "lower bounds of HR@K, NDCG@K and AUC (all-items evaluation) under EVERY perturbation of "
@@ -246,6 +252,29 @@ def read_certified(file):
             parts = line.rstrip("\n").split("\t")
             if len(parts) != 6:
                 raise ValueError(f"{file}: line {n} has {len(parts)} fields, expected 6")
+            rows.append((parts[0], float(parts[1]), int(parts[2]), *[float(x) for x in parts[3:]]))
+    return rows
+
+
+def write_lists(path, name, rows):
+    """One line "mode<TAB>eps<TAB>K<TAB>jaccard<TAB>rbo<TAB>overlap<TAB>coverage<TAB>gini<TAB>entropy<TAB>arp
+    <TAB>aplt" per row of evaluate.list_robustness (floats by repr: the reader gets the same values back)."""
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, name), "w") as f:
+        for mode, eps, K, *vals in rows:
+            if len(vals) != 8:
+                raise ValueError(f"a lists row has 8 metrics, got {len(vals)}")
+            f.write("%s\t%r\t%d\t%s\n" % (mode, float(eps), int(K), "\t".join(repr(float(v)) for v in vals)))
+
+
+def read_lists(file):
+    """The rows [(mode, eps, K, jaccard, rbo, overlap, coverage, gini, entropy, arp, aplt)] write_lists wrote."""
+    rows = []
+    with open(file) as f:
+        for n, line in enumerate(f):
+            parts = line.rstrip("\n").split("\t")
+            if len(parts) != 11:
+                raise ValueError(f"{file}: line {n} has {len(parts)} fields, expected 11")
             rows.append((parts[0], float(parts[1]), int(parts[2]), *[float(x) for x in parts[3:]]))
     return rows
 
@@ -446,6 +475,14 @@ def main(argv=None, flavor="ori"):
             rows = robustness(final, dataset, init_eval_model(dataset, args), trip, args.robust_eps, modes=modes,
                               seed=args.seed, iters=args.robust_iters or 10, step=args.robust_step)
             write_robust(out, runName + ".robust", rows)
+            if args.robust_lists:
+                from .evaluate import list_robustness
+                rows = list_robustness(final, dataset, trip, args.robust_eps, k=max(args.robust_lists),
+                                       cutoffs=args.robust_lists, modes=modes, seed=args.seed,
+                                       iters=args.robust_iters or 10, step=args.robust_step)
+                write_lists(out, runName + ".lists", rows)
+    elif args.robust_lists:
+        print("--robust_lists: needs --robust_eps, nothing to evaluate", file=sys.stderr)
     if args.certify_eps:
         from .evaluate import certified, init_eval_model
         final = amf if args.model == "apr" else m

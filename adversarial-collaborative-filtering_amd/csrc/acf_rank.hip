@@ -23,6 +23,7 @@
 #include "acf_neighbors.h"  // nearest-neighbour lists (k_nbr_*): DESIGN.md §4h
 #include "acf_adv.h"   // whole-stream adversarial direction (k_adv_*): DESIGN.md §4c
 #include "acf_eval_multi.h"  // multi-item evaluation and rank metrics (k_evx_*): DESIGN.md §4f
+#include "acf_lists.h"  // list-level robustness: list overlap and item exposure (k_lst_*): DESIGN.md §4l
 #include "acf_eval_worst.h"  // the certified margin sweep (k_cert_sweep), worst-case positions: DESIGN.md §4g
 #include "acf_eval_radius.h"  // certified radius, the K weakest candidates (its selecting sink): DESIGN.md §4j
 
@@ -354,6 +355,101 @@ extern "C" int acf_eval_rank_metrics(const int32_t* positions, const int64_t* te
   const int ncol = n_cutoffs * EVX_NM;
   k_evx_means<<<(unsigned)(ncol + 2), 256, 0, s>>>(per_user, per_user_free, test_off, n_users, ncol, mean_cut,
                                                    mean_free, n_scored);
+  HIP_TRY(hipGetLastError());
+  return ACF_OK;
+}
+
+// ---- list-level robustness: list overlap, item exposure (acf_lists.h) ------------
+static int lst_cuts(int32_t k, const int32_t* cutoffs, int32_t n_cutoffs, LstCuts* cuts) {
+  ACF_CHECK(k >= 1 && k <= LST_MAX_K, ACF_E_INVALID, "k must be in [1, %d], got %d", LST_MAX_K, k);
+  ACF_CHECK(n_cutoffs >= 1 && n_cutoffs <= LST_MAX_CUT, ACF_E_INVALID, "n_cutoffs %d outside [1, %d]", n_cutoffs,
+            LST_MAX_CUT);
+  ACF_CHECK(cutoffs, ACF_E_INVALID, "NULL argument");
+  *cuts = LstCuts{};
+  cuts->n = n_cutoffs;
+  for (int c = 0; c < n_cutoffs; ++c) {
+    ACF_CHECK(cutoffs[c] >= 1 && cutoffs[c] <= k, ACF_E_INVALID, "cutoff %d outside [1, k = %d]", cutoffs[c], k);
+    cuts->k[c] = cutoffs[c];
+  }
+  return ACF_OK;
+}
+
+extern "C" int acf_list_compare(const int32_t* A, const int32_t* B, int32_t n, int32_t k, const int32_t* cutoffs,
+                                int32_t n_cutoffs, double p, double* per_user, double* mean, int64_t* n_scored,
+                                void* stream_) {
+  ACF_CHECK(n >= 0, ACF_E_INVALID, "negative count");
+  LstCuts cuts;
+  ACF_RET(lst_cuts(k, cutoffs, n_cutoffs, &cuts));
+  ACF_CHECK(p > 0.0 && p < 1.0, ACF_E_INVALID, "p must lie in (0, 1), got %g", p);
+  ACF_CHECK(mean && n_scored && (n == 0 || (A && B && per_user)), ACF_E_INVALID, "NULL argument");
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  uint8_t* scored = nullptr;  // which rows count: the means' only scratch
+  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&scored), (size_t)std::max(n, 1), s));
+  if (n > 0) k_lst_compare<<<grid_for(n, LST_WAVES), 64 * LST_WAVES, 0, s>>>(A, B, n, k, cuts, p, per_user, scored);
+  k_lst_means<<<(unsigned)(n_cutoffs * LST_NM), 256, 0, s>>>(per_user, scored, n, n_cutoffs * LST_NM, mean, n_scored);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipFreeAsync(scored, s));
+  return ACF_OK;
+}
+
+extern "C" int acf_list_exposure(const int32_t* lists, int32_t n, int32_t k, int32_t num_items,
+                                 const int32_t* cutoffs, int32_t n_cutoffs, int32_t* counts, void* stream_) {
+  ACF_CHECK(n >= 0, ACF_E_INVALID, "negative count");
+  ACF_CHECK(num_items >= 1, ACF_E_INVALID, "num_items must be >= 1, got %d", num_items);
+  LstCuts cuts;
+  ACF_RET(lst_cuts(k, cutoffs, n_cutoffs, &cuts));
+  ACF_CHECK((int64_t)n * k < ((int64_t)1 << 31), ACF_E_INVALID, "n * k must stay below 2^31");
+  ACF_CHECK(counts && (n == 0 || lists), ACF_E_INVALID, "NULL argument");
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_cutoffs * num_items * sizeof(int32_t), s));
+  if (n == 0) return ACF_OK;
+  k_lst_exposure<<<grid_for(n, LSX_ROWS), 256, 0, s>>>(lists, n, k, num_items, cuts, counts);
+  HIP_TRY(hipGetLastError());
+  return ACF_OK;
+}
+
+static int lsm_check(int32_t num_items, int32_t n_cutoffs) {
+  ACF_CHECK(num_items >= 1, ACF_E_INVALID, "num_items must be >= 1, got %d", num_items);
+  ACF_CHECK(n_cutoffs >= 1 && n_cutoffs <= LST_MAX_CUT, ACF_E_INVALID, "n_cutoffs %d outside [1, %d]", n_cutoffs,
+            LST_MAX_CUT);
+  return ACF_OK;
+}
+
+extern "C" int acf_exposure_metrics_workspace(int32_t num_items, int32_t n_cutoffs, size_t* bytes) {
+  ACF_CHECK(bytes, ACF_E_INVALID, "NULL argument");
+  ACF_RET(lsm_check(num_items, n_cutoffs));
+  *bytes = lsm_layout(num_items, n_cutoffs).total;
+  return ACF_OK;
+}
+
+extern "C" int acf_exposure_metrics(const int32_t* counts, int32_t num_items, int32_t n_cutoffs, const int32_t* pop,
+                                    const uint8_t* tail, double* out, void* workspace, size_t workspace_bytes,
+                                    void* stream_) {
+  ACF_RET(lsm_check(num_items, n_cutoffs));
+  ACF_CHECK(counts && out && workspace, ACF_E_INVALID, "NULL argument");
+  const int64_t N = num_items;
+  const LsmLayout L = lsm_layout(N, n_cutoffs);
+  ACF_RET(check_workspace(workspace, workspace_bytes, L.total, 8));
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  char* ws = static_cast<char*>(workspace);
+  uint32_t* sorted = reinterpret_cast<uint32_t*>(ws + L.sorted);
+  long long* part = reinterpret_cast<long long*>(ws + L.part);
+  double* epart = reinterpret_cast<double*>(ws + L.epart);
+  // counts are >= 0, so they sort as unsigned.  rocPRIM sizes its temporary storage by the device's
+  // architecture, which a host-only workspace query cannot ask for: it comes from the stream's allocator.
+  const uint32_t* keys = reinterpret_cast<const uint32_t*>(counts);
+  size_t tb = 0;
+  HIP_TRY(rocprim::radix_sort_keys(nullptr, tb, keys, sorted, (size_t)N, 0, 32, s));
+  void* tmp = nullptr;
+  HIP_TRY(hipMallocAsync(&tmp, std::max<size_t>(tb, 1), s));
+  for (int c = 0; c < n_cutoffs; ++c)
+    HIP_TRY(rocprim::radix_sort_keys(tmp, tb, keys + c * N, sorted + c * N, (size_t)N, 0, 32, s));
+  HIP_TRY(hipFreeAsync(tmp, s));
+  const int B = lsm_blocks(N);
+  const dim3 grid((unsigned)B, (unsigned)n_cutoffs);
+  k_lst_expo_ints<<<grid, 256, 0, s>>>(counts, sorted, N, pop, tail, part);
+  k_lst_expo_entropy<<<grid, 256, 0, s>>>(counts, N, part, epart);
+  k_lst_expo_final<<<(unsigned)n_cutoffs, 256, 0, s>>>(part, epart, B, N, out);
   HIP_TRY(hipGetLastError());
   return ACF_OK;
 }

@@ -213,6 +213,16 @@ def robustness(model, dataset, plan: EvalPlan, triplets, eps_list, modes=("grad"
     (P + delta_P, Q + delta_Q); it needs at least one triplet.  eps = 0 reproduces
     evaluate(output_adv=0).  The model's tables and delta_P / delta_Q are left
     as they are."""
+    return [_metrics_row(mode, eps, positions(Pa, Qa, plan).cpu().numpy(), plan)
+            for mode, eps, Pa, Qa in attacked_tables(model, triplets, eps_list, modes, seed, iters, step, side)]
+
+
+def attacked_tables(model, triplets, eps_list, modes=("grad", "random"), seed=0, iters=10, step=None, side="both"):
+    """The attack loop robustness and list_robustness share: a generator of
+    (mode, eps, P', Q') for every mode, then every eps, in that order; modes,
+    directions and the "pgd" arguments as robustness describes them.  The
+    arguments are checked when the generator is made, before anything runs; the
+    model's tables are read, never written."""
     for mode in modes:
         if mode not in ops.ADV_MODES and mode != "pgd":
             raise ValueError(f"mode must be one of {sorted(ops.ADV_MODES) + ['pgd']}, got {mode!r}")
@@ -231,23 +241,127 @@ def robustness(model, dataset, plan: EvalPlan, triplets, eps_list, modes=("grad"
             raise ValueError("the 'pgd' mode must be given at least one triplet: without a stream there is no "
                              "gradient to iterate on")
     P, Q = model.embedding_P, model.embedding_Q
-    rows = []
-    adv_plan = None
-    for mode in modes:
-        if mode == "pgd":
-            if adv_plan is None:
-                adv_plan = ops.adv_plan(u, i, j, P.shape[0], Q.shape[0], device=P.device)
+
+    def tables():
+        adv_plan = None
+        for mode in modes:
+            if mode == "pgd":
+                if adv_plan is None:
+                    adv_plan = ops.adv_plan(u, i, j, P.shape[0], Q.shape[0], device=P.device)
+                for eps in eps_list:
+                    Pa, Qa = P, Q
+                    if eps > 0:
+                        dP, dQ, _ = ops.adv_pgd(P, Q, u, i, j, eps, iters=iters, alpha=step, side=side,
+                                                plan=adv_plan)
+                        Pa, Qa = ops.adv_apply(P, dP, 1.0), ops.adv_apply(Q, dQ, 1.0)
+                    yield mode, eps, Pa, Qa
+                continue
+            nP, nQ = ops.adv_direction(P, Q, u, i, j, adv=mode, seed=int(seed or 0), call=1, t=0)
             for eps in eps_list:
-                Pa, Qa = P, Q
-                if eps > 0:
-                    dP, dQ, _ = ops.adv_pgd(P, Q, u, i, j, eps, iters=iters, alpha=step, side=side, plan=adv_plan)
-                    Pa, Qa = ops.adv_apply(P, dP, 1.0), ops.adv_apply(Q, dQ, 1.0)
-                rows.append(_metrics_row(mode, eps, positions(Pa, Qa, plan).cpu().numpy(), plan))
-            continue
-        nP, nQ = ops.adv_direction(P, Q, u, i, j, adv=mode, seed=int(seed or 0), call=1, t=0)
-        for eps in eps_list:
-            pos = positions(ops.adv_apply(P, nP, eps), ops.adv_apply(Q, nQ, eps), plan).cpu().numpy()
-            rows.append(_metrics_row(mode, eps, pos, plan))
+                yield mode, eps, ops.adv_apply(P, nP, eps), ops.adv_apply(Q, nQ, eps)
+    return tables()
+
+
+def item_popularity(dataset, head_share=0.2):
+    """(pop int32 [num_items], tail bool [num_items]) from the train lists: pop[i]
+    is the number of train interactions of item i; the head is the
+    ceil(head_share * num_items) most popular items, ties going to the lower id,
+    and tail marks the rest.  Pure numpy."""
+    if not 0.0 <= float(head_share) <= 1.0:
+        raise ValueError(f"head_share must lie in [0, 1], got {head_share!r}")
+    n = int(dataset.num_items)
+    _, items = dataset.sorted_lists()
+    items = np.asarray(items, dtype=np.int64).reshape(-1)
+    items = items[(items >= 0) & (items < n)]
+    pop = np.bincount(items, minlength=n).astype(np.int32)
+    head = int(math.ceil(float(head_share) * n))
+    order = np.lexsort((np.arange(n), -pop.astype(np.int64)))  # popularity descending, then id ascending
+    tail = np.ones(n, dtype=bool)
+    tail[order[:head]] = False
+    return pop, tail
+
+
+def _tables_of(model_or_tables):
+    if hasattr(model_or_tables, "embedding_P"):
+        return model_or_tables.embedding_P, model_or_tables.embedding_Q
+    return model_or_tables[0], model_or_tables[1]
+
+
+def _list_cutoffs(cutoffs, k):
+    cutoffs = [int(c) for c in cutoffs]
+    if any(c > int(k) for c in cutoffs):
+        raise ValueError(f"every cutoff must be <= k = {k}, got {cutoffs}")
+    return cutoffs
+
+
+class _ListSweep:
+    """recommend_topk for a fixed set of users and exclusions, and the exposure
+    metrics of such lists against a dataset's popularity, all on the device."""
+
+    def __init__(self, P, dataset, users, k, cutoffs, exclude_train):
+        import torch
+        dev = P.device
+        if users is None:
+            users = np.arange(dataset.num_users, dtype=np.int64)
+        users = np.asarray(users, dtype=np.int64).reshape(-1)
+        self.k, self.cutoffs, self.num_items = int(k), cutoffs, int(dataset.num_items)
+        self.users = torch.as_tensor(users.astype(np.int32), device=dev)
+        self.off = self.ex = None
+        if exclude_train:
+            off, ex = train_exclusions(dataset, users)
+            self.off = torch.as_tensor(off, device=dev)
+            self.ex = torch.as_tensor(ex if len(ex) else np.zeros(1, np.int32), device=dev)
+        pop, tail = item_popularity(dataset)
+        self.pop = torch.as_tensor(pop, device=dev)
+        self.tail = torch.as_tensor(tail.astype(np.uint8), device=dev)
+
+    def lists(self, P, Q):
+        return ops.recommend_topk(P, Q, self.users, self.k, min(self.num_items, Q.shape[0]), self.off, self.ex)[0]
+
+    def exposure(self, lists):
+        """rows [n_cut][6] in ops.EXPOSURE_METRICS order, as Python floats"""
+        counts = ops.list_exposure(lists, self.num_items, self.cutoffs)
+        return ops.exposure_metrics(counts, self.pop, self.tail).cpu().tolist()
+
+
+def exposure(model_or_tables, dataset, users=None, k=100, cutoffs=(10, 100), exclude_train=True):
+    """What the model's own top-k lists do to the items: rows (cutoff, total,
+    coverage, gini, entropy, arp, aplt), one per cutoff (ops.EXPOSURE_METRICS;
+    arp and aplt against item_popularity(dataset)).  The lists stay on the device
+    between ops.recommend_topk and the metrics.  users: default every user of
+    the dataset; cutoffs above k are an error."""
+    cutoffs = _list_cutoffs(cutoffs, k)
+    P, Q = _tables_of(model_or_tables)
+    sweep = _ListSweep(P, dataset, users, k, cutoffs, exclude_train)
+    return [(c, *row) for c, row in zip(cutoffs, sweep.exposure(sweep.lists(P, Q)))]
+
+
+def list_robustness(model, dataset, triplets, eps_list, k=100, cutoffs=(1, 10, 100), modes=("grad", "random"),
+                    p=0.9, seed=0, iters=10, step=None, side="both", users=None):
+    """How far an attack moves the top-k lists: rows (mode, eps, cutoff, jaccard,
+    rbo, overlap, coverage, gini, entropy, arp, aplt).  One clean
+    ops.recommend_topk (train items excluded) gives the rows ("clean", 0.0,
+    cutoff, 1.0, 1.0, overlap, exposure...) first, overlap being the mean list
+    length up to the cutoff; then, for every (mode, eps) of robustness' own attack
+    loop (attacked_tables), one recommend_topk on the perturbed tables, one
+    ops.list_compare against the clean lists (jaccard, rbo with persistence p and
+    overlap are means over the users) and one ops.list_exposure +
+    ops.exposure_metrics.  Cutoffs above k are an error.  The model's tables and
+    delta_P / delta_Q are left as they are."""
+    cutoffs = _list_cutoffs(cutoffs, k)
+    attacks = attacked_tables(model, triplets, eps_list, modes, seed, iters, step, side)
+    P, Q = model.embedding_P, model.embedding_Q
+    sweep = _ListSweep(P, dataset, users, k, cutoffs, True)
+    clean = sweep.lists(P, Q)
+
+    def rows_of(mode, eps, lists):
+        cmp = ops.list_compare(clean, lists, cutoffs, p).mean.cpu().tolist()  # [n_cut][overlap, jaccard, rbo]
+        return [(mode, eps, c, m[1], m[2], m[0], *e[1:]) for c, m, e in zip(cutoffs, cmp, sweep.exposure(lists))]
+
+    # a list against itself: jaccard and rbo are 1 by definition (the fp64 rbo sum is 1 to a few ulps)
+    rows = [(*r[:3], 1.0, 1.0, *r[5:]) for r in rows_of("clean", 0.0, clean)]
+    for mode, eps, Pa, Qa in attacks:
+        rows += rows_of(mode, eps, sweep.lists(Pa, Qa))
     return rows
 
 

@@ -262,6 +262,21 @@ class MF:
         return robustness(self, dataset, plan, triplets, eps_list, modes=modes, seed=seed, iters=iters, step=step,
                           side=side)
 
+    def exposure(self, dataset, users=None, k=100, cutoffs=(10, 100), exclude_train=True):
+        """evaluate.exposure: rows (cutoff, total, coverage, gini, entropy, arp,
+        aplt) of this model's own top-k lists."""
+        from .evaluate import exposure
+        return exposure(self, dataset, users=users, k=k, cutoffs=cutoffs, exclude_train=exclude_train)
+
+    def list_robustness(self, dataset, triplets, eps_list, k=100, cutoffs=(1, 10, 100), modes=("grad", "random"),
+                        p=0.9, seed=0, iters=10, step=None, side="both", users=None):
+        """evaluate.list_robustness: rows (mode, eps, cutoff, jaccard, rbo, overlap,
+        coverage, gini, entropy, arp, aplt), how far each attack of robustness moves
+        the top-k lists and what the attacked lists do to the items."""
+        from .evaluate import list_robustness
+        return list_robustness(self, dataset, triplets, eps_list, k=k, cutoffs=cutoffs, modes=modes, p=p, seed=seed,
+                               iters=iters, step=step, side=side, users=users)
+
     def certified(self, plan, eps_list, side="user", cutoffs=None):
         """evaluate.certified: rows (side, eps, K, hr_lb, ndcg_lb, auc_lb), lower
         bounds under EVERY perturbation of that side within eps per row."""

@@ -1069,6 +1069,156 @@ def rank_metrics(positions, test_off, n_neg, cutoffs) -> RankMetrics:
     return out
 
 
+# ---- list-level robustness: list overlap and item exposure ----
+LIST_METRICS = ("overlap", "jaccard", "rbo")                                   # LST_NM
+EXPOSURE_METRICS = ("total", "coverage", "gini", "entropy", "arp", "aplt")     # LSM_NM
+
+
+@dataclass
+class ListCompare:
+    """What list_compare returns (device tensors): per_user fp64 [n, n_cut, 3] in
+    LIST_METRICS order, mean fp64 [n_cut, 3] over the scored rows (those where a
+    list holds at least one id) and n_scored int64 [n_cut], their number."""
+    cutoffs: tuple
+    per_user: torch.Tensor
+    mean: torch.Tensor
+    n_scored: torch.Tensor
+
+
+def _id_lists(t, name: str) -> None:
+    """TypeError / ValueError unless t is a contiguous 2-D int32 tensor [n, k],
+    1 <= k <= TOPK_MAX_K; the device is the caller's to check, after its host
+    arguments."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+        raise TypeError(f"{name} must be a torch.int32 tensor")
+    if t.dim() != 2:
+        raise ValueError(f"{name} must be 2-D [n, k], got shape {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if not 1 <= t.shape[1] <= TOPK_MAX_K:
+        raise ValueError(f"{name}: k must lie in [1, {TOPK_MAX_K}], got {t.shape[1]}")
+
+
+def _list_cutoffs(cutoffs, k: int):
+    """The cutoffs of a [n, k] list array as a tuple and a C array: 1 to 8 ints in [1, k]."""
+    ks = _cutoffs(cutoffs)
+    if not ks:
+        raise ValueError("cutoffs must hold at least one value")
+    for c in ks:
+        if c > k:
+            raise ValueError(f"a cutoff must lie in [1, k = {k}], got {c}")
+    return ks, (ctypes.c_int32 * len(ks))(*ks)
+
+
+def _hip(t, name: str, dev=None):
+    if t.device.type != "cuda":
+        raise ValueError(f"{name} must live on a HIP device (got {t.device}); there is no CPU path")
+    if dev is not None and t.device != dev:
+        raise ValueError(f"{name} is on {t.device}, expected {dev}")
+    return t.device
+
+
+def list_compare(A, B, cutoffs, p: float = 0.9) -> ListCompare:
+    """How far the lists B differ from the lists A, row by row (acf_list_compare;
+    definitions in include/acf_apr.h, tests/lists_ref.py is the numpy yardstick).
+    A, B: device int32 [n, k] as recommend_topk writes them (-1: none), k <= 128;
+    cutoffs: 1 to 8 ints in [1, k]; p: the rank-biased overlap's persistence in
+    (0, 1).  Per row and cutoff: overlap (an integer), jaccard, extrapolated rbo.
+    Exact integers and fp64 in a fixed order: equal inputs give equal bits."""
+    _id_lists(A, "A")
+    _id_lists(B, "B")
+    if A.shape != B.shape:
+        raise ValueError(f"A and B must have one shape, got {tuple(A.shape)} and {tuple(B.shape)}")
+    n, k = A.shape
+    ks, cuts = _list_cutoffs(cutoffs, k)
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 < float(p) < 1.0:
+        raise ValueError(f"p must lie in (0, 1), got {p!r}")
+    dev = _hip(A, "A")
+    _hip(B, "B", dev)
+    nc = len(ks)
+    out = ListCompare(ks, torch.zeros((n, nc, 3), dtype=torch.float64, device=dev),
+                      torch.zeros((nc, 3), dtype=torch.float64, device=dev),
+                      torch.zeros(nc, dtype=torch.int64, device=dev))
+    if n == 0:
+        return out
+    with _on(dev):
+        call("acf_list_compare", A.data_ptr(), B.data_ptr(), n, k, cuts, nc, float(p), out.per_user.data_ptr(),
+             out.mean.data_ptr(), out.n_scored.data_ptr(), _stream_ptr(dev))
+    return out
+
+
+def _check_num_items(num_items) -> None:
+    if isinstance(num_items, bool) or not isinstance(num_items, int) or not 1 <= num_items < 1 << 31:
+        raise ValueError(f"num_items must be an int in [1, 2^31), got {num_items!r}")
+
+
+def list_exposure(lists, num_items: int, cutoffs) -> torch.Tensor:
+    """How often the lists recommend each item: counts int32 [n_cut, num_items],
+    counts[c, i] = the number of rows that hold item i among their first
+    cutoffs[c] entries (acf_list_exposure).  lists: device int32 [n, k]; entries
+    outside [0, num_items) are ignored.  Integer atomics only: exact."""
+    _id_lists(lists, "lists")
+    n, k = lists.shape
+    ks, cuts = _list_cutoffs(cutoffs, k)
+    _check_num_items(num_items)
+    if n * k >= 1 << 31:
+        raise ValueError("n * k must stay below 2^31")
+    if num_items * n * k >= 1 << 63:
+        raise ValueError("num_items * n * k must stay below 2^63 (the Gini numerator is an int64)")
+    dev = _hip(lists, "lists")
+    counts = torch.zeros((len(ks), num_items), dtype=torch.int32, device=dev)
+    if n == 0:
+        return counts
+    with _on(dev):
+        call("acf_list_exposure", lists.data_ptr(), n, k, num_items, cuts, len(ks), counts.data_ptr(),
+             _stream_ptr(dev))
+    return counts
+
+
+def exposure_metrics_workspace(num_items: int, n_cutoffs: int) -> int:
+    """Bytes of device workspace acf_exposure_metrics needs (a host-only query)."""
+    _check_num_items(num_items)
+    if isinstance(n_cutoffs, bool) or not isinstance(n_cutoffs, int) or not 1 <= n_cutoffs <= RANK_MAX_CUTOFFS:
+        raise ValueError(f"n_cutoffs must be an int in [1, {RANK_MAX_CUTOFFS}], got {n_cutoffs!r}")
+    return _workspace_bytes("acf_exposure_metrics_workspace", num_items, n_cutoffs)
+
+
+def exposure_metrics(counts, pop=None, tail=None) -> torch.Tensor:
+    """Exposure metrics of list_exposure's counts: fp64 [n_cut, 6] in
+    EXPOSURE_METRICS order (acf_exposure_metrics: total, catalogue coverage, Gini
+    index, entropy in bits, average popularity of what is recommended, long-tail
+    share).  pop: device int32 [num_items], each item's training interactions;
+    tail: device uint8 (or bool) [num_items], nonzero for a long-tail item; None:
+    that column is 0.  All but the entropy are one fp64 division of exact
+    integers; the entropy is summed in a fixed order."""
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32:
+        raise TypeError("counts must be a torch.int32 tensor")
+    if counts.dim() != 2 or not counts.is_contiguous():
+        raise ValueError(f"counts must be a contiguous 2-D [n_cut, num_items] tensor, got shape {tuple(counts.shape)}")
+    nc, N = counts.shape
+    if not 1 <= nc <= RANK_MAX_CUTOFFS or N < 1:
+        raise ValueError(f"counts must be [1..{RANK_MAX_CUTOFFS}, >= 1], got shape {tuple(counts.shape)}")
+    for t, name, dtypes in ((pop, "pop", (torch.int32,)), (tail, "tail", (torch.uint8, torch.bool))):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes:
+            raise TypeError(f"{name} must be a torch.{str(dtypes[0]).split('.')[-1]} tensor")
+        if t.dim() != 1 or t.numel() != N or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous 1-D tensor of num_items = {N} entries, got shape "
+                             f"{tuple(t.shape)}")
+    dev = _hip(counts, "counts")
+    for t, name in ((pop, "pop"), (tail, "tail")):
+        if t is not None:
+            _hip(t, name, dev)
+    out = torch.empty((nc, 6), dtype=torch.float64, device=dev)
+    nbytes = exposure_metrics_workspace(N, nc)
+    work = _workspace(nbytes, 8, dev)
+    with _on(dev):
+        call("acf_exposure_metrics", counts.data_ptr(), N, nc, _ptr(pop), _ptr(tail), out.data_ptr(),
+             work.data_ptr(), nbytes, _stream_ptr(dev))
+    return out
+
+
 WORST_MAX_EPS = 8                       # EVW_MAX_EPS
 WORST_SIDES = {"user": 0, "item": 1}
 

@@ -303,6 +303,21 @@ class APR(Recommender):
         return self.model.robustness(dataset, plan, ([x_train[0]], [x_train[1]], [x_train[2]]), eps_list,
                                      modes=modes, seed=seed, iters=iters, step=step, side=side)
 
+    def exposure(self, dataset, users=None, k=100, cutoffs=(10, 100), exclude_train=True):
+        """evaluate.exposure: rows (cutoff, total, coverage, gini, entropy, arp,
+        aplt) of the model's own top-k lists."""
+        self._ensure()
+        return self.model.exposure(dataset, users=users, k=k, cutoffs=cutoffs, exclude_train=exclude_train)
+
+    def list_robustness(self, dataset, x_train, eps_list, k=100, cutoffs=(1, 10, 100), modes=("grad", "random"),
+                        p=0.9, seed=0, iters=10, step=None, side="both", users=None):
+        """evaluate.list_robustness on the triplets of get_train_instances: rows
+        (mode, eps, cutoff, jaccard, rbo, overlap, coverage, gini, entropy, arp, aplt)."""
+        self._ensure()
+        return self.model.list_robustness(dataset, ([x_train[0]], [x_train[1]], [x_train[2]]), eps_list, k=k,
+                                          cutoffs=cutoffs, modes=modes, p=p, seed=seed, iters=iters, step=step,
+                                          side=side, users=users)
+
     def certified(self, plan, eps_list, side="user", cutoffs=None):
         """evaluate.certified against an all-items plan: rows (side, eps, K, hr_lb,
         ndcg_lb, auc_lb), lower bounds under every attack of that budget."""

@@ -499,6 +499,70 @@ int acf_eval_rank_metrics(const int32_t* positions, const int64_t* test_off, int
                           double* per_user, double* per_user_free, double* mean_cut, double* mean_free,
                           int64_t* n_scored, void* stream);
 
+/* ---- list-level robustness: how far two sets of top-K lists differ, and what
+ * lists do to the items (no reference counterpart).
+ * A list array is device int32 [n][k], row-major, 1 <= k <= 128, in the form
+ * acf_recommend_topk writes: ids >= 0 first, then -1.  A negative entry is
+ * "none" wherever it stands and matches nothing.  A row that holds an id twice
+ * gives unspecified values for that row (every loop stays in bounds and ends).
+ * cutoffs: a HOST array of 1 <= n_cutoffs <= 8 values K with 1 <= K <= k.
+ * Everything is asynchronous on `stream`; NULL pointers, k outside [1, 128], a
+ * bad cutoff, p outside (0, 1) and a short or misaligned workspace are
+ * ACF_E_INVALID before any launch.
+ *
+ * acf_list_compare: per row r and cutoff K, with la, lb the numbers of valid ids
+ * in the whole rows A[r], B[r], D = min(K, max(la, lb)) and X_d (d = 1..D) the
+ * number of ids that occur in both A[r][0..d) and B[r][0..d), per_user
+ * [n][n_cutoffs][3] (device fp64) =
+ *   overlap  X_D (an exact integer)
+ *   jaccard  X_D / (min(la, D) + min(lb, D) - X_D)
+ *   rbo      (X_D / D) p^D + ((1 - p) / p) sum_{d=1..D} (X_d / d) p^d
+ * the last the extrapolated rank-biased overlap, 0 < p < 1, summed over d
+ * ascending in fp64 by one thread, p^d by repeated multiplication, every
+ * operation rounded on its own.  The X_d are integers (a histogram of the depth
+ * max(i, j) at which a shared id is in both prefixes, prefix-summed), so
+ * overlap and jaccard have exactly one right answer.  jaccard at K = 1 is "the
+ * top item is unchanged".  A row with D = 0 (both lists empty) writes zeros and
+ * is not scored.  mean [n_cutoffs][3]: the means over the scored rows, summed
+ * in a fixed order with no float atomics (zeros when no row is scored);
+ * n_scored: device int64 [n_cutoffs].  Equal inputs give equal bits.  n = 0
+ * writes the zero means only.
+ *
+ * acf_list_exposure: counts (device int32 [n_cutoffs][num_items]) is zeroed by
+ * the call, then counts[c][i] = #{(r, x) : x < K_c, lists[r][x] = i}; entries
+ * outside [0, num_items) are ignored.  n * k < 2^31.  Integer atomics only, equal
+ * ids combined inside a wave first: exact whatever the order.
+ *
+ * acf_exposure_metrics: with c_i = counts[c][i], N = num_items and T = sum c_i,
+ * out [n_cutoffs][6] (device fp64) =
+ *   total     T
+ *   coverage  #{c_i > 0} / N
+ *   gini      G / (N T), G = sum_{j=1..N} (2j - N - 1) c_(j) over the counts
+ *             sorted ascending
+ *   entropy   - sum_{c_i > 0} (c_i / T) log2(c_i / T)
+ *   arp       (sum c_i pop_i) / T     (pop NULL: 0)
+ *   aplt      (sum_{tail_i != 0} c_i) / T   (tail NULL: 0)
+ * pop: device int32 [num_items] or NULL, each item's number of training
+ * interactions; tail: device uint8 [num_items] or NULL, nonzero for a long-tail
+ * item.  T, the covered items, G and both numerators are exact int64 (the
+ * caller guarantees N T < 2^63), each converted to fp64 once, so coverage,
+ * gini, arp and aplt are one fp64 division of two integers; the entropy is
+ * summed in fp64 in an order fixed by N alone.  T = 0 gives a row of zeros.
+ * `workspace`: device memory, 8-byte aligned, at least
+ * acf_exposure_metrics_workspace(num_items, n_cutoffs) bytes (the sorted counts
+ * and the partial sums) -- a host-only query that touches no device;
+ * ACF_E_INVALID on a NULL out pointer, num_items < 1 or n_cutoffs outside
+ * [1, 8].  The radix sort's own temporary storage comes from the stream's
+ * allocator. */
+int acf_list_compare(const int32_t* A, const int32_t* B, int32_t n, int32_t k, const int32_t* cutoffs,
+                     int32_t n_cutoffs, double p, double* per_user, double* mean, int64_t* n_scored,
+                     void* stream);
+int acf_list_exposure(const int32_t* lists, int32_t n, int32_t k, int32_t num_items, const int32_t* cutoffs,
+                      int32_t n_cutoffs, int32_t* counts, void* stream);
+int acf_exposure_metrics_workspace(int32_t num_items, int32_t n_cutoffs, size_t* bytes);
+int acf_exposure_metrics(const int32_t* counts, int32_t num_items, int32_t n_cutoffs, const int32_t* pop,
+                         const uint8_t* tail, double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- certified ranking robustness: worst-case positions under an eps attack --
  * (no reference counterpart.)  Entry r (row users[r] of P; any order, repeats
  * allowed) has the test item t = test_items[r] and the candidates C_r =
