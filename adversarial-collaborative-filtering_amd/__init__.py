@@ -18,13 +18,13 @@ from .data import (DeviceDataset, OriginalDataset, SyntheticDataset, get_dataset
                    synthetic_dataset, synthetic_large, yelp_like)
 from .evaluate import certified, certified_radius, evaluate, init_eval_model, robustness
 from .evaluation import evaluate_apr_mode, evaluate_model
-from .model import MF, Session
+from .model import MF, MFGrid, Session
 from .neumf import AdversarialNeuMF, NeuMF
 from .fast_adversarial_mf import FastAdversarialMF
 from .recommender import APR, Recommender
 from .sampler import DeviceSampler, EpochTriplets, sampling, shuffle
-from .train import (adv_update, output_evaluate, prediction2file, training, training_batch, training_loss_acc,
-                    write2file)
+from .train import (adv_update, output_evaluate, prediction2file, training, training_batch, training_grid,
+                    training_loss_acc, write2file)
 
 _sys.modules.setdefault("acf_amd", _sys.modules[__name__])
 
@@ -33,5 +33,5 @@ __all__ = [
     "SyntheticDataset", "evaluate", "evaluate_apr_mode", "evaluate_model", "get_dataset", "init_eval_model", "ml1m_like", "output_evaluate",
     "pinterest_like", "prediction2file", "sampling", "shuffle", "synthetic_dataset", "synthetic_large", "training",
     "training_batch", "training_loss_acc", "write2file", "yelp_like", "adv_update", "robustness", "certified",
-    "certified_radius",
+    "certified_radius", "MFGrid", "training_grid",
 ]

@@ -30,7 +30,7 @@ PKG = os.path.basename(PKG_DIR)
 LIBS = {
     "apr": {"lib": f"{PKG}/lib/libacf_apr.so",
             "srcs": [f"{PKG}/csrc/acf_apr.hip", f"{PKG}/csrc/acf_plan.hip", f"{PKG}/csrc/acf_rank.hip",
-                     f"{PKG}/csrc/acf_ops.hip"],
+                     f"{PKG}/csrc/acf_ops.hip", f"{PKG}/csrc/acf_grid.hip"],
             "headers": ["include/acf_apr.h", f"{PKG}/csrc/acf_host.h", f"{PKG}/csrc/acf_rows.h",
                         f"{PKG}/csrc/acf_plan.h", f"{PKG}/csrc/acf_hplan.h",
                         f"{PKG}/csrc/acf_eval.h", f"{PKG}/csrc/acf_topk.h", f"{PKG}/csrc/acf_adv.h",

@@ -114,7 +114,26 @@ def parse_args(argv=None, flavor="ori"):
                         "is never its own neighbour.  Needs --topk.")
     p.add_argument("--similar_metric", choices=["dot", "cosine", "euclid"], default="cosine",
                    help="The similarity of --similar: cosine, the dot product, or euclid (nearest by L2 distance).")
+    p.add_argument("--grid_eps", type=parse_eps_list, default=[],
+                   help="With --model apr: train the APR phase as a grid, one member per value of eps (comma "
+                        "separated, e.g. \"0.1,0.5,1\"), all members over one triplet stream in one call per epoch. "
+                        "The BPR phase runs once; every member branches from it.  The grid is the product of the "
+                        "--grid_* lists; each member logs under the run name a single run at its (eps, reg_adv) "
+                        "gets, and <out>/<runName>.grid lists the members (empty: off).")
+    p.add_argument("--grid_reg_adv", type=parse_eps_list, default=[],
+                   help="Grid axis: values of reg_adv (comma separated).")
+    p.add_argument("--grid_lr", type=parse_grid_lr, default=[], help="Grid axis: values of lr (comma separated).")
+    p.add_argument("--grid_seeds", type=parse_grid_seeds, default=0,
+                   help="Grid axis: N members per point, seeds 0..N-1 (they differ where the APR phase starts from "
+                        "scratch, --adv_epoch 0; 0: off).")
     args = p.parse_args(argv)
+    if grid_of(args) is not None:
+        extras = [f for f in ("topk", "fold_in", "fold_in_items", "test_multi", "similar", "robust_eps",
+                              "robust_lists", "certify_eps", "certify_radius") if getattr(args, f)]
+        if extras:
+            p.error("--grid_* trains several models; --%s works on one (run it on a member's checkpoint)" % extras[0])
+        if len(grid_of(args)) > 64:
+            p.error("a grid has at most 64 members, the product of the --grid_* lists has %d" % len(grid_of(args)))
     if args.fold_in is not None and args.topk <= 0:
         p.error("--fold_in needs --topk K (K > 0)")
     if args.fold_in_items is not None and args.topk <= 0:
@@ -139,6 +158,42 @@ def parse_eps_list(text):
             raise argparse.ArgumentTypeError(f"eps must be finite and >= 0, got {tok!r}")
         out.append(v)
     return out
+
+
+def parse_grid_lr(text):
+    """--grid_lr: "0.01,0.05" -> [0.01, 0.05]; every value finite and > 0."""
+    out = parse_eps_list(text)
+    for v in out:
+        if not v > 0:
+            raise argparse.ArgumentTypeError(f"a learning rate must be > 0, got {v!r}")
+    return out
+
+
+def parse_grid_seeds(text):
+    """--grid_seeds: an integer in [0, 64] (0: off)."""
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not an integer: {text!r}")
+    if not 0 <= v <= 64:
+        raise argparse.ArgumentTypeError(f"grid_seeds must lie in [0, 64], got {text!r}")
+    return v
+
+
+def grid_of(args):
+    """The grid dicts of the --grid_* flags (model.MFGrid.product order: eps slowest,
+    then reg_adv, lr, the seed fastest), or None when no --grid_* flag is given."""
+    axes = dict(eps=args.grid_eps or None, reg_adv=args.grid_reg_adv or None, lr=args.grid_lr or None,
+                seeds=args.grid_seeds or None)
+    if all(v is None for v in axes.values()):
+        return None
+    from .model import MFGrid
+    return MFGrid.product(**axes)
+
+
+def apr_run_name(dataset, model, embed_size, eps, reg_adv, time_stamp):
+    """The run name of an apr run (run_adv_ori.py:91)."""
+    return "%s_%s_d%d_e%f_l%f_%s" % (dataset, model, embed_size, eps, reg_adv, time_stamp)
 
 
 def parse_robust_iters(text):
@@ -426,6 +481,18 @@ def main(argv=None, flavor="ori"):
         training(m, dataset, args, runName, epoch_start=0, epoch_end=args.adv_epoch - 1,
                  time_stamp=time_stamp)
         args.adver = 1
+        grid = grid_of(args)
+        if grid is not None:  # the APR phase as a grid: every member branches from the one BPR model
+            from .model import MFGrid
+            from .train import training_grid
+            if args.adv_epoch > 0:
+                gm = MFGrid.from_model(m, grid, args)
+            else:  # no BPR phase: every member starts from its own seed's init
+                gm = MFGrid(dataset.num_users, dataset.num_items, args, grid, device=m.device)
+            write2file(out, runName + ".out", "Initialize APR grid of %d" % len(gm))
+            training_grid(gm, dataset, args, runName, epoch_start=args.adv_epoch, epoch_end=args.epochs,
+                          time_stamp=time_stamp)
+            return 0
         amf = MF(dataset.num_users, dataset.num_items, args).build_graph(device=m.device)
         write2file(out, runName + ".out", "Initialize APR")
         training(amf, dataset, args, runName, epoch_start=args.adv_epoch, epoch_end=args.epochs,

@@ -243,6 +243,12 @@ class MF:
         from .evaluate import similar_users
         return similar_users(self, users, k=k, metric=metric, rows=rows)
 
+    def evaluate(self, dataset, plan, output_adv=0, args=None):
+        """evaluate.evaluate: ((hr, ndcg, auc) per K, raw [users, 3, K]) of the
+        leave-one-out protocol (plan: evaluate.init_eval_model)."""
+        from .evaluate import evaluate
+        return evaluate(self, None, dataset, plan, output_adv, args)
+
     def evaluate_multi(self, plan, cutoffs=(10, 50, 100), raw=False):
         """evaluate.evaluate_multi: recall / ndcg / map / ... @K, mrr and auc against
         several held-out items per user (plan: evaluate.init_eval_multi)."""
@@ -289,6 +295,152 @@ class MF:
         and the items that break the certificate first."""
         from .evaluate import certified_radius
         return certified_radius(self, plan, k=k, side=side)
+
+
+class MFGrid:
+    """M MF models over one triplet stream: the sweep the reference runs as one
+    job per (eps, reg_adv) point, trained by ops.grid_train in one call per epoch.
+
+    grid: a list of dicts over GRID_KEYS (eps, reg_adv, lr, reg, adver, seed);
+    a key a dict leaves out takes the value of `args`.  The tables are
+    [M, rows, d], member-major: slice m is an ordinary dense table, and
+    member(m) is an MF whose tables are views of it, so evaluation, top-K,
+    robustness, certificates, neighbours and checkpoints work on a member as on
+    any MF.  Members are initialised as MF._create_variables does with that
+    member's seed (equal seeds: equal tables)."""
+
+    GRID_KEYS = ("eps", "reg_adv", "lr", "reg", "adver", "seed")
+
+    def __init__(self, num_users, num_items, args, grid, device=None, _init=True):
+        import copy
+        grid = [dict(g) for g in grid]
+        if not 1 <= len(grid) <= ops.GRID_MAX_MODELS:
+            raise ValueError(f"a grid has 1 to {ops.GRID_MAX_MODELS} members, got {len(grid)}")
+        for g in grid:
+            bad = set(g) - set(self.GRID_KEYS)
+            if bad:
+                raise ValueError(f"unknown grid keys {sorted(bad)}: a member varies {self.GRID_KEYS}")
+        d = args.embed_size
+        if d % 4 or not 4 <= d <= ops.GRID_MAX_DIM:
+            raise ValueError(f"grid dim must be a multiple of 4 in [4, {ops.GRID_MAX_DIM}], got {d}")
+        if getattr(args, "adv", "grad") != "grad" or getattr(args, "dns", 1) != 1:
+            raise ValueError("a grid trains adv='grad' with dns=1 only")
+        self.num_users, self.num_items, self.args = num_users, num_items, args
+        self.grid = grid
+        self.member_args = []
+        for g in grid:
+            a = copy.copy(args)
+            if not hasattr(a, "adver"):
+                a.adver = 1
+            for k, v in g.items():
+                setattr(a, k, v)
+            self.member_args.append(a)
+        self.embedding_size = d
+        self.num_user_rows, self.num_item_rows = num_users + 1, num_items + 1
+        self._members = [None] * len(grid)
+        self.built = False
+        if _init:
+            self.build_graph(device)
+
+    def __len__(self):
+        return len(self.grid)
+
+    @staticmethod
+    def product(eps=None, reg_adv=None, lr=None, seeds=None):
+        """The product of the given lists as grid dicts, in itertools.product order
+        over (eps, reg_adv, lr, seed): eps varies slowest, the seed fastest.  A list
+        left out (None) is not a key of the dicts.  seeds: a list of seeds, or an
+        int N for seeds 0..N-1."""
+        import itertools
+        if isinstance(seeds, int):
+            seeds = list(range(seeds))
+        axes = [(k, list(v)) for k, v in (("eps", eps), ("reg_adv", reg_adv), ("lr", lr), ("seed", seeds))
+                if v is not None]
+        if any(not v for _, v in axes):
+            raise ValueError("a grid axis is empty")
+        return [dict(zip([k for k, _ in axes], vals)) for vals in itertools.product(*[v for _, v in axes])]
+
+    def _allocate(self, device):
+        self.device = torch.device(device) if device is not None else default_device()
+        M, d = len(self.grid), self.embedding_size
+        self.embedding_P = torch.empty(M, self.num_user_rows, d, dtype=torch.float32, device=self.device)
+        self.embedding_Q = torch.empty(M, self.num_item_rows, d, dtype=torch.float32, device=self.device)
+        self.accumulator_P = torch.full_like(self.embedding_P, 0.1)
+        self.accumulator_Q = torch.full_like(self.embedding_Q, 0.1)
+        self.built = True
+
+    def build_graph(self, device=None):
+        self._allocate(device)
+        drawn = {}
+        for m, a in enumerate(self.member_args):
+            seed = getattr(a, "seed", None)
+            if seed is None or seed not in drawn:
+                tmp = MF(self.num_users, self.num_items, a)
+                tmp._create_variables(self.device)
+                src = (tmp.embedding_P, tmp.embedding_Q)
+                if seed is not None:
+                    drawn[seed] = src
+            else:
+                src = drawn[seed]
+            self.embedding_P[m].copy_(src[0])
+            self.embedding_Q[m].copy_(src[1])
+        return self
+
+    @classmethod
+    def from_model(cls, mf, grid, args=None):
+        """Every member starts from one trained model's P and Q, with fresh Adagrad
+        slots at 0.1: the reference's BPR -> APR switch, pre-train once, branch M ways.
+        args: what a grid dict leaves out (default: the model's own values, with
+        adver = 1)."""
+        import copy
+        if mf.twin:
+            raise ValueError("a grid branches from an MF with num_users + 1 / num_items + 1 rows (twin=False)")
+        ops.settle_tables()
+        args = copy.copy(args) if args is not None else argparse_like(mf)
+        if args.embed_size != mf.embedding_size:
+            raise ValueError(f"args.embed_size {args.embed_size} is not the model's {mf.embedding_size}")
+        args.adver = 1  # the branch is the APR phase unless a member says adver = 0
+        g = cls(mf.num_users, mf.num_items, args, grid, _init=False)
+        g._allocate(mf.device)
+        g.embedding_P.copy_(mf.embedding_P.unsqueeze(0).expand_as(g.embedding_P))
+        g.embedding_Q.copy_(mf.embedding_Q.unsqueeze(0).expand_as(g.embedding_Q))
+        return g
+
+    def hparams(self):
+        """The members' StepHParams, in member order."""
+        return [ops.StepHParams(lr=a.lr, eps=a.eps, reg=a.reg, reg_adv=a.reg_adv, adver=int(bool(a.adver)))
+                for a in self.member_args]
+
+    def member(self, m):
+        """Member m as an MF on views of slice m: it owns no table storage, and
+        what the grid trains it sees (and the other way round)."""
+        if self._members[m] is None:
+            mf = MF(self.num_users, self.num_items, self.member_args[m])
+            mf._create_placeholders()
+            mf.device = self.device
+            mf.num_user_rows, mf.num_item_rows = self.num_user_rows, self.num_item_rows
+            mf.embedding_P, mf.embedding_Q = self.embedding_P[m], self.embedding_Q[m]
+            mf.accumulator_P, mf.accumulator_Q = self.accumulator_P[m], self.accumulator_Q[m]
+            mf.h = None
+            mf._create_fetches()
+            mf.delta_P = torch.zeros_like(mf.embedding_P)
+            mf.delta_Q = torch.zeros_like(mf.embedding_Q)
+            mf._adv_calls, mf._ctx, mf._pipe, mf._delta_feed = 0, None, None, None
+            mf.built = True
+            self._members[m] = mf
+        return self._members[m]
+
+    def train_epoch(self, user, item_pos, item_neg, batch_size, losses=False, check=True):
+        """One ops.grid_train call over the triplets, on every member."""
+        return ops.grid_train(self.embedding_P, self.embedding_Q, self.accumulator_P, self.accumulator_Q,
+                              self.hparams(), user, item_pos, item_neg, batch_size, losses=losses, check=check)
+
+
+def argparse_like(mf):
+    """The constructor arguments of an MF, read back from it (MFGrid.from_model)."""
+    import argparse
+    return argparse.Namespace(embed_size=mf.embedding_size, lr=mf.learning_rate, reg=mf.reg, dns=mf.dns, adv=mf.adv,
+                              eps=mf.eps, adver=mf.adver, reg_adv=mf.reg_adv, epochs=mf.epochs, seed=mf.seed)
 
 
 class Session:

@@ -1732,6 +1732,85 @@ def fold_in_items(P, Q, item_off, user_pos, item_neg, hp: StepHParams, epochs: i
                     user_pos, item_neg, hp, epochs, batch, init, acc_init, check)
 
 
+GRID_MAX_MODELS = 64    # ACF_GRID_MAX_MODELS
+GRID_MAX_BATCH = 1024   # ACF_GRID_MAX_BATCH
+GRID_MAX_DIM = 256
+
+
+def grid_workspace(n_models: int, batch_size: int, n_batches: int, num_user_rows: int, num_item_rows: int,
+                   dim: int) -> int:
+    """Bytes of workspace grid_train needs (acf_apr_grid_workspace; host only)."""
+    return _workspace_bytes("acf_apr_grid_workspace", n_models, batch_size, n_batches, num_user_rows, num_item_rows,
+                            dim)
+
+
+def grid_train(P, Q, accP, accQ, hparams, user, item_pos, item_neg, batch_size: int, *, losses: bool = False,
+               check: bool = True):
+    """training_batch for M models over ONE triplet stream in one call
+    (acf_apr_grid_train), in place.  P, accP [M, user rows, d] and Q, accQ
+    [M, item rows, d] are member-major, so P[m] is an ordinary dense table;
+    hparams is a sequence of M StepHParams (lr, eps, reg, reg_adv, adver, clip_lo,
+    clip_hi per member; adv="random" and zero_delta are not grid modes); the
+    triplets (int32, a multiple of batch_size long) are shared by all members.
+    d is a multiple of 4 in [4, 256], 1 <= M <= 64, 1 <= batch_size <= 1024.
+    A member's result depends on its own tables and hparams and the triplets only,
+    bit for bit, whatever M and its position are; equal inputs give equal bits.
+    losses: return (loss_clean, loss_adv) [M, n] float32, the per-triplet losses of
+    each batch before its update (loss_adv rows of members with adver = 0 stay 0);
+    otherwise None.  Bad arguments raise ValueError / TypeError before any native
+    call; with check, an index outside its table raises NativeIndexError before
+    any table is written."""
+    hps = list(hparams)
+    M = len(hps)
+    if not 1 <= M <= GRID_MAX_MODELS:
+        raise ValueError(f"a grid has 1 to {GRID_MAX_MODELS} members, got {M}")
+    for m, h in enumerate(hps):
+        if not isinstance(h, StepHParams):
+            raise TypeError(f"hparams[{m}] must be a StepHParams, got {type(h).__name__}")
+        if h.adv != "grad" or h.zero_delta:
+            raise ValueError(f"hparams[{m}]: adv='random' and zero_delta are not grid modes")
+    for t, n in ((P, "embedding_P"), (Q, "embedding_Q"), (accP, "accumulator_P"), (accQ, "accumulator_Q")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{n} must be a torch.Tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{n} must be torch.float32, got {t.dtype}")
+        if t.dim() != 3 or t.shape[0] != M:
+            raise ValueError(f"{n} must be [M = {M}, rows, d], got shape {tuple(t.shape)}")
+    if accP.shape != P.shape or accQ.shape != Q.shape:
+        raise ValueError(f"accumulator shapes {tuple(accP.shape)} / {tuple(accQ.shape)} differ from the tables' "
+                         f"{tuple(P.shape)} / {tuple(Q.shape)}")
+    d = P.shape[2]
+    if Q.shape[2] != d:
+        raise ValueError("embedding_P and embedding_Q dims differ")
+    if d % 4 or not 4 <= d <= GRID_MAX_DIM:
+        raise ValueError(f"grid dim must be a multiple of 4 in [4, {GRID_MAX_DIM}], got {d}")
+    B = int(batch_size)
+    if not 1 <= B <= GRID_MAX_BATCH:
+        raise ValueError(f"batch_size must lie in [1, {GRID_MAX_BATCH}], got {batch_size}")
+    n = len(user)
+    if len(item_pos) != n or len(item_neg) != n:
+        raise ValueError("user, item_pos and item_neg must have equal lengths")
+    if n % B:
+        raise ValueError(f"{n} triplets is not a multiple of batch_size {B}")
+    dev = P.device
+    for t, nm in ((P, "embedding_P"), (Q, "embedding_Q"), (accP, "accumulator_P"), (accQ, "accumulator_Q")):
+        _require(t, nm, torch.float32, dev, 3)
+    u, i, j = (_idx(x, nm, dev) for x, nm in ((user, "user"), (item_pos, "item_pos"), (item_neg, "item_neg")))
+    settle_tables()
+    nb = n // B
+    U1, I1 = P.shape[1], Q.shape[1]
+    lc = torch.zeros((M, n), dtype=torch.float32, device=dev) if losses else None
+    la = torch.zeros((M, n), dtype=torch.float32, device=dev) if losses else None
+    chp = (HParams * M)(*[h.to_c() for h in hps])
+    nbytes = grid_workspace(M, B, nb, U1, I1, d)
+    work = _workspace(nbytes, 8, dev)
+    with _on(dev):
+        call("acf_apr_grid_train", P.data_ptr(), Q.data_ptr(), accP.data_ptr(), accQ.data_ptr(), M, U1, I1, d, chp,
+             u.data_ptr() if n else None, i.data_ptr() if n else None, j.data_ptr() if n else None, B, nb,
+             _ptr(lc), _ptr(la), work.data_ptr(), nbytes, int(bool(check)), _stream_ptr(dev))
+    return (lc, la) if losses else None
+
+
 def eval_positions_list(P, Q, users, test_items, cand_off, cand_items):
     """_eval_by_user positions over explicit candidate lists ("sample" mode)."""
     settle_tables()

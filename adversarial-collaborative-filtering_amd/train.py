@@ -270,3 +270,113 @@ def training(model, dataset, args, runName, epoch_start, epoch_end, time_stamp, 
             save_checkpoint(model, ckpt_save_path, epoch_count)
     save_checkpoint(model, ckpt_save_path, epoch_count)
     return best_res
+
+
+# ---------------------------------------------------------------------------
+# a grid of models over one triplet stream
+def grid_run_names(grid_model, args, time_stamp):
+    """The run name of every member: the name cli.main gives a single apr run at
+    that member's (eps, reg_adv); a grid that also varies lr or the seed appends
+    _lr<lr> / _s<seed>, which no single-model name has."""
+    from .cli import apr_run_name
+    lrs = {a.lr for a in grid_model.member_args}
+    seeds = {getattr(a, "seed", None) for a in grid_model.member_args}
+    names = []
+    for a in grid_model.member_args:
+        name = apr_run_name(args.dataset, args.model, args.embed_size, a.eps, a.reg_adv, time_stamp)
+        if len(lrs) > 1:
+            name += "_lr%f" % a.lr
+        if len(seeds) > 1:
+            name += "_s%d" % int(a.seed or 0)
+        names.append(name)
+    if len(set(names)) != len(names):
+        names = ["%s_g%d" % (n, m) for m, n in enumerate(names)]  # members equal in all four: tell them apart
+    return names
+
+
+def write_grid_table(path, name, grid_model, best):
+    """<runName>.grid: one line per member, "member<TAB>eps<TAB>reg_adv<TAB>lr<TAB>reg<TAB>adver<TAB>seed<TAB>
+    best_epoch<TAB>hr10<TAB>ndcg10" (floats by repr; best_epoch -1 and nan metrics: never evaluated)."""
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, name), "w") as f:
+        for m, a in enumerate(grid_model.member_args):
+            b = best[m]
+            f.write("%d\t%r\t%r\t%r\t%r\t%d\t%d\t%d\t%r\t%r\n" % (
+                m, float(a.eps), float(a.reg_adv), float(a.lr), float(a.reg), int(bool(a.adver)),
+                int(getattr(a, "seed", 0) or 0), b.get("epoch", -1), float(b.get("hr10", float("nan"))),
+                float(b.get("ndcg10", float("nan")))))
+
+
+def read_grid_table(file):
+    """The rows [(member, eps, reg_adv, lr, reg, adver, seed, best_epoch, hr10, ndcg10)] write_grid_table wrote."""
+    rows = []
+    with open(file) as f:
+        for n, line in enumerate(f):
+            p = line.rstrip("\n").split("\t")
+            if len(p) != 10:
+                raise ValueError(f"{file}: line {n} has {len(p)} fields, expected 10")
+            rows.append((int(p[0]), float(p[1]), float(p[2]), float(p[3]), float(p[4]), int(p[5]), int(p[6]),
+                         int(p[7]), float(p[8]), float(p[9])))
+    return rows
+
+
+def training_grid(grid_model, dataset, args, runName, epoch_start, epoch_end, time_stamp, sampler=None):
+    """`training` for an MFGrid: every epoch draws ONE sampled triplet stream and
+    trains all members on it in one ops.grid_train call.  The members therefore
+    see common negatives (common random numbers): a difference between two
+    members of a grid is a difference of their hyper-parameters or seeds, not
+    sampling noise, but M members are not M independent replications of the
+    sampler.  Every args.verbose epochs each member is evaluated through the
+    existing evaluation (output_evaluate on grid_model.member(m)) and logs to its
+    own <name>.out / .hr / .ndcg in the reference's formats, under the name a
+    single run at its (eps, reg_adv) gets (grid_run_names); the best epoch is
+    tracked per member, and <runName>.grid holds one line per member
+    (write_grid_table).  Returns the per-member best results."""
+    M = len(grid_model)
+    names = grid_run_names(grid_model, args, time_stamp)
+    out = args.path + "out/" + args.opath
+    eval_feed_dicts = init_eval_model(dataset, args)
+    if sampler is None:
+        sampler = DeviceSampler(dataset, args.batch_size, grid_model.device, seed=getattr(args, "seed", 0) or 0)
+    members = [grid_model.member(m) for m in range(M)]
+    best = [{} for _ in range(M)]
+    max_ndcg = [0.0] * M
+    k10 = min(10, eval_feed_dicts.K) - 1
+    epoch_count = epoch_start
+    for epoch_count in range(epoch_start, epoch_end + 1):
+        batch_begin = time()
+        ep = sampler.epoch(epoch_count)
+        torch.cuda.synchronize(grid_model.device)
+        batch_time = time() - batch_begin
+        evaluated = epoch_count % args.verbose == 0
+        prev_acc = [training_loss_acc(mf, None, ep, output_adv=0)[1] for mf in members] if evaluated else None
+        train_begin = time()
+        grid_model.train_epoch(ep.user, ep.item_pos, ep.item_neg, ep.batch_size)
+        torch.cuda.synchronize(grid_model.device)
+        train_time = time() - train_begin
+        for mf in members:
+            mf.last_train_batches = ep
+        if evaluated:
+            for m, mf in enumerate(members):
+                _, ndcg, cur_res, raw_result = output_evaluate(
+                    mf, None, dataset, ep, eval_feed_dicts, epoch_count, batch_time, train_time, prev_acc[m],
+                    names[m], args, output_adv=0)
+                if max_ndcg[m] < ndcg:
+                    max_ndcg[m] = ndcg
+                    hr_k, ndcg_k, _ = cur_res
+                    best[m] = {"result": cur_res, "epoch": epoch_count, "hr10": hr_k[k10], "ndcg10": ndcg_k[k10]}
+                    prediction2file(out, names[m] + ".hr", raw_result[:, 0, -1])
+                    prediction2file(out, names[m] + ".ndcg", raw_result[:, 1, -1])
+        if args.epochs == epoch_count:
+            for m in range(M):
+                if not best[m]:
+                    continue
+                write2file(out, names[m] + ".out", "Epoch %d is the best epoch" % best[m]["epoch"])
+                for idx, (hr_k, ndcg_k, auc_k) in enumerate(np.swapaxes(best[m]["result"], 0, 1)):
+                    write2file(out, names[m] + ".out",
+                               "K = %d: HR = %.4f, NDCG = %.4f AUC = %.4f" % (idx + 1, hr_k, ndcg_k, auc_k))
+    write_grid_table(out, runName + ".grid", grid_model, best)
+    if getattr(args, "ckpt", 0) > 0:
+        for m, mf in enumerate(members):
+            save_checkpoint(mf, ckpt_dirs(args, "%s_g%d" % (time_stamp, m))[0], epoch_count)
+    return best

@@ -809,6 +809,55 @@ int acf_fold_in_items(const float* P, int64_t num_user_rows, const float* Q, int
                       const float* init, const float* acc_init, float* Q_new, float* acc_new, float* loss,
                       int32_t check, void* stream);
 
+/* ---- grid training: M models over one triplet stream in one call --------------
+ * (the reference sweeps eps, reg_adv and d as one job per point; DESIGN.md
+ * section 4m.)  training_batch (utils.py:106-119, dns == 1) for n_batches
+ * consecutive batches of the shared triplets, for n_models members at once.
+ * Member m owns slice m of P, accP [M][num_user_rows][dim] and Q, accQ
+ * [M][num_item_rows][dim] (contiguous, member-major: a slice is an ordinary dense
+ * table for every other entry point) and trains under hp[m] (a HOST array of M):
+ * lr, eps, reg, reg_adv, adver, clip_lo, clip_hi.  Members with adver = 0 (BPR:
+ * no delta and no adversarial term at all) and adver = 1 may share a grid; reg acts
+ * per occurrence, twice when adversarial, as in the step.  adv_mode != 0 (the
+ * random delta is keyed on a context's call counter) and zero_delta != 0 are
+ * ACF_E_INVALID.  dim: a multiple of 4 in [4, 256]; 1 <= n_models <=
+ * ACF_GRID_MAX_MODELS; 1 <= batch_size <= ACF_GRID_MAX_BATCH; num_user_rows +
+ * num_item_rows <= 2^31.  No context: the plan and all scratch live in `workspace`
+ * (device memory, 16-byte aligned, at least acf_apr_grid_workspace(...) bytes -- a
+ * host-only query).  Asynchronous on `stream`; the call never synchronises unless
+ * check != 0.
+ *   Plan: built once per call from the triplets alone and read by all members: per
+ *   batch the unique user and item rows and per row its terms in a fixed order, the
+ *   pos branch's terms in triplet order, then the neg branch's (acf_adv_direction's
+ *   order); a row of more than 256 terms is summed as partial sums of 256
+ *   consecutive terms, added in order.
+ *   Schedule: per batch three launches with (member, unique row) as the grid: the
+ *   clean gradient and delta, the adversarial sum, Adagrad.  No float atomics.
+ *   loss_clean, loss_adv [M][n_batches * batch_size] (may be NULL): the per-triplet
+ *   losses of every member, each batch before its own update; loss_adv of a member
+ *   with adver = 0 is not written.
+ * Guarantees.  A member's outputs depend on that member's tables, its hp and the
+ * triplets only: they are the same bits whatever n_models is and whichever position
+ * the member has.  Two calls on equal inputs give equal bits.  One call of n batches
+ * equals n calls of one batch.  The results are NOT bit-identical to acf_apr_train,
+ * whose summation order depends on its team geometry; they agree with it at the
+ * oracle's tolerance.
+ * Errors.  ACF_E_INVALID before any launch: a NULL pointer, n_models, dim,
+ * batch_size or n_batches out of range, a short or misaligned workspace, an
+ * unsupported hp field.  check != 0: the call synchronises once after the plan
+ * kernel and returns ACF_E_RANGE when an index is outside its table, before any
+ * table is written (check == 0: such an index is read as row 0).  n_batches = 0
+ * does nothing. */
+#define ACF_GRID_MAX_MODELS 64
+#define ACF_GRID_MAX_BATCH 1024
+int acf_apr_grid_workspace(int32_t n_models, int32_t batch_size, int32_t n_batches, int64_t num_user_rows,
+                           int64_t num_item_rows, int32_t dim, size_t* bytes);
+int acf_apr_grid_train(float* P, float* Q, float* accP, float* accQ, int32_t n_models, int64_t num_user_rows,
+                       int64_t num_item_rows, int32_t dim, const acf_apr_hparams* hp, const int32_t* user,
+                       const int32_t* item_pos, const int32_t* item_neg, int32_t batch_size, int32_t n_batches,
+                       float* loss_clean, float* loss_adv, void* workspace, size_t workspace_bytes, int32_t check,
+                       void* stream);
+
 /* ---- sampler: shuffle/_get_train_batch (APR.py:39-81) --------------------
  * Shuffles the n_pos positive pairs with a counter-based permutation of
  * `seed`, keeps floor(n_pos / batch_size) * batch_size of them (drop-last,
