@@ -92,6 +92,8 @@ SIGNATURES = {
     "acf_list_exposure": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _I32, _P, _P]),
     "acf_exposure_metrics_workspace": (ctypes.c_int, [_I32, _I32, ctypes.POINTER(ctypes.c_size_t)]),
     "acf_exposure_metrics": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "acf_list_similarity": (ctypes.c_int, [_P, _I64, _I32, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _I32, _P]),
+    "acf_rerank_mmr": (ctypes.c_int, [_P, _I64, _I32, _P, _P, _I32, _I32, _I32, _F, _I32, _P, _P, _P, _I32, _P]),
     "acf_eval_positions_worst_workspace": (ctypes.c_int, [_I32, _I32, _I32, ctypes.POINTER(ctypes.c_size_t)]),
     "acf_eval_positions_worst": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _I32, _I32, _P, _P, _P, _I32, _I32,
                                                 _P, _P, ctypes.c_size_t, _I32, _P]),

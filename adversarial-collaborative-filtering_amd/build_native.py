@@ -37,7 +37,8 @@ LIBS = {
                         f"{PKG}/csrc/acf_fold.h", f"{PKG}/csrc/acf_fold_items.h", f"{PKG}/csrc/acf_topk_select.h",
                         f"{PKG}/csrc/acf_eval_multi.h", f"{PKG}/csrc/acf_sweep.h",
                         f"{PKG}/csrc/acf_eval_worst.h", f"{PKG}/csrc/acf_neighbors.h",
-                        f"{PKG}/csrc/acf_eval_radius.h", f"{PKG}/csrc/acf_lists.h"]},
+                        f"{PKG}/csrc/acf_eval_radius.h", f"{PKG}/csrc/acf_lists.h",
+                        f"{PKG}/csrc/acf_diverse.h"]},
     "neumf": {"lib": f"{PKG}/lib/libacf_neumf.so",
               "srcs": [f"{PKG}/csrc/acf_neumf.hip", f"{PKG}/csrc/acf_keras_mf.hip"],
               "headers": ["include/acf_apr.h", "include/acf_neumf.h", f"{PKG}/csrc/acf_host.h",

@@ -114,6 +114,16 @@ def parse_args(argv=None, flavor="ori"):
                         "is never its own neighbour.  Needs --topk.")
     p.add_argument("--similar_metric", choices=["dot", "cosine", "euclid"], default="cosine",
                    help="The similarity of --similar: cosine, the dot product, or euclid (nearest by L2 distance).")
+    p.add_argument("--diverse_lambda", type=parse_lambda_list, default=[],
+                   help="After training, re-rank each user's --diverse_pool best items to --topk by maximal marginal "
+                        "relevance at these lambda in [0, 1] (comma separated, e.g. \"1,0.7,0.5\"; 1 keeps the "
+                        "plain top-K) and write, per lambda, HR and NDCG of the held-out item, the intra-list "
+                        "similarity and the exposure metrics of the lists to <out>/<runName>.diverse (empty: off).  "
+                        "Needs --topk.")
+    p.add_argument("--diverse_pool", type=int, default=128,
+                   help="The size of the candidate pool of --diverse_lambda: --topk <= N <= 128.")
+    p.add_argument("--diverse_metric", choices=["dot", "cosine", "euclid"], default="cosine",
+                   help="The item similarity of --diverse_lambda.")
     p.add_argument("--grid_eps", type=parse_eps_list, default=[],
                    help="With --model apr: train the APR phase as a grid, one member per value of eps (comma "
                         "separated, e.g. \"0.1,0.5,1\"), all members over one triplet stream in one call per epoch. "
@@ -129,7 +139,7 @@ def parse_args(argv=None, flavor="ori"):
     args = p.parse_args(argv)
     if grid_of(args) is not None:
         extras = [f for f in ("topk", "fold_in", "fold_in_items", "test_multi", "similar", "robust_eps",
-                              "robust_lists", "certify_eps", "certify_radius") if getattr(args, f)]
+                              "robust_lists", "certify_eps", "certify_radius", "diverse_lambda") if getattr(args, f)]
         if extras:
             p.error("--grid_* trains several models; --%s works on one (run it on a member's checkpoint)" % extras[0])
         if len(grid_of(args)) > 64:
@@ -140,6 +150,8 @@ def parse_args(argv=None, flavor="ori"):
         p.error("--fold_in_items needs --topk K (K > 0)")
     if args.similar is not None and args.topk <= 0:
         p.error("--similar needs --topk K (K > 0)")
+    if args.diverse_lambda and not 1 <= args.topk <= args.diverse_pool <= 128:
+        p.error("--diverse_lambda needs 1 <= --topk <= --diverse_pool <= 128")
     return args
 
 
@@ -178,6 +190,15 @@ def parse_grid_seeds(text):
     if not 0 <= v <= 64:
         raise argparse.ArgumentTypeError(f"grid_seeds must lie in [0, 64], got {text!r}")
     return v
+
+
+def parse_lambda_list(text):
+    """--diverse_lambda: "1,0.7,0.5" -> [1.0, 0.7, 0.5]; every value in [0, 1]."""
+    out = parse_eps_list(text)
+    for v in out:
+        if not v <= 1:
+            raise argparse.ArgumentTypeError(f"a lambda must lie in [0, 1], got {v!r}")
+    return out
 
 
 def grid_of(args):
@@ -331,6 +352,29 @@ def read_lists(file):
             if len(parts) != 11:
                 raise ValueError(f"{file}: line {n} has {len(parts)} fields, expected 11")
             rows.append((parts[0], float(parts[1]), int(parts[2]), *[float(x) for x in parts[3:]]))
+    return rows
+
+
+def write_diverse(path, name, rows):
+    """One line "lam<TAB>K<TAB>hr<TAB>ndcg<TAB>ils<TAB>total<TAB>coverage<TAB>gini<TAB>entropy<TAB>arp<TAB>aplt"
+    per row of evaluate.diversity_tradeoff (floats by repr: the reader gets the same values back)."""
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, name), "w") as f:
+        for lam, K, *vals in rows:
+            if len(vals) != 9:
+                raise ValueError(f"a diverse row has 9 metrics, got {len(vals)}")
+            f.write("%r\t%d\t%s\n" % (float(lam), int(K), "\t".join(repr(float(v)) for v in vals)))
+
+
+def read_diverse(file):
+    """The rows [(lam, K, hr, ndcg, ils, total, coverage, gini, entropy, arp, aplt)] write_diverse wrote."""
+    rows = []
+    with open(file) as f:
+        for n, line in enumerate(f):
+            parts = line.rstrip("\n").split("\t")
+            if len(parts) != 11:
+                raise ValueError(f"{file}: line {n} has {len(parts)} fields, expected 11")
+            rows.append((float(parts[0]), int(parts[1]), *[float(x) for x in parts[2:]]))
     return rows
 
 
@@ -525,6 +569,12 @@ def main(argv=None, flavor="ori"):
         final = amf if args.model == "apr" else m
         items, _ = similar_items(final, read_id_file(args.similar), k=args.topk, metric=args.similar_metric)
         write_topk(out, runName + ".similar", items)  # line n: the n-th id of FILE
+    if args.diverse_lambda:
+        from .evaluate import diversity_tradeoff
+        final = amf if args.model == "apr" else m
+        rows = diversity_tradeoff(final, dataset, lams=args.diverse_lambda, k=args.topk, pool=args.diverse_pool,
+                                  cutoffs=[args.topk], metric=args.diverse_metric)
+        write_diverse(out, runName + ".diverse", rows)
     if args.test_multi is not None:
         from .data import load_test_lists
         from .evaluate import evaluate_multi, init_eval_multi

@@ -24,6 +24,7 @@
 #include "acf_adv.h"   // whole-stream adversarial direction (k_adv_*): DESIGN.md §4c
 #include "acf_eval_multi.h"  // multi-item evaluation and rank metrics (k_evx_*): DESIGN.md §4f
 #include "acf_lists.h"  // list-level robustness: list overlap and item exposure (k_lst_*): DESIGN.md §4l
+#include "acf_diverse.h"  // intra-list similarity and MMR re-ranking (k_div_*): DESIGN.md §4n
 #include "acf_eval_worst.h"  // the certified margin sweep (k_cert_sweep), worst-case positions: DESIGN.md §4g
 #include "acf_eval_radius.h"  // certified radius, the K weakest candidates (its selecting sink): DESIGN.md §4j
 
@@ -452,6 +453,82 @@ extern "C" int acf_exposure_metrics(const int32_t* counts, int32_t num_items, in
   k_lst_expo_final<<<(unsigned)n_cutoffs, 256, 0, s>>>(part, epart, B, N, out);
   HIP_TRY(hipGetLastError());
   return ACF_OK;
+}
+
+// ---- diversity: intra-list similarity, MMR re-ranking (acf_diverse.h) ----------------
+static int div_check(int64_t TR, int32_t d, int32_t n, int32_t metric) {
+  ACF_RET(check_dim(d));
+  ACF_CHECK(n >= 0, ACF_E_INVALID, "negative count");
+  ACF_CHECK(TR > 0, ACF_E_INVALID, "empty table");
+  ACF_CHECK(metric >= NBR_DOT && metric <= NBR_EUC, ACF_E_INVALID,
+            "metric must be 0 (dot), 1 (cosine) or 2 (Euclidean), got %d", metric);
+  return ACF_OK;
+}
+
+// the instance of a kernel family KFN<METRIC, EPL, LDS> for a row of `len` positions
+#define DIV_PICK(KFN, metric, len, lds)                                                           \
+  ((metric) == NBR_DOT   ? DIV_PICK2(KFN, NBR_DOT, len, lds)                                      \
+   : (metric) == NBR_COS ? DIV_PICK2(KFN, NBR_COS, len, lds)                                      \
+                         : DIV_PICK2(KFN, NBR_EUC, len, lds))
+#define DIV_PICK2(KFN, M, len, lds)                                                               \
+  ((len) > 64 ? ((lds) ? &KFN<M, 2, true> : &KFN<M, 2, false>) : ((lds) ? &KFN<M, 1, true> : &KFN<M, 1, false>))
+
+// the error word of a call, from the stream's allocator; with `check`, read back once after the launches
+static int div_finish(int32_t* err, int32_t check, hipStream_t s) {
+  int32_t herr = 0;
+  if (check) ACF_RET(read_error_word(err, s, &herr));
+  HIP_TRY(hipFreeAsync(err, s));
+  ACF_CHECK(herr == 0, ACF_E_RANGE, "index out of range (id >= num_rows)");
+  return ACF_OK;
+}
+
+extern "C" int acf_list_similarity(const float* T, int64_t TR, int32_t d, const int32_t* lists, int32_t n, int32_t k,
+                                   const int32_t* cutoffs, int32_t n_cutoffs, int32_t metric, double* ils,
+                                   double* means, int32_t check, void* stream_) {
+  ACF_RET(div_check(TR, d, n, metric));
+  LstCuts cuts;
+  ACF_RET(lst_cuts(k, cutoffs, n_cutoffs, &cuts));
+  ACF_CHECK(T && lists && ils && means, ACF_E_INVALID, "NULL argument");
+  if (n == 0) return ACF_OK;
+  int kmax = 0;
+  for (int c = 0; c < n_cutoffs; ++c) kmax = std::max(kmax, cuts.k[c]);
+  const size_t rows_bytes = div_rows_bytes(kmax, d);
+  const bool lds = rows_bytes <= DIV_ROWS_LDS;
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  // [ error word, padded to 16 bytes | flag [n][n_cutoffs]: which rows count in which mean ]
+  char* tmp = nullptr;
+  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&tmp), 16 + (size_t)n * n_cutoffs, s));
+  int32_t* err = reinterpret_cast<int32_t*>(tmp);
+  uint8_t* flag = reinterpret_cast<uint8_t*>(tmp + 16);
+  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+  const auto kfn = DIV_PICK(k_div_ils, metric, kmax, lds);
+  kfn<<<(unsigned)n, 64, lds ? rows_bytes : 0, s>>>(T, TR, d, lists, k, cuts, ils, flag, err);
+  HIP_TRY(hipGetLastError());
+  k_div_means<<<(unsigned)n_cutoffs, 256, 0, s>>>(ils, flag, n, n_cutoffs, means);
+  HIP_TRY(hipGetLastError());
+  return div_finish(err, check, s);
+}
+
+extern "C" int acf_rerank_mmr(const float* T, int64_t TR, int32_t d, const int32_t* cand, const float* rel, int32_t n,
+                              int32_t m, int32_t k_out, float lam, int32_t metric, int32_t* items, float* rel_out,
+                              float* obj, int32_t check, void* stream_) {
+  ACF_RET(div_check(TR, d, n, metric));
+  ACF_CHECK(m >= 1 && m <= DIV_MAX_M, ACF_E_INVALID, "m must be in [1, %d], got %d", DIV_MAX_M, m);
+  ACF_CHECK(k_out >= 1 && k_out <= m, ACF_E_INVALID, "k_out must be in [1, m = %d], got %d", m, k_out);
+  ACF_CHECK(lam >= 0.f && lam <= 1.f, ACF_E_INVALID, "lam must lie in [0, 1], got %g", (double)lam);
+  ACF_CHECK(T && cand && rel && items && rel_out && obj, ACF_E_INVALID, "NULL argument");
+  if (n == 0) return ACF_OK;
+  const float oml = 1.0f - lam;
+  const size_t rows_bytes = div_rows_bytes(m, d);
+  const bool lds = rows_bytes <= DIV_ROWS_LDS;
+  hipStream_t s = static_cast<hipStream_t>(stream_);
+  int32_t* err = nullptr;
+  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&err), 16, s));
+  HIP_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+  const auto kfn = DIV_PICK(k_div_mmr, metric, m, lds);
+  kfn<<<(unsigned)n, 64, lds ? rows_bytes : 0, s>>>(T, TR, d, cand, rel, m, k_out, lam, oml, items, rel_out, obj, err);
+  HIP_TRY(hipGetLastError());
+  return div_finish(err, check, s);
 }
 
 // ---- the certified evaluations' host frame (k_cert_sweep: acf_eval_worst.h, acf_eval_radius.h) ----

@@ -365,6 +365,131 @@ def list_robustness(model, dataset, triplets, eps_list, k=100, cutoffs=(1, 10, 1
     return rows
 
 
+REL_NORMS = ("minmax", "none")
+
+
+def normalise_relevance(items, scores, rel_norm="minmax"):
+    """The relevances ops.rerank_mmr gets for a pool (items int32 [n, m], scores
+    float32 [n, m] tensors, as ops.recommend_topk writes them), in torch on the
+    pool's device.  'minmax': per row (s - min) / (max - min) over the valid
+    entries (id >= 0), so that relevance and similarity share a scale; 0 where
+    max = min (a constant row, a single valid entry) and at the entries that are
+    not valid.  'none': the scores as they are."""
+    import torch
+    if rel_norm not in REL_NORMS:
+        raise ValueError(f"rel_norm must be one of {REL_NORMS}, got {rel_norm!r}")
+    if rel_norm == "none":
+        return scores.contiguous()
+    valid = items >= 0
+    inf = torch.full_like(scores, float("inf"))
+    lo = torch.where(valid, scores, inf).min(dim=1, keepdim=True).values
+    hi = torch.where(valid, scores, -inf).max(dim=1, keepdim=True).values
+    span = hi - lo
+    ok = valid & (span > 0)
+    rel = (scores - lo) / torch.where(span > 0, span, torch.ones_like(span))
+    return torch.where(ok, rel, torch.zeros_like(rel)).contiguous()
+
+
+def _pool_scores(pool_items, pool_scores, items):
+    """The pool's scores of the re-ranked ids (a pool holds an id once): sort each
+    pool row by id, search, gather; -inf at the -1 tail."""
+    import torch
+    sid, perm = pool_items.sort(dim=1)
+    at = torch.searchsorted(sid, items.clamp(min=0).contiguous()).clamp(max=pool_items.shape[1] - 1)
+    out = pool_scores.gather(1, perm.gather(1, at))
+    return torch.where(items >= 0, out, torch.full_like(out, float("-inf")))
+
+
+def _rerank(Q, pool_items, pool_scores, k, lam, metric, rel_norm):
+    rel = normalise_relevance(pool_items, pool_scores, rel_norm)
+    return ops.rerank_mmr(Q, pool_items, rel, int(k), float(lam), metric)[0]
+
+
+def _check_pool(k, pool):
+    if not 1 <= int(k) <= int(pool) <= ops.TOPK_MAX_K:
+        raise ValueError(f"need 1 <= k <= pool <= {ops.TOPK_MAX_K}, got k = {k}, pool = {pool}")
+
+
+def recommend_diverse(model_or_tables, dataset=None, users=None, k: int = 10, pool: int = 128, lam: float = 0.7,
+                      metric: str = "cosine", rel_norm: str = "minmax", exclude_train: bool = True):
+    """k diverse items per user: recommend's `pool` best items, re-ranked greedily
+    by maximal marginal relevance on the GPU (ops.rerank_mmr): each pick maximises
+    lam * relevance - (1 - lam) * the largest similarity to what is already picked,
+    similarity being `metric` between rows of the item table.  rel_norm: 'minmax'
+    scales a user's pool scores to [0, 1] first, 'none' uses them as they are.
+    Returns (items int32 [n, k], scores float32 [n, k]) numpy arrays in the order
+    picked, the scores the model's own; -1 / -inf past a user's candidates.
+    lam = 1 is recommend(k)."""
+    _check_pool(k, pool)
+    if rel_norm not in REL_NORMS:
+        raise ValueError(f"rel_norm must be one of {REL_NORMS}, got {rel_norm!r}")
+    P, Q = _tables_of(model_or_tables)
+    if users is None:
+        if dataset is None:
+            raise ValueError("users=None needs a dataset")
+        users = np.arange(dataset.num_users, dtype=np.int64)
+    users = np.asarray(users, dtype=np.int64).reshape(-1)
+    num_candidates = min(int(dataset.num_items), Q.shape[0]) if dataset is not None else Q.shape[0]
+    off = ex = None
+    if exclude_train and dataset is not None:
+        off, ex = train_exclusions(dataset, users)
+    pool_items, pool_scores = ops.recommend_topk(P, Q, users.astype(np.int32), int(pool), num_candidates, off, ex)
+    items = _rerank(Q, pool_items, pool_scores, k, lam, metric, rel_norm)
+    return items.cpu().numpy(), _pool_scores(pool_items, pool_scores, items).cpu().numpy()
+
+
+def diversity(model_or_tables, dataset, users=None, k=100, cutoffs=(10, 100), metric="cosine", exclude_train=True):
+    """How alike the items of the model's own top-k lists are: rows (cutoff, ils),
+    ils the mean over the users of the intra-list similarity at that cutoff
+    (ops.list_similarity: the mean `metric` over the pairs of a list's items).
+    The lists stay on the device.  Cutoffs above k are an error."""
+    cutoffs = _list_cutoffs(cutoffs, k)
+    P, Q = _tables_of(model_or_tables)
+    sweep = _ListSweep(P, dataset, users, k, cutoffs, exclude_train)
+    _, means = ops.list_similarity(Q, sweep.lists(P, Q), cutoffs, metric)
+    return list(zip(cutoffs, means.cpu().tolist()))
+
+
+def _held_out_metrics(lists, tests, cutoffs):
+    """[(hr, ndcg)] per cutoff of each row's held-out item in its list, on the
+    device: the item's index p in the list gives 1 / log2(p + 2) when p < K."""
+    import torch
+    hit = lists == tests[:, None]
+    found = hit.any(dim=1)
+    p = torch.where(found, hit.to(torch.int32).argmax(dim=1), torch.full_like(tests, lists.shape[1])).to(torch.float64)
+    gain = math.log(2) / torch.log(p + 2.0)
+    n = max(1, lists.shape[0])
+    return [(float((p < K).sum()) / n, float(torch.where(p < K, gain, torch.zeros_like(gain)).sum()) / n)
+            for K in cutoffs]
+
+
+def diversity_tradeoff(model_or_tables, dataset, lams=(1.0, 0.7, 0.5), k=10, pool=128, cutoffs=(10,),
+                       metric="cosine", rel_norm="minmax", users=None):
+    """What diversifying costs and buys: rows (lam, cutoff, hr, ndcg, ils, total,
+    coverage, gini, entropy, arp, aplt), one per (lam, cutoff).  The pool (every
+    user's `pool` best items, train items excluded) is computed once; per lam it is
+    re-ranked to k items (ops.rerank_mmr) and the lists are held against the
+    dataset's held-out item (hr, ndcg at the cutoff), against themselves
+    (ops.list_similarity) and against the catalogue (ops.list_exposure +
+    ops.exposure_metrics), all on the device.  lam = 1 is the plain top-k row."""
+    import torch
+    _check_pool(k, pool)
+    cutoffs = _list_cutoffs(cutoffs, k)
+    P, Q = _tables_of(model_or_tables)
+    sweep = _ListSweep(P, dataset, users, pool, cutoffs, True)
+    tests = torch.as_tensor(np.asarray([dataset.testRatings[int(u)][1] for u in sweep.users.cpu().tolist()],
+                                       dtype=np.int32), device=P.device)
+    pool_items, pool_scores = ops.recommend_topk(P, Q, sweep.users, sweep.k, min(sweep.num_items, Q.shape[0]),
+                                                 sweep.off, sweep.ex)
+    rows = []
+    for lam in lams:
+        lists = _rerank(Q, pool_items, pool_scores, k, lam, metric, rel_norm)
+        ils = ops.list_similarity(Q, lists, cutoffs, metric)[1].cpu().tolist()
+        rows += [(float(lam), c, hr, ndcg, s, *e) for c, (hr, ndcg), s, e in
+                 zip(cutoffs, _held_out_metrics(lists, tests, cutoffs), ils, sweep.exposure(lists))]
+    return rows
+
+
 def pgd_host(P, Q, u, i, j, eps, iters=10, alpha=None, side="both", start=None, lo=-80.0, hi=1e8):
     """ops.adv_pgd restated in float64 numpy, the tests' yardstick: (delta_P,
     delta_Q, losses [iters + 1]).  Per iteration the clean BPR gradient of all the

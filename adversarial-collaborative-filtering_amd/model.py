@@ -274,6 +274,27 @@ class MF:
         from .evaluate import exposure
         return exposure(self, dataset, users=users, k=k, cutoffs=cutoffs, exclude_train=exclude_train)
 
+    def recommend_diverse(self, dataset=None, users=None, k=10, pool=128, lam=0.7, metric="cosine",
+                          rel_norm="minmax", exclude_train=True):
+        """evaluate.recommend_diverse: this model's `pool` best items per user
+        re-ranked to k by maximal marginal relevance: (items [n, k], scores [n, k])
+        numpy arrays."""
+        from .evaluate import recommend_diverse
+        return recommend_diverse(self, dataset, users=users, k=k, pool=pool, lam=lam, metric=metric,
+                                 rel_norm=rel_norm, exclude_train=exclude_train)
+
+    def diversity(self, dataset, users=None, k=100, cutoffs=(10, 100), metric="cosine"):
+        """evaluate.diversity: rows (cutoff, ils), the mean intra-list similarity of
+        this model's own top-k lists."""
+        from .evaluate import diversity
+        return diversity(self, dataset, users=users, k=k, cutoffs=cutoffs, metric=metric)
+
+    def diversity_tradeoff(self, dataset, lams=(1.0, 0.7, 0.5), k=10, pool=128, cutoffs=(10,), metric="cosine"):
+        """evaluate.diversity_tradeoff: rows (lam, cutoff, hr, ndcg, ils, total,
+        coverage, gini, entropy, arp, aplt) of the MMR re-ranked lists."""
+        from .evaluate import diversity_tradeoff
+        return diversity_tradeoff(self, dataset, lams=lams, k=k, pool=pool, cutoffs=cutoffs, metric=metric)
+
     def list_robustness(self, dataset, triplets, eps_list, k=100, cutoffs=(1, 10, 100), modes=("grad", "random"),
                         p=0.9, seed=0, iters=10, step=None, side="both", users=None):
         """evaluate.list_robustness: rows (mode, eps, cutoff, jaccard, rbo, overlap,

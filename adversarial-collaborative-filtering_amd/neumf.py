@@ -429,6 +429,13 @@ class NeuMF:
         raise NotImplementedError("NeuMF has two item tables (the GMF and the MLP embeddings) that only the "
                                   "network combines, so there is no single similarity between two items.")
 
+    def _no_item_similarity(self, *args, **kwargs):
+        raise NotImplementedError("NeuMF has two item tables (the GMF and the MLP embeddings) that only the "
+                                  "network combines, so there is no single similarity between two items to "
+                                  "diversify or to measure a list by.")
+
+    recommend_diverse = diversity = diversity_tradeoff = _no_item_similarity
+
     def similar_users(self, users, k=10, metric="cosine", rows=None):
         raise NotImplementedError("NeuMF has two user tables (the GMF and the MLP embeddings) that only the "
                                   "network combines, so there is no single similarity between two users.")

@@ -1219,6 +1219,95 @@ def exposure_metrics(counts, pop=None, tail=None) -> torch.Tensor:
     return out
 
 
+# ---- diversity: intra-list similarity and MMR re-ranking ----
+def _metric_id(metric) -> int:
+    if metric not in NEIGHBOR_METRICS:
+        raise ValueError(f"metric must be one of {sorted(NEIGHBOR_METRICS)}, got {metric!r}")
+    return NEIGHBOR_METRICS[metric]
+
+
+def _sim_table(T) -> None:
+    """TypeError / ValueError unless T is a contiguous 2-D float32 tensor with at
+    least one row and a dim the ranking calls take; its device is checked last."""
+    if not isinstance(T, torch.Tensor) or T.dtype != torch.float32 or T.dim() != 2:
+        raise TypeError("T must be a 2-D torch.float32 tensor")
+    if not T.is_contiguous():
+        raise ValueError("T must be contiguous")
+    rows, d = T.shape
+    if rows < 1 or not 4 <= d <= 1024 or d % 4:
+        raise ValueError(f"T must be [>= 1, dim] with dim a multiple of 4 in [4, 1024], got shape {tuple(T.shape)}")
+
+
+def list_similarity(T, lists, cutoffs, metric: str = "cosine", check: bool = True):
+    """Intra-list similarity of the lists under table T (acf_list_similarity;
+    tests/diverse_ref.py is the numpy yardstick): (ils fp64 [n, n_cut], means fp64
+    [n_cut]) device tensors.  lists: device int32 [n, k], k <= 128, a negative
+    entry is "none"; cutoffs: 1 to 8 ints in [1, k]; metric as neighbors_topk's.
+    ils[r, c] is the mean similarity over the pairs of valid entries among the
+    first cutoffs[c] of row r, the pairs added in fp64 in a fixed order and divided
+    once; a row with fewer than 2 valid entries there gets 0.0 and is left out of
+    means[c].  Equal inputs give equal bits.  An id >= the table's rows is read as
+    row 0; with check the call then raises NativeIndexError (one sync, after its
+    launches).  Bad types, shapes, cutoffs and metric raise before any launch."""
+    _sim_table(T)
+    _id_lists(lists, "lists")
+    n, k = lists.shape
+    ks, cuts = _list_cutoffs(cutoffs, k)
+    mid = _metric_id(metric)
+    dev = _hip(T, "T")
+    _hip(lists, "lists", dev)
+    ils = torch.zeros((n, len(ks)), dtype=torch.float64, device=dev)
+    means = torch.zeros(len(ks), dtype=torch.float64, device=dev)
+    if n == 0:
+        return ils, means
+    settle_tables()
+    with _on(dev):
+        call("acf_list_similarity", T.data_ptr(), T.shape[0], T.shape[1], lists.data_ptr(), n, k, cuts, len(ks), mid,
+             ils.data_ptr(), means.data_ptr(), int(bool(check)), _stream_ptr(dev))
+    return ils, means
+
+
+def rerank_mmr(T, cand, rel, k: int, lam: float, metric: str = "cosine", check: bool = True):
+    """Greedy maximal-marginal-relevance re-ranking of candidate pools
+    (acf_rerank_mmr): (items int32 [n, k], rel float32 [n, k], obj float32 [n, k])
+    device tensors.  cand: device int32 [n, m], m <= 128; rel: device float32
+    [n, m], the pool's relevances; an entry counts if its id is >= 0 and its
+    relevance finite.  The first pick maximises lam * rel; every later one lam *
+    rel - (1 - lam) * max over the picks so far of sim(entry, pick), sim being
+    neighbors_topk's `metric` between rows of T; ties go to the lower pool position.
+    obj is the value each pick was made at; -1 / -inf / -inf once a pool runs out.
+    lam = 1 keeps the order of relevance, lam = 0 looks at similarity alone.  Every
+    operation is fp32 and rounded on its own: equal inputs give equal bits.  An id
+    >= the table's rows is read as row 0; with check the call then raises
+    NativeIndexError (one sync, after its launches).  Bad types, shapes, k, lam and
+    metric raise before any launch."""
+    _sim_table(T)
+    _id_lists(cand, "cand")
+    if not isinstance(rel, torch.Tensor) or rel.dtype != torch.float32:
+        raise TypeError("rel must be a torch.float32 tensor")
+    if rel.shape != cand.shape or not rel.is_contiguous():
+        raise ValueError(f"rel must be contiguous with cand's shape {tuple(cand.shape)}, got {tuple(rel.shape)}")
+    n, m = cand.shape
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= m:
+        raise ValueError(f"k must be an int in [1, m = {m}], got {k!r}")
+    if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not 0.0 <= float(lam) <= 1.0:
+        raise ValueError(f"lam must lie in [0, 1], got {lam!r}")
+    mid = _metric_id(metric)
+    dev = _hip(T, "T")
+    _hip(cand, "cand", dev)
+    _hip(rel, "rel", dev)
+    items = torch.empty((n, k), dtype=torch.int32, device=dev)
+    rel_out = torch.empty((n, k), dtype=torch.float32, device=dev)
+    obj = torch.empty((n, k), dtype=torch.float32, device=dev)
+    if n == 0:
+        return items, rel_out, obj
+    settle_tables()
+    with _on(dev):
+        call("acf_rerank_mmr", T.data_ptr(), T.shape[0], T.shape[1], cand.data_ptr(), rel.data_ptr(), n, m, k,
+             float(lam), mid, items.data_ptr(), rel_out.data_ptr(), obj.data_ptr(), int(bool(check)), _stream_ptr(dev))
+    return items, rel_out, obj
+
+
 WORST_MAX_EPS = 8                       # EVW_MAX_EPS
 WORST_SIDES = {"user": 0, "item": 1}
 

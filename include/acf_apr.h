@@ -563,6 +563,51 @@ int acf_exposure_metrics_workspace(int32_t num_items, int32_t n_cutoffs, size_t*
 int acf_exposure_metrics(const int32_t* counts, int32_t num_items, int32_t n_cutoffs, const int32_t* pop,
                          const uint8_t* tail, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- diversity: intra-list similarity and MMR re-ranking (no reference
+ * counterpart).  T: device fp32 [num_rows][dim], dim as
+ * the ranking calls take it.  sim(a, b) of two rows is acf_neighbors_topk's
+ * score under `metric` (0 dot, 1 cosine, 2 minus the squared Euclidean
+ * distance), from the same device functions: fp32, every operation rounded on
+ * its own, s = the sequential round-then-add dot product; cosine is den > 0 ?
+ * s / den + 0.0f : +0.0f with den = sqrtf(s_aa) * sqrtf(s_bb); sim is symmetric
+ * bit for bit and never -0.0.  An id >= num_rows anywhere in `lists` / `cand` is
+ * read as row 0; with check != 0 the call then synchronises once, after its
+ * launches, and returns ACF_E_RANGE (check == 0: no error, no sync).  A negative
+ * id is "none" wherever it stands.  dim, metric, m, k, k_out, the cutoffs or lam
+ * out of range and NULL pointers are ACF_E_INVALID before any launch; n = 0
+ * returns at once and writes nothing.  Both calls are asynchronous on `stream`
+ * (the error word and the flags come from the stream's allocator), use no float
+ * atomics, and give every row a result that depends on that row alone: equal
+ * inputs give equal bits.  Tables are assumed finite.
+ *
+ * acf_list_similarity: lists device int32 [n][k], 1 <= k <= 128; cutoffs: a HOST
+ * array of 1 <= n_cutoffs <= 8 values K in [1, k].  For row r, position b holding
+ * a valid id has c_b = sum over the valid positions a < b, a ascending from
+ * +0.0, of (double)sim(T[id_a], T[id_b]); repeated ids are separate entries.  With
+ * L the number of valid positions among the first K and S_K the sum of their
+ * c_b, b ascending from +0.0, ils[r][K] = S_K / (double)(L (L - 1) / 2) (device
+ * fp64 [n][n_cutoffs]), and 0.0 where L < 2.  means [n_cutoffs]: per cutoff the
+ * mean over the rows with L >= 2 (0.0 when there is none): thread t of 256 adds
+ * rows t, t + 256, ... ascending, a fixed halving tree adds the 256 sums, one
+ * division by the number of rows.
+ *
+ * acf_rerank_mmr: cand device int32 [n][m], rel device fp32 [n][m], 1 <= m <=
+ * 128, 1 <= k_out <= m, 0 <= lam <= 1.  Position c is valid iff cand >= 0 and rel
+ * is finite.  a_c = lam * rel_c; oml = 1.0f - lam (host, once).  Step 0 picks the
+ * valid position with the largest a_c; step j >= 1 the unpicked valid position
+ * with the largest a_c - oml * pen_c (two products and a subtraction, each
+ * rounded), where pen_c = sim(T[cand_c], T[cand_s]) for the first pick s and
+ * fmaxf(pen_c, that) for every later one (no sim is -0.0, so no pen is).  Equal
+ * values (-0 and +0 are equal) go to the lower position.  Step j writes items[r][j] = cand as given, rel_out =
+ * its rel, obj = the value it was picked at; once the valid positions run out the
+ * tail is -1 / -inf / -inf. */
+int acf_list_similarity(const float* T, int64_t num_rows, int32_t dim, const int32_t* lists, int32_t n, int32_t k,
+                        const int32_t* cutoffs, int32_t n_cutoffs, int32_t metric, double* ils, double* means,
+                        int32_t check, void* stream);
+int acf_rerank_mmr(const float* T, int64_t num_rows, int32_t dim, const int32_t* cand, const float* rel, int32_t n,
+                   int32_t m, int32_t k_out, float lam, int32_t metric, int32_t* items, float* rel_out, float* obj,
+                   int32_t check, void* stream);
+
 /* ---- certified ranking robustness: worst-case positions under an eps attack --
  * (no reference counterpart.)  Entry r (row users[r] of P; any order, repeats
  * allowed) has the test item t = test_items[r] and the candidates C_r =
