@@ -42,7 +42,9 @@ LIBS = {
     "neumf": {"lib": f"{PKG}/lib/libacf_neumf.so",
               "srcs": [f"{PKG}/csrc/acf_neumf.hip", f"{PKG}/csrc/acf_keras_mf.hip"],
               "headers": ["include/acf_apr.h", "include/acf_neumf.h", f"{PKG}/csrc/acf_host.h",
-                          f"{PKG}/csrc/acf_neumf_adam.h", f"{PKG}/csrc/acf_topk_select.h"]},
+                          f"{PKG}/csrc/acf_neumf_adam.h", f"{PKG}/csrc/acf_topk_select.h",
+                          f"{PKG}/csrc/acf_neumf_step.h", f"{PKG}/csrc/acf_neumf_rank.h",
+                          f"{PKG}/csrc/acf_neumf_lazy.h"]},
     "torch": {"lib": f"{PKG}/lib/libacf_torch.so",
               "srcs": [f"{PKG}/csrc/acf_torch.cpp"],
               "headers": ["include/acf_apr.h"]},

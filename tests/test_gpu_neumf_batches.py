@@ -1,7 +1,7 @@
 """libacf_neumf.so above 1,024 instances per batch and at the dims that are no
 power of two, against the float64 autograd of the same graph (tests/neumf_ref.py).
 
-The regimes (thresholds in csrc/acf_neumf.hip):
+The regimes (thresholds in csrc/acf_neumf_step.h):
   B <= 1,024 (FR_MAXB)   rows in line (k_nmf_step / k_nmf_inst<.., true>)
   B >  1,024             k_nmf_inst<0>, k_nmf_rows, k_nmf_inst<1> with the clean
                          pass's weight-gradient workgroups, k_nmf_rows; the second

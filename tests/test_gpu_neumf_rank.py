@@ -16,7 +16,7 @@ from conftest import PKG
 pytestmark = pytest.mark.gpu
 
 U1, I1, NE = 37, 1003, 53  # user rows, item rows, entries of `users`
-# The kernel's constants the two-strip case relies on (acf_neumf.hip): strips are cut
+# The kernel's constants the two-strip case relies on (acf_neumf_rank.h): strips are cut
 # down to RK_STRIP_MIN = 4,096 candidates while users x strips < RK_TARGET_WG = 1,024,
 # and a block is MR = 16 candidates: 53 users x 5,003 candidates -> 2 strips of 2,512
 # and 2,491 candidates, the last block of the second holding 11.
