@@ -4006,11 +4006,11 @@ static int sample_epoch(const int32_t* pu, const int32_t* pi, int64_t n_pos, int
                         int32_t num_lists, const int64_t* loff, const int32_t* litems, uint64_t seed,
                         int32_t max_tries, int32_t check, const float* prob, const int32_t* alias, int32_t* ou,
                         int32_t* op, int32_t* on, void* stream_) {
-  ACF_CHECK(pu && pi && loff && ou && op && on, ACF_E_INVALID, "NULL argument");
   ACF_CHECK(B > 0 && num_items > 0 && n_pos >= 0 && n_pos < (1ll << 31), ACF_E_INVALID,
             "bad sizes");
   const int64_t n_out = (n_pos / B) * B;
-  if (n_out == 0) return ACF_OK;
+  if (n_out == 0) return ACF_OK;  // an empty epoch (APR.py:52, zero batches): zero-length arrays may be NULL
+  ACF_CHECK(pu && pi && loff && ou && op && on, ACF_E_INVALID, "NULL argument");
   hipStream_t s = static_cast<hipStream_t>(stream_);
   uint64_t *k_in = nullptr, *k_out = nullptr;
   int32_t *v_in = nullptr, *v_out = nullptr, *err = nullptr;
@@ -4055,8 +4055,9 @@ extern "C" int acf_dns_select(const float* P, const float* Q, int64_t U1, int64_
                               const int32_t* u, const int32_t* cand, int64_t n, int32_t dns,
                               int32_t* out, void* stream_) {
   ACF_RET(check_dim(d));
-  ACF_CHECK(P && Q && u && cand && out && dns > 0, ACF_E_INVALID, "bad argument");
-  if (n <= 0) return ACF_OK;
+  ACF_CHECK(P && Q && dns > 0, ACF_E_INVALID, "bad argument");
+  if (n <= 0) return ACF_OK;  // no triplets: zero-length arrays may be NULL
+  ACF_CHECK(u && cand && out, ACF_E_INVALID, "bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream_);
   ACF_RET(DISPATCH_GEOM(d, launch_dns, P, Q, d, u, cand, n, dns, out, s));
   HIP_TRY(hipGetLastError());
