@@ -228,6 +228,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
   at::Tensor loss = at::empty({n}, P.options()), x = at::empty({n}, P.options());
   at::Tensor pi = at::empty({2 * n}, u.options()), qi = at::empty({2 * n}, u.options());
   at::Tensor pv = at::empty({2 * n, d}, P.options()), qv = at::empty({2 * n, d}, P.options());
+  if (n == 0) return {loss, x, pi, pv, qi, qv};  // empty tensors have no storage: NULL to the C ABI
   ok(acf_gather_bpr_fwd_bwd(P.data_ptr<float>(), Q.data_ptr<float>(), P.size(0), Q.size(0), (int32_t)d,
                             u.data_ptr<int32_t>(), i.data_ptr<int32_t>(), j.data_ptr<int32_t>(), n, (float)clip_lo,
                             (float)clip_hi, loss.data_ptr<float>(), x.data_ptr<float>(), pi.data_ptr<int32_t>(),
@@ -249,6 +250,9 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> row_segment_sum(const at::Tensor&
     TORCH_CHECK(std::get<0>(mm).item<int32_t>() >= 0 && std::get<1>(mm).item<int32_t>() < num_rows,
                 "row_segment_sum: an index is outside [0, ", num_rows, ")");
   }
+  TORCH_CHECK(num_rows > 0 && num_rows <= (1ll << 31), "row_segment_sum: num_rows outside (0, 2^31]");
+  if (m == 0)  // empty tensors have no storage: NULL to the C ABI
+    return {at::empty({0}, idx.options()), at::empty({0, d}, vals.options()), at::empty({0}, idx.options())};
   size_t ws = 0;
   ok(acf_row_segment_sum_workspace(m, &ws), "acf_row_segment_sum_workspace");
   at::Tensor work = at::empty({(int64_t)ws}, vals.options().dtype(at::kByte));
@@ -266,7 +270,10 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> row_segment_sum(const at::Tensor&
 at::Tensor l2norm_perturb(const at::Tensor& g, double eps) {
   need(g, "g_rows", at::kFloat, 2);
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(g.device());
+  const int64_t d = g.size(1);
+  TORCH_CHECK(d >= 4 && d <= 1024 && d % 4 == 0, "g_rows: dim must be a multiple of 4 in [4, 1024], got ", d);
   at::Tensor out = at::empty_like(g);
+  if (g.size(0) == 0) return out;  // an empty tensor has no storage: NULL to the C ABI
   ok(acf_l2norm_perturb(g.data_ptr<float>(), g.size(0), (int32_t)g.size(1), (float)eps, out.data_ptr<float>(),
                         stream_of(g)),
      "acf_l2norm_perturb");
@@ -282,6 +289,7 @@ void sparse_adagrad_apply(at::Tensor& W, at::Tensor& acc, const at::Tensor& idx_
   at::Tensor idx = idx32(idx_, "unique indices", W);
   TORCH_CHECK(g.size(0) == idx.numel() && g.size(1) == W.size(1), "g_rows must be [len(indices), dim]");
   check_range(idx, W.size(0), "unique indices");
+  if (idx.numel() == 0) return;  // empty tensors have no storage: NULL to the C ABI
   ok(acf_sparse_adagrad_apply(W.data_ptr<float>(), acc.data_ptr<float>(), W.size(0), (int32_t)W.size(1),
                               idx.data_ptr<int32_t>(), g.data_ptr<float>(), idx.numel(), (float)lr, stream_of(W)),
      "acf_sparse_adagrad_apply");
