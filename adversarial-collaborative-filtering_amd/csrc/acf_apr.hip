@@ -946,9 +946,9 @@ struct RawRow {
   u64 x[NV][4];
 };
 
+// (the caller tests the lane's need bit: a row is issued and checked only where it is still waited for)
 template <int LPR, int NV>
-__device__ __forceinline__ void issue_row(VSrc s, int d, int l, bool ok, RawRow<NV>& w, RowV<NV>& r) {
-  if (ok) return;
+__device__ __forceinline__ void issue_row(VSrc s, int d, int l, RawRow<NV>& w, RowV<NV>& r) {
   if (!(s & 1ull)) {  // table row: nothing writes it in this launch
     const float* p = reinterpret_cast<const float*>((uintptr_t)s);
 #pragma unroll
@@ -977,14 +977,10 @@ __device__ __forceinline__ void issue_row(VSrc s, int d, int l, bool ok, RawRow<
   }
 }
 
+// true: the row is there (a table row always is)
 template <int LPR, int NV>
-__device__ __forceinline__ void check_row(VSrc s, int d, int l, uint32_t tag, const RawRow<NV>& w, RowV<NV>& r,
-                                          bool& ok) {
-  if (ok) return;
-  if (!(s & 1ull)) {
-    ok = true;
-    return;
-  }
+__device__ __forceinline__ bool check_row(VSrc s, int d, int l, uint32_t tag, const RawRow<NV>& w, RowV<NV>& r) {
+  if (!(s & 1ull)) return true;
   bool all = true;
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
@@ -998,24 +994,26 @@ __device__ __forceinline__ void check_row(VSrc s, int d, int l, uint32_t tag, co
       r.v[v] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
   }
-  ok = all;
+  return all;
 }
 
-// Wait until every listed row is there (ok[k] true on entry: not needed).
+// Wait until every listed row is there.  need: bit k set = this lane still waits
+// for row k.  The per-lane state of a wait is this one word in a vector register,
+// tested where a row is issued and checked (as K separate bools every row's
+// state was a 64-bit lane mask held, and spilled, in the scalar file across the
+// whole wait).
 template <int LPR, int NV, int K, bool GEN>
 __device__ __forceinline__ void poll_rows(const StreamArgs& a, const VSrc (&s)[K], RowV<NV>* const (&r)[K],
-                                          bool (&ok)[K], uint32_t tag, int l) {
+                                          uint32_t need, uint32_t tag, int l) {
   for (int it = 0;; ++it) {
     RawRow<NV> w[K];
 #pragma unroll
-    for (int k = 0; k < K; ++k) issue_row<LPR, NV>(s[k], a.d, l, ok[k], w[k], *r[k]);
-    bool all = true;
+    for (int k = 0; k < K; ++k)
+      if (need & (1u << k)) issue_row<LPR, NV>(s[k], a.d, l, w[k], *r[k]);
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-      check_row<LPR, NV>(s[k], a.d, l, tag, w[k], *r[k], ok[k]);
-      all = all && ok[k];
-    }
-    if (wait_round<GEN>(a, all, it)) break;
+    for (int k = 0; k < K; ++k)
+      if ((need & (1u << k)) && check_row<LPR, NV>(s[k], a.d, l, tag, w[k], *r[k])) need &= ~(1u << k);
+    if (wait_round<GEN>(a, need == 0, it)) break;
   }
 }
 
@@ -1031,8 +1029,7 @@ __device__ __forceinline__ void stream_partners(const StreamArgs& a, int32_t t, 
   const VSrc sb1 = a1 ? ver_src(a, t, a.Q, a.ver_w, r1.pb_row(), r1.pb_src()) : 0;
   const VSrc src[4] = {sa0, sb0, sa1, sb1};
   RowV<NV>* const dst[4] = {&ra0, &rb0, &ra1, &rb1};
-  bool ok[4] = {!a0, !a0, !a1, !a1};
-  poll_rows<LPR, NV, 4, GEN>(a, src, dst, ok, tag, l);
+  poll_rows<LPR, NV, 4, GEN>(a, src, dst, (a0 ? 3u : 0u) | (a1 ? 12u : 0u), tag, l);
 }
 
 // make_delta of the streamed step: the default instance forms the gradient delta
@@ -1088,13 +1085,76 @@ __device__ __forceinline__ RowV<NV> solo_delta(const StreamArgs& a, int32_t t, i
   return stream_delta<LPR, NV, GEN>(a, t, G, p_item, pb ? r.pb_row() : r.pa_row(), l);
 }
 
+// Deltas of BOTH items of a user occurrence (own = p_u; di: item i, dj: item j),
+// the gradient delta only (l2_delta; a random delta is keyed on the row id and
+// keeps one solo_delta per partner).  solo_delta forms G_i = 0 + gb p and
+// G_j = 0 + (-gb) p.  (-gb) p is the exact negation of gb p, so an element of G_j
+// is the negation of G_i's, or +0 in both where the product is a zero of either
+// sign (0 + (+-0) = +0).  The team additions of +0 keep both.  dot_row(G, G) sums
+// the same squares in the same order, so inv is the same number, and the two
+// rounded products (G inv) eps of a negated element are the negated products: a
+// sign flip, also where a product underflows to a zero.  Where G_i's element is
+// +0, so is G_j's, and both deltas are the same zero.  Hence dj = G_i != 0 ? -di
+// : di, bit for bit (0.0f - di wherever di != 0), and the second axpy -> team
+// adds -> norm -> rsq -> two scales chain is not run.  Which of the two is used
+// stays each lane's own choice (sa / sb at the caller), so a wave in which one
+// lane-group has both partners solo and another has one keeps exact results.
+template <int LPR, int NV, int TEAM>
+__device__ __forceinline__ void solo_delta_user_pair(const StreamArgs& a, const RowV<NV>& own, const RowV<NV>& ra,
+                                                     const RowV<NV>& rb, const float* gk, RowV<NV>& di,
+                                                     RowV<NV>& dj) {
+  float gb, loss;
+  if (gk) gb = *gk;
+  else bpr_term(dot_row<LPR, NV>(own, ra) - dot_row<LPR, NV>(own, rb), a.clip_lo, a.clip_hi, gb, loss);
+  RowV<NV> G = zero_row<NV>();
+  axpy_row(G, gb, own);
+#pragma unroll
+  for (int s = 1; s < TEAM; s <<= 1) G = add_row(G, zero_row<NV>());
+  di = l2_delta<LPR, NV>(G, a.eps);
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    dj.v[v].x = G.v[v].x != 0.f ? -di.v[v].x : di.v[v].x;
+    dj.v[v].y = G.v[v].y != 0.f ? -di.v[v].y : di.v[v].y;
+    dj.v[v].z = G.v[v].z != 0.f ? -di.v[v].z : di.v[v].z;
+    dj.v[v].w = G.v[v].w != 0.f ? -di.v[v].w : di.v[v].w;
+  }
+}
+
+// The solo partners' deltas of one occurrence (sa / sb: this lane's pa / pb is solo)
+template <int LPR, int NV, int TEAM, bool GEN>
+__device__ __forceinline__ void solo_deltas(const StreamArgs& a, int32_t t, int is_item, const RowV<NV>& own,
+                                            const RecV& r, const RowV<NV>& ra, const RowV<NV>& rb, bool sa,
+                                            bool sb, int l, const float* gk, RowV<NV>& da, RowV<NV>& db) {
+  if constexpr (!GEN) {
+    if (!is_item) {  // wave-uniform
+      if (__any(sa || sb)) {
+        RowV<NV> xi, xj;
+        solo_delta_user_pair<LPR, NV, TEAM>(a, own, ra, rb, gk, xi, xj);
+        if (sa) da = xi;
+        if (sb) db = xj;
+      }
+      return;
+    }
+  }
+  if (__any(sa)) {
+    const RowV<NV> x = solo_delta<LPR, NV, TEAM, GEN>(a, t, is_item, own, r, ra, rb, 0, l, gk);
+    if (sa) da = x;
+  }
+  if (__any(sb)) {
+    const RowV<NV> x = solo_delta<LPR, NV, TEAM, GEN>(a, t, is_item, own, r, ra, rb, 1, l, gk);
+    if (sb) db = x;
+  }
+}
+
 // Adversarial terms of one pass: partner rows (batch-start values) plus their
 // deltas: formed here for a solo partner, otherwise the one its clean half
-// publishes in this batch (wait for it).
-template <int LPR, int NV, int TEAM, bool GEN>
+// publishes in this batch (wait for it).  TWO = false: no member has a second
+// occurrence (the slot has at most TEAM), and r1 / a1 / ra1 / rb1 / g1 / x1 are
+// not read; TWO = true: two (wave-uniform) says whether any member has one.
+template <int LPR, int NV, int TEAM, bool GEN, bool TWO>
 __device__ __forceinline__ void stream_adv_pass(const StreamArgs& a, int32_t t, int is_item, const RowV<NV>& own,
                                                 const RowV<NV>& ownp, const RecV& r0, const RecV& r1, bool a0,
-                                                bool a1, RowV<NV> ra0, RowV<NV> rb0, RowV<NV> ra1,
+                                                bool a1, bool two, RowV<NV> ra0, RowV<NV> rb0, RowV<NV> ra1,
                                                 RowV<NV> rb1, uint32_t tag, int l, RowV<NV>& GA,
                                                 int k = 0,  // k: diagnostic stamps only
                                                 const float* g0 = nullptr, const float* g1 = nullptr,
@@ -1102,42 +1162,37 @@ __device__ __forceinline__ void stream_adv_pass(const StreamArgs& a, int32_t t, 
                                                 float* x0 = nullptr, float* x1 = nullptr) {
   RowV<NV> da0 = zero_row<NV>(), db0 = da0, da1 = da0, db1 = da0;
   const bool sa0 = a0 && r0.pa_solo(), sb0 = a0 && r0.pb_solo();
-  const bool sa1 = a1 && r1.pa_solo(), sb1 = a1 && r1.pb_solo();
   const VSrc ta0 = a0 && !sa0 ? ver_at(vrow(a.ver_d, a, t, r0.pa_slot())) : 0;
   const VSrc tb0 = a0 && !sb0 ? ver_at(vrow(a.ver_d, a, t, r0.pb_slot())) : 0;
-  const VSrc ta1 = a1 && !sa1 ? ver_at(vrow(a.ver_d, a, t, r1.pa_slot())) : 0;
-  const VSrc tb1 = a1 && !sb1 ? ver_at(vrow(a.ver_d, a, t, r1.pb_slot())) : 0;
-  bool pa0 = !ta0, pb0 = !tb0, pa1 = !ta1, pb1 = !tb1;
-  if (__any(sa0)) {
-    const RowV<NV> x = solo_delta<LPR, NV, TEAM, GEN>(a, t, is_item, own, r0, ra0, rb0, 0, l, g0);
-    if (sa0) da0 = x;
-  }
-  if (__any(sb0)) {
-    const RowV<NV> x = solo_delta<LPR, NV, TEAM, GEN>(a, t, is_item, own, r0, ra0, rb0, 1, l, g0);
-    if (sb0) db0 = x;
-  }
-  if (__any(sa1)) {
-    const RowV<NV> x = solo_delta<LPR, NV, TEAM, GEN>(a, t, is_item, own, r1, ra1, rb1, 0, l, g1);
-    if (sa1) da1 = x;
-  }
-  if (__any(sb1)) {
-    const RowV<NV> x = solo_delta<LPR, NV, TEAM, GEN>(a, t, is_item, own, r1, ra1, rb1, 1, l, g1);
-    if (sb1) db1 = x;
-  }
-  STAMP(t, k, 6);
-  {
+  solo_deltas<LPR, NV, TEAM, GEN>(a, t, is_item, own, r0, ra0, rb0, sa0, sb0, l, g0, da0, db0);
+  if constexpr (TWO) {
+    const bool sa1 = a1 && r1.pa_solo(), sb1 = a1 && r1.pb_solo();
+    const VSrc ta1 = a1 && !sa1 ? ver_at(vrow(a.ver_d, a, t, r1.pa_slot())) : 0;
+    const VSrc tb1 = a1 && !sb1 ? ver_at(vrow(a.ver_d, a, t, r1.pb_slot())) : 0;
+    if (two) solo_deltas<LPR, NV, TEAM, GEN>(a, t, is_item, own, r1, ra1, rb1, sa1, sb1, l, g1, da1, db1);
+    STAMP(t, k, 6);
     const VSrc src[4] = {ta0, tb0, ta1, tb1};
     RowV<NV>* const dst[4] = {&da0, &db0, &da1, &db1};
-    bool ok[4] = {pa0, pb0, pa1, pb1};
-    poll_rows<LPR, NV, 4, GEN>(a, src, dst, ok, tag, l);
+    const uint32_t need = (a0 && !sa0 ? 1u : 0u) | (a0 && !sb0 ? 2u : 0u) | (a1 && !sa1 ? 4u : 0u) |
+                          (a1 && !sb1 ? 8u : 0u);
+    poll_rows<LPR, NV, 4, GEN>(a, src, dst, need, tag, l);
+  } else {
+    STAMP(t, k, 6);
+    const VSrc src[2] = {ta0, tb0};
+    RowV<NV>* const dst[2] = {&da0, &db0};
+    poll_rows<LPR, NV, 2, GEN>(a, src, dst, (a0 && !sa0 ? 1u : 0u) | (a0 && !sb0 ? 2u : 0u), tag, l);
   }
   STAMP(t, k, 7);
   ra0 = add_row(ra0, da0);
   rb0 = add_row(rb0, db0);
-  ra1 = add_row(ra1, da1);
-  rb1 = add_row(rb1, db1);
   occ_term<LPR, NV>(a, is_item, ownp, r0, ra0, rb0, a0, l, a.loss_adv, GA, nullptr, nullptr, x0);
-  if (__any(a1)) occ_term<LPR, NV>(a, is_item, ownp, r1, ra1, rb1, a1, l, a.loss_adv, GA, nullptr, nullptr, x1);
+  if constexpr (TWO) {
+    if (two) {
+      ra1 = add_row(ra1, da1);
+      rb1 = add_row(rb1, db1);
+      occ_term<LPR, NV>(a, is_item, ownp, r1, ra1, rb1, a1, l, a.loss_adv, GA, nullptr, nullptr, x1);
+    }
+  }
 }
 
 // One unique row of batch a.t: clean half (utils.py:117, APR.py:180-191), its
@@ -1186,7 +1241,8 @@ __device__ __forceinline__ HotSums<NV> stream_slot_hot(const StreamArgs& a, int3
     RowV<NV> xa0 = zero_row<NV>(), xb0 = xa0, xa1 = xa0, xb1 = xa0;
     stream_partners<LPR, NV, GEN>(a, t, h.is_item, q0, q1, b0, b1, tag, l, xa0, xb0, xa1, xb1);
     occ_term<LPR, NV>(a, h.is_item, own, q0, xa0, xb0, b0, l, a.loss_clean, G);
-    if (__any(b1)) occ_term<LPR, NV>(a, h.is_item, own, q1, xa1, xb1, b1, l, a.loss_clean, G);
+    // some member has a second occurrence in this pass: a scalar compare (h.count is wave-uniform)
+    if (base + TEAM < h.count) occ_term<LPR, NV>(a, h.is_item, own, q1, xa1, xb1, b1, l, a.loss_clean, G);
   }
   const RowV<NV> ownp = stream_finish_clean<LPR, NV, TEAM, GEN>(a, t, h, k, m, l, tag, own, G);
   for (int base = 0; base < h.count; base += 2 * TEAM) {
@@ -1197,56 +1253,63 @@ __device__ __forceinline__ HotSums<NV> stream_slot_hot(const StreamArgs& a, int3
     if (b1) q1 = occ_rec_mem(a, t, h, k, i1);
     RowV<NV> xa0 = zero_row<NV>(), xb0 = xa0, xa1 = xa0, xb1 = xa0;
     stream_partners<LPR, NV, GEN>(a, t, h.is_item, q0, q1, b0, b1, tag, l, xa0, xb0, xa1, xb1);
-    stream_adv_pass<LPR, NV, TEAM, GEN>(a, t, h.is_item, own, ownp, q0, q1, b0, b1, xa0, xb0, xa1, xb1, tag, l, o.GA);
+    stream_adv_pass<LPR, NV, TEAM, GEN, true>(a, t, h.is_item, own, ownp, q0, q1, b0, b1, base + TEAM < h.count, xa0,
+                                              xb0, xa1, xb1, tag, l, o.GA);
   }
   o.G = G;
   return o;
 }
 
-template <int LPR, int NV, int TEAM, bool GEN>
-__device__ __forceinline__ void stream_slot(const StreamArgs& a, int32_t t, int k, int m, int l, int leader,
-                                            uint32_t tag) {
-  STAMP(t, k, 0);
-  const SlotRec sr = slot_header_at<LPR, TEAM>(a, t, GEN ? a.use_single : 1, k, m, leader);
+// TWO = false is the instance for a slot of at most TEAM occurrences (the median
+// slot has one or two): no member has a second occurrence, so r1, its partner
+// rows, its two polled rows in each wait, its solo deltas and its terms are not
+// in the code at all.  TWO = true: TEAM < count, so member 0 has a second
+// occurrence and the tests "does any member have one" are true by construction.
+template <int LPR, int NV, int TEAM, bool GEN, bool TWO>
+__device__ __forceinline__ void stream_slot_body(const StreamArgs& a, int32_t t, const SlotRec& sr, int k, int m,
+                                                 int l, uint32_t tag) {
   const SlotHdr& h = sr.h;
-  if (h.count == 0) return;
-  STAMP(t, k, 1);
   const int d = a.d;
+  // own and the Adagrad slot are versions in every lane or table rows in every
+  // lane (the header is wave-uniform); only member 0 reads the Adagrad slot (its need bit)
   const VSrc own_s = ver_src(a, t, h.is_item ? a.Q : a.P, a.ver_w, h.own_row, h.own_src);
-  const VSrc acc_s = m == 0 ? ver_src(a, t, h.is_item ? a.accQ : a.accP, a.ver_a, h.own_row, h.own_src) : 0;
+  const VSrc acc_s = ver_src(a, t, h.is_item ? a.accQ : a.accP, a.ver_a, h.own_row, h.own_src);
   RowV<NV> own = zero_row<NV>(), acc = own, G = own;
   RowV<NV> ra0 = own, rb0 = own, ra1 = own, rb1 = own;
   RecV r0, r1;
-  bool a0 = false, a1 = false;
   // a user occurrence's clipped arguments (clean, adversarial): its losses are
   // evaluated behind the task's version stores, which is where the next batch waits
   float xc0 = 0.f, xc1 = 0.f, xa0 = 0.f, xa1 = 0.f, gc0 = 0.f, gc1 = 0.f;
+  const bool a0 = m < h.count;
+  const bool a1 = TWO && TEAM + m < h.count;
   {  // first pass: own row, Adagrad slot, partners in one wait
-    a0 = m < h.count;
-    a1 = TEAM + m < h.count;
     if (a0) r0 = occ_rec<TEAM>(a, sr, m, m);
-    if (a1) r1 = occ_rec<TEAM>(a, sr, TEAM + m, m);
     const float* ptab = h.is_item ? a.P : a.Q;
     const VSrc sa0 = a0 ? ver_src(a, t, ptab, a.ver_w, r0.pa_row(), r0.pa_src()) : 0;
     const VSrc sb0 = a0 ? ver_src(a, t, a.Q, a.ver_w, r0.pb_row(), r0.pb_src()) : 0;
-    const VSrc sa1 = a1 ? ver_src(a, t, ptab, a.ver_w, r1.pa_row(), r1.pa_src()) : 0;
-    const VSrc sb1 = a1 ? ver_src(a, t, a.Q, a.ver_w, r1.pb_row(), r1.pb_src()) : 0;
-    {
+    const uint32_t need0 = 1u | (m == 0 ? 2u : 0u) | (a0 ? 12u : 0u);
+    if constexpr (TWO) {
+      if (a1) r1 = occ_rec<TEAM>(a, sr, TEAM + m, m);
+      const VSrc sa1 = a1 ? ver_src(a, t, ptab, a.ver_w, r1.pa_row(), r1.pa_src()) : 0;
+      const VSrc sb1 = a1 ? ver_src(a, t, a.Q, a.ver_w, r1.pb_row(), r1.pb_src()) : 0;
       const VSrc src[6] = {own_s, acc_s, sa0, sb0, sa1, sb1};
       RowV<NV>* const dst[6] = {&own, &acc, &ra0, &rb0, &ra1, &rb1};
-      bool ok[6] = {false, m != 0, !a0, !a0, !a1, !a1};
-      poll_rows<LPR, NV, 6, GEN>(a, src, dst, ok, tag, l);
+      poll_rows<LPR, NV, 6, GEN>(a, src, dst, need0 | (a1 ? 48u : 0u), tag, l);
+    } else {
+      const VSrc src[4] = {own_s, acc_s, sa0, sb0};
+      RowV<NV>* const dst[4] = {&own, &acc, &ra0, &rb0};
+      poll_rows<LPR, NV, 4, GEN>(a, src, dst, need0, tag, l);
     }
     STAMP(t, k, 2);
     occ_term<LPR, NV>(a, h.is_item, own, r0, ra0, rb0, a0, l, a.loss_clean, G, nullptr, &gc0, &xc0);
-    if (__any(a1)) occ_term<LPR, NV>(a, h.is_item, own, r1, ra1, rb1, a1, l, a.loss_clean, G, nullptr, &gc1, &xc1);
+    if constexpr (TWO) occ_term<LPR, NV>(a, h.is_item, own, r1, ra1, rb1, a1, l, a.loss_clean, G, nullptr, &gc1, &xc1);
   }
   RowV<NV> GA = zero_row<NV>();
-  const bool one_pass = h.count <= 2 * TEAM;  // wave-uniform
+  const bool one_pass = !TWO || h.count <= 2 * TEAM;  // wave-uniform
   if (one_pass) {  // partner rows kept for the adversarial half
     const RowV<NV> ownp = stream_finish_clean<LPR, NV, TEAM, GEN>(a, t, h, k, m, l, tag, own, G);
-    stream_adv_pass<LPR, NV, TEAM, GEN>(a, t, h.is_item, own, ownp, r0, r1, a0, a1, ra0, rb0, ra1, rb1, tag, l, GA, k,
-                                        &gc0, &gc1, &xa0, &xa1);
+    stream_adv_pass<LPR, NV, TEAM, GEN, TWO>(a, t, h.is_item, own, ownp, r0, r1, a0, a1, true, ra0, rb0, ra1, rb1, tag,
+                                             l, GA, k, &gc0, &gc1, &xa0, &xa1);
   } else {  // a hot row: its adversarial losses are stored in there, pass by pass
     const HotSums<NV> o = stream_slot_hot<LPR, NV, TEAM, GEN>(a, t, h, k, m, l, tag, own, G);
     G = o.G;
@@ -1266,13 +1329,25 @@ __device__ __forceinline__ void stream_slot(const StreamArgs& a, int32_t t, int 
   __builtin_amdgcn_sched_barrier(0);
   if (!h.is_item && l == 0) {
     if (a0) a.loss_clean[r0.e_role()] = bpr_loss(xc0);
-    if (a1) a.loss_clean[r1.e_role()] = bpr_loss(xc1);
+    if (TWO && a1) a.loss_clean[r1.e_role()] = bpr_loss(xc1);
     if (one_pass) {
       if (a0) a.loss_adv[r0.e_role()] = bpr_loss(xa0);
-      if (a1) a.loss_adv[r1.e_role()] = bpr_loss(xa1);
+      if (TWO && a1) a.loss_adv[r1.e_role()] = bpr_loss(xa1);
     }
   }
   STAMP(t, k, 5);
+}
+
+template <int LPR, int NV, int TEAM, bool GEN>
+__device__ __forceinline__ void stream_slot(const StreamArgs& a, int32_t t, int k, int m, int l, int leader,
+                                            uint32_t tag) {
+  STAMP(t, k, 0);
+  const SlotRec sr = slot_header_at<LPR, TEAM>(a, t, GEN ? a.use_single : 1, k, m, leader);
+  if (sr.h.count == 0) return;
+  STAMP(t, k, 1);
+  // count comes from v_readlane: a scalar compare picks the instance
+  if (sr.h.count <= TEAM) stream_slot_body<LPR, NV, TEAM, GEN, false>(a, t, sr, k, m, l, tag);
+  else stream_slot_body<LPR, NV, TEAM, GEN, true>(a, t, sr, k, m, l, tag);
 }
 
 // A fused triplet of batch a.t (k_single's APR sequence): rows and Adagrad
@@ -1296,8 +1371,7 @@ __device__ __forceinline__ void stream_single(const StreamArgs& a, int32_t t, in
   {
     const VSrc src[6] = {su, si, sj, cu_s, ci_s, cj_s};
     RowV<NV>* const dst[6] = {&p, &qi, &qj, &cu, &ci, &cj};
-    bool ok[6] = {!act, !act, !act, !act, !act, !act};
-    poll_rows<LPR, NV, 6, GEN>(a, src, dst, ok, tag, l);
+    poll_rows<LPR, NV, 6, GEN>(a, src, dst, act ? 63u : 0u, tag, l);
   }
   if (!act) return;
   // the two losses are functions of the clipped arguments alone (bpr_term =
