@@ -259,6 +259,19 @@ struct StreamArgs {
   static constexpr int32_t adver = 1;  // the streamed step is the APR step (use_stream)
 };
 
+// StreamArgs as the full-row instance of k_stream reads them: d == W = 4 LPR NV
+// (the host launches it for no other d), so the width is a constant there.  Same
+// layout; the field d stays what the host set, for the code that takes the base
+// (the tail, the waits' ends).  With W folded, every `c * 4 < d` lane test and the
+// zero-fill of padded lanes go (no lane is padded), and the four granules of a row
+// are one address and three immediate offsets (d/4 was a run-time stride: four
+// 64-bit address pairs per polled row, a lane mask and a saved exec mask per
+// guarded load).
+template <int W>
+struct StreamArgsFull : StreamArgs {
+  static constexpr int32_t d = W;
+};
+
 // An OccRec as three int4 registers (kept in VGPRs; a struct of scalars passed
 // by reference got demoted to scratch).  Field order as in OccRec.
 struct RecV {
@@ -861,7 +874,8 @@ __device__ __forceinline__ const u64* vrow(const u64* base, const StepArgs& a, i
 
 // the same row through k_stream's precomputed stride: one 32 x 32 -> 64 multiply-add
 // (k * d < S * d = Sd fits 31 bits)
-__device__ __forceinline__ const u64* vrow(const u64* base, const StreamArgs& a, int32_t t, int32_t k) {
+template <class A>
+__device__ __forceinline__ const u64* vrow(const u64* base, const A& a, int32_t t, int32_t k) {
   return base + ((int64_t)t * a.Sd + k * a.d);
 }
 
@@ -870,7 +884,8 @@ __device__ __forceinline__ const u64* vrow(const u64* base, const StreamArgs& a,
 // earlier batch of this launch)
 typedef uint64_t VSrc;
 
-__device__ __forceinline__ VSrc ver_src(const StreamArgs& a, int32_t t, const float* table, const u64* vbase,
+template <class A>
+__device__ __forceinline__ VSrc ver_src(const A& a, int32_t t, const float* table, const u64* vbase,
                                         int32_t row, int32_t src) {
   if (src < 0) {
     const int32_t tp = t - src_dt(src, a.kb);
@@ -946,23 +961,27 @@ struct RawRow {
   u64 x[NV][4];
 };
 
+// a table row (s even): nothing writes it in this launch, so it is read once,
+// straight into the row, and never polled
+template <int LPR, int NV>
+__device__ __forceinline__ void load_table_row(VSrc s, int d, int l, RowV<NV>& r) {
+  const float* p = reinterpret_cast<const float*>((uintptr_t)s);
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    const int c = l + LPR * v;
+    if (c * 4 < d) {
+      const f32x4 x = *(gf4_ptr)(p + c * 4);
+      r.v[v] = make_float4(x[0], x[1], x[2], x[3]);
+    } else {
+      r.v[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+}
+
+// one attempt at a version row (s odd), first half: the loads of its granules
 // (the caller tests the lane's need bit: a row is issued and checked only where it is still waited for)
 template <int LPR, int NV>
-__device__ __forceinline__ void issue_row(VSrc s, int d, int l, RawRow<NV>& w, RowV<NV>& r) {
-  if (!(s & 1ull)) {  // table row: nothing writes it in this launch
-    const float* p = reinterpret_cast<const float*>((uintptr_t)s);
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      const int c = l + LPR * v;
-      if (c * 4 < d) {
-        const f32x4 x = *(gf4_ptr)(p + c * 4);
-        r.v[v] = make_float4(x[0], x[1], x[2], x[3]);
-      } else {
-        r.v[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    }
-    return;
-  }
+__device__ __forceinline__ void issue_row(VSrc s, int d, int l, RawRow<NV>& w) {
   const u64* base = reinterpret_cast<const u64*>((uintptr_t)(s & ~1ull));
   const int d4 = d >> 2;
 #pragma unroll
@@ -977,10 +996,9 @@ __device__ __forceinline__ void issue_row(VSrc s, int d, int l, RawRow<NV>& w, R
   }
 }
 
-// true: the row is there (a table row always is)
+// second half: the tags' test.  true: the row is there
 template <int LPR, int NV>
-__device__ __forceinline__ bool check_row(VSrc s, int d, int l, uint32_t tag, const RawRow<NV>& w, RowV<NV>& r) {
-  if (!(s & 1ull)) return true;
+__device__ __forceinline__ bool check_row(int d, int l, uint32_t tag, const RawRow<NV>& w, RowV<NV>& r) {
   bool all = true;
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
@@ -1002,24 +1020,47 @@ __device__ __forceinline__ bool check_row(VSrc s, int d, int l, uint32_t tag, co
 // tested where a row is issued and checked (as K separate bools every row's
 // state was a 64-bit lane mask held, and spilled, in the scalar file across the
 // whole wait).
-template <int LPR, int NV, int K, bool GEN>
-__device__ __forceinline__ void poll_rows(const StreamArgs& a, const VSrc (&s)[K], RowV<NV>* const (&r)[K],
+//
+// Table rows leave the wait in front of it: a row is a table row only the first
+// time the launch touches it (about 2% of the occurrences of a 647-batch chunk),
+// so the common wave skips the block with one scalar branch, and the attempts see
+// versions only.  (Told apart inside issue_row / check_row, the lane-divergent
+// `s & 1` cost two exec-mask levels per row per attempt and a lane mask per row
+// across the wait, and the table branch's load drained the loads of the rows
+// before it: its destination is the row itself.)  The table loads are not waited
+// for here: they are in flight beside the first attempt's version loads.
+// TABLES = false: every source is a version (the deltas of a batch).
+template <int LPR, int NV, int K, bool GEN, bool TABLES = true, class A>
+__device__ __forceinline__ void poll_rows(const A& a, const VSrc (&s)[K], RowV<NV>* const (&r)[K],
                                           uint32_t need, uint32_t tag, int l) {
+  if constexpr (TABLES) {
+    uint32_t tab = 0;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      if (!(s[k] & 1ull)) tab |= 1u << k;
+    tab &= need;
+    if (__any(tab != 0)) {
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        if (tab & (1u << k)) load_table_row<LPR, NV>(s[k], a.d, l, *r[k]);
+      need &= ~tab;
+    }
+  }
   for (int it = 0;; ++it) {
     RawRow<NV> w[K];
 #pragma unroll
     for (int k = 0; k < K; ++k)
-      if (need & (1u << k)) issue_row<LPR, NV>(s[k], a.d, l, w[k], *r[k]);
+      if (need & (1u << k)) issue_row<LPR, NV>(s[k], a.d, l, w[k]);
 #pragma unroll
     for (int k = 0; k < K; ++k)
-      if ((need & (1u << k)) && check_row<LPR, NV>(s[k], a.d, l, tag, w[k], *r[k])) need &= ~(1u << k);
+      if ((need & (1u << k)) && check_row<LPR, NV>(a.d, l, tag, w[k], *r[k])) need &= ~(1u << k);
     if (wait_round<GEN>(a, need == 0, it)) break;
   }
 }
 
 // Partner rows of the member's two occurrences of a pass (batch-start values)
-template <int LPR, int NV, bool GEN>
-__device__ __forceinline__ void stream_partners(const StreamArgs& a, int32_t t, int is_item, const RecV& r0,
+template <int LPR, int NV, bool GEN, class A>
+__device__ __forceinline__ void stream_partners(const A& a, int32_t t, int is_item, const RecV& r0,
                                                 const RecV& r1, bool a0, bool a1, uint32_t tag, int l,
                                                 RowV<NV>& ra0, RowV<NV>& rb0, RowV<NV>& ra1, RowV<NV>& rb1) {
   const float* ptab = is_item ? a.P : a.Q;
@@ -1151,8 +1192,8 @@ __device__ __forceinline__ void solo_deltas(const StreamArgs& a, int32_t t, int 
 // publishes in this batch (wait for it).  TWO = false: no member has a second
 // occurrence (the slot has at most TEAM), and r1 / a1 / ra1 / rb1 / g1 / x1 are
 // not read; TWO = true: two (wave-uniform) says whether any member has one.
-template <int LPR, int NV, int TEAM, bool GEN, bool TWO>
-__device__ __forceinline__ void stream_adv_pass(const StreamArgs& a, int32_t t, int is_item, const RowV<NV>& own,
+template <int LPR, int NV, int TEAM, bool GEN, bool TWO, class A>
+__device__ __forceinline__ void stream_adv_pass(const A& a, int32_t t, int is_item, const RowV<NV>& own,
                                                 const RowV<NV>& ownp, const RecV& r0, const RecV& r1, bool a0,
                                                 bool a1, bool two, RowV<NV> ra0, RowV<NV> rb0, RowV<NV> ra1,
                                                 RowV<NV> rb1, uint32_t tag, int l, RowV<NV>& GA,
@@ -1175,12 +1216,12 @@ __device__ __forceinline__ void stream_adv_pass(const StreamArgs& a, int32_t t, 
     RowV<NV>* const dst[4] = {&da0, &db0, &da1, &db1};
     const uint32_t need = (a0 && !sa0 ? 1u : 0u) | (a0 && !sb0 ? 2u : 0u) | (a1 && !sa1 ? 4u : 0u) |
                           (a1 && !sb1 ? 8u : 0u);
-    poll_rows<LPR, NV, 4, GEN>(a, src, dst, need, tag, l);
+    poll_rows<LPR, NV, 4, GEN, false>(a, src, dst, need, tag, l);
   } else {
     STAMP(t, k, 6);
     const VSrc src[2] = {ta0, tb0};
     RowV<NV>* const dst[2] = {&da0, &db0};
-    poll_rows<LPR, NV, 2, GEN>(a, src, dst, (a0 && !sa0 ? 1u : 0u) | (a0 && !sb0 ? 2u : 0u), tag, l);
+    poll_rows<LPR, NV, 2, GEN, false>(a, src, dst, (a0 && !sa0 ? 1u : 0u) | (a0 && !sb0 ? 2u : 0u), tag, l);
   }
   STAMP(t, k, 7);
   ra0 = add_row(ra0, da0);
@@ -1202,8 +1243,8 @@ __device__ __forceinline__ void stream_adv_pass(const StreamArgs& a, int32_t t, 
 // 2 TEAM occurrences (one pass) keeps its partner rows for the adversarial half;
 // the Adagrad slot is fetched with the first gathers.
 // the clean half's end: batch-summed gradient, delta, delta published; returns own + delta
-template <int LPR, int NV, int TEAM, bool GEN>
-__device__ __forceinline__ RowV<NV> stream_finish_clean(const StreamArgs& a, int32_t t, const SlotHdr& h, int k,
+template <int LPR, int NV, int TEAM, bool GEN, class A>
+__device__ __forceinline__ RowV<NV> stream_finish_clean(const A& a, int32_t t, const SlotHdr& h, int k,
                                                         int m, int l, uint32_t tag, const RowV<NV>& own,
                                                         RowV<NV>& Gc) {
   team_allreduce_wave<LPR, TEAM, NV>(Gc);
@@ -1226,8 +1267,8 @@ struct HotSums {
 // function it made the kernel keep what lives across the call in the callee-saved
 // registers, and the one-pass body spilled vector registers to scratch (256 VGPRs,
 // 64 B of scratch, against none in line).
-template <int LPR, int NV, int TEAM, bool GEN>
-__device__ __forceinline__ HotSums<NV> stream_slot_hot(const StreamArgs& a, int32_t t, const SlotHdr& h, int k,
+template <int LPR, int NV, int TEAM, bool GEN, class A>
+__device__ __forceinline__ HotSums<NV> stream_slot_hot(const A& a, int32_t t, const SlotHdr& h, int k,
                                                        int m, int l, uint32_t tag, const RowV<NV>& own,
                                                        RowV<NV> G) {
   HotSums<NV> o;
@@ -1265,8 +1306,8 @@ __device__ __forceinline__ HotSums<NV> stream_slot_hot(const StreamArgs& a, int3
 // rows, its two polled rows in each wait, its solo deltas and its terms are not
 // in the code at all.  TWO = true: TEAM < count, so member 0 has a second
 // occurrence and the tests "does any member have one" are true by construction.
-template <int LPR, int NV, int TEAM, bool GEN, bool TWO>
-__device__ __forceinline__ void stream_slot_body(const StreamArgs& a, int32_t t, const SlotRec& sr, int k, int m,
+template <int LPR, int NV, int TEAM, bool GEN, bool TWO, class A>
+__device__ __forceinline__ void stream_slot_body(const A& a, int32_t t, const SlotRec& sr, int k, int m,
                                                  int l, uint32_t tag) {
   const SlotHdr& h = sr.h;
   const int d = a.d;
@@ -1338,8 +1379,8 @@ __device__ __forceinline__ void stream_slot_body(const StreamArgs& a, int32_t t,
   STAMP(t, k, 5);
 }
 
-template <int LPR, int NV, int TEAM, bool GEN>
-__device__ __forceinline__ void stream_slot(const StreamArgs& a, int32_t t, int k, int m, int l, int leader,
+template <int LPR, int NV, int TEAM, bool GEN, class A>
+__device__ __forceinline__ void stream_slot(const A& a, int32_t t, int k, int m, int l, int leader,
                                             uint32_t tag) {
   STAMP(t, k, 0);
   const SlotRec sr = slot_header_at<LPR, TEAM>(a, t, GEN ? a.use_single : 1, k, m, leader);
@@ -1352,8 +1393,8 @@ __device__ __forceinline__ void stream_slot(const StreamArgs& a, int32_t t, int 
 
 // A fused triplet of batch a.t (k_single's APR sequence): rows and Adagrad
 // slots from their versions or the tables, results as versions of its 3 slots.
-template <int LPR, int NV, bool GEN>
-__device__ __forceinline__ void stream_single(const StreamArgs& a, int32_t t, int b, int l, uint32_t tag) {
+template <int LPR, int NV, bool GEN, class A>
+__device__ __forceinline__ void stream_single(const A& a, int32_t t, int b, int l, uint32_t tag) {
   const int64_t e = (int64_t)t * a.B + b;
   RecV r;
   r.a = r.b = r.c = make_int4(0, 0, 0, -1);
@@ -1583,9 +1624,12 @@ __device__ __forceinline__ void stream_tail(const StreamArgs& a, uint32_t tag, b
 // those switches folded at compile time: they are fixed for a launch, and tested
 // at run time they sat in every link of the chain of recurring rows.
 // k_stream_any (GEN) tests them as before and runs every other mode; the host
-// picks (run_streamed).  Same operations on the same values in both.
-template <int LPR, int NV, int TEAM, bool GEN>
-__device__ __forceinline__ void stream_body(const StreamArgs& a, int32_t positions) {
+// picks (run_streamed).  Same operations on the same values in both.  The default
+// mode's instance comes at two widths: k_stream for a full row (d == 4 LPR NV,
+// the width a constant: StreamArgsFull) and k_stream_pad for a padded one (d read
+// at run time, as in k_stream_any); get_kernels picks by d.
+template <int LPR, int NV, int TEAM, bool GEN, class A>
+__device__ __forceinline__ void stream_body(const A& a, int32_t positions) {
   static_assert(TEAM * LPR == 64, "k_stream: one wave per slot");
   const bool lists = GEN ? a.task_list != nullptr : true;
   unsigned long long* const tail_diag = GEN ? a.tail_diag : nullptr;
@@ -1646,7 +1690,13 @@ __device__ __forceinline__ void stream_body(const StreamArgs& a, int32_t positio
 }
 
 template <int LPR, int NV, int TEAM>
-__global__ void __launch_bounds__(256, 2) k_stream(StreamArgs a, int32_t positions) {
+__global__ void __launch_bounds__(256, 2) k_stream(StreamArgsFull<4 * LPR * NV> a, int32_t positions) {
+  stream_body<LPR, NV, TEAM, false>(a, positions);
+}
+
+// the default mode at a padded width (d < 4 LPR NV: 36, 60, 132, ...)
+template <int LPR, int NV, int TEAM>
+__global__ void __launch_bounds__(256, 2) k_stream_pad(StreamArgs a, int32_t positions) {
   stream_body<LPR, NV, TEAM, false>(a, positions);
 }
 
@@ -3050,7 +3100,10 @@ static StepArgs make_args(acf_apr_ctx* c, const acf_apr_tables* tb, const acf_ap
 // the kernels of the context's geometry and mapping (get_kernels)
 struct Kernels {
   void *clean_apr = nullptr, *clean_bpr = nullptr, *adv = nullptr, *flush = nullptr;
-  void* stream = nullptr;  // k_stream (one wave per slot, d <= 256): the default mode's instance
+  // the default mode's instance (one wave per slot, d <= 256): k_stream for a
+  // full row, k_stream_pad for a padded one (get_kernels picks by d)
+  void* stream = nullptr;
+  void* stream_pad = nullptr;
   void* stream_any = nullptr;  // k_stream_any: every other mode (run_streamed picks)
   void* stream_flush = nullptr;  // its write-back, k_stream_flush<LPR>
   void *hot_clean = nullptr, *hot_bpr = nullptr, *hot_adv = nullptr;  // k_hot_combine (list kernels)
@@ -3131,6 +3184,7 @@ static void kernel_ptrs(Kernels* k, int packed, int fused, int lists, int tri) {
     kernel_ptrs_team<LPR, NV, OPW>(k, fused);
     if constexpr (NV == 1) {
       k->stream = reinterpret_cast<void*>(&k_stream<LPR, NV, OPW>);
+      k->stream_pad = reinterpret_cast<void*>(&k_stream_pad<LPR, NV, OPW>);
       k->stream_any = reinterpret_cast<void*>(&k_stream_any<LPR, NV, OPW>);
       k->stream_flush = reinterpret_cast<void*>(&k_stream_flush<LPR>);
     }
@@ -3142,8 +3196,11 @@ static void kernel_ptrs(Kernels* k, int packed, int fused, int lists, int tri) {
 // per slot, 2 one lane-group per slot
 
 static int get_kernels(const acf_apr_ctx* c, Kernels* k, int fused = 0) {
-  return DISPATCH_GEOM(c->d, kernel_ptrs, k, is_packed(c, c->B), fused || c->shard, c->lists,
-                       c->tri && (fused || c->shard));
+  ACF_RET(DISPATCH_GEOM(c->d, kernel_ptrs, k, is_packed(c, c->B), fused || c->shard, c->lists,
+                        c->tri && (fused || c->shard)));
+  // k_stream has the row width folded: it runs a full row only (StreamArgsFull)
+  if (c->d != 4 * c->lpr * c->nv) k->stream = k->stream_pad;
+  return ACF_OK;
 }
 
 // The kind of a launch, for acf_apr_time_kernels (ms and launches per kind; include/acf_apr.h):
