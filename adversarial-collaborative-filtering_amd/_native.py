@@ -120,6 +120,11 @@ SIGNATURES = {
     "acf_apr_grid_workspace": (ctypes.c_int, [_I32, _I32, _I32, _I64, _I64, _I32, ctypes.POINTER(ctypes.c_size_t)]),
     "acf_apr_grid_train": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I64, _I64, _I32, ctypes.POINTER(HParams), _P, _P,
                                           _P, _I32, _I32, _P, _P, _P, ctypes.c_size_t, _I32, _P]),
+    "acf_apr_grid_pgd_workspace": (ctypes.c_int, [_I32, _I32, _I32, _I64, _I64, _I32,
+                                                  ctypes.POINTER(ctypes.c_size_t)]),
+    "acf_apr_grid_train_pgd": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I64, _I64, _I32, ctypes.POINTER(HParams),
+                                              ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), _P,
+                                              _P, _P, _I32, _I32, _P, _P, _P, ctypes.c_size_t, _I32, _P]),
     "acf_sample_epoch": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _U64, _I32, _I32, _P, _P,
                                         _P, _P]),
     "acf_gather_bpr_fwd_bwd": (ctypes.c_int, [_P, _P, _I64, _I64, _I32, _P, _P, _P, _I64, _F, _F, _P, _P, _P,

@@ -136,7 +136,25 @@ def parse_args(argv=None, flavor="ori"):
     p.add_argument("--grid_seeds", type=parse_grid_seeds, default=0,
                    help="Grid axis: N members per point, seeds 0..N-1 (they differ where the APR phase starts from "
                         "scratch, --adv_epoch 0; 0: off).")
+    p.add_argument("--grid_adv_iters", type=parse_grid_adv_iters, default=[],
+                   help="Grid axis (the outermost): steps K of the inner attack each member is trained against (comma "
+                        "separated, e.g. \"1,3,5\", each in [1, 32]).  K = 1 is APR's one normalised gradient step; "
+                        "K > 1 is a projected-gradient attack of K steps inside the eps ball, and that member logs "
+                        "under its run name plus _k<K>.")
+    p.add_argument("--adv_iters", type=parse_adv_iters, default=1,
+                   help="With --model apr: train the APR phase against a K-step projected-gradient attack inside "
+                        "the eps ball (1 to 32) instead of one normalised gradient step; the run is named "
+                        "<runName>_k<K>.  With --grid_*: the K of every member (unless --grid_adv_iters is given).  "
+                        "Check the result with --robust_eps ... --robust_iters.")
+    p.add_argument("--adv_step", type=parse_robust_step, default=None,
+                   help="Step size of --adv_iters / --grid_adv_iters (default: 2.5 * eps / K).")
     args = p.parse_args(argv)
+    if args.model != "apr" and (args.adv_iters > 1 or args.grid_adv_iters):
+        p.error("--adv_iters / --grid_adv_iters train the APR phase: they need --model apr")
+    if args.adv_step is not None and args.adv_iters == 1 and not args.grid_adv_iters:
+        p.error("--adv_step needs --adv_iters K > 1 or --grid_adv_iters")
+    if (args.adv_iters > 1 or args.grid_adv_iters) and (args.adv != "grad" or args.dns != 1):
+        p.error("--adv_iters / --grid_adv_iters need --adv grad and --dns 1")
     if grid_of(args) is not None:
         extras = [f for f in ("topk", "fold_in", "fold_in_items", "test_multi", "similar", "robust_eps",
                               "robust_lists", "certify_eps", "certify_radius", "diverse_lambda") if getattr(args, f)]
@@ -201,15 +219,42 @@ def parse_lambda_list(text):
     return out
 
 
+def parse_adv_iters(text):
+    """--adv_iters: an integer in [1, 32] (ops.GRID_MAX_ADV_ITERS)."""
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not an integer: {text!r}")
+    if not 1 <= v <= 32:
+        raise argparse.ArgumentTypeError(f"adv_iters must lie in [1, 32], got {text!r}")
+    return v
+
+
+def parse_grid_adv_iters(text):
+    """--grid_adv_iters: "1,3,5" -> [1, 3, 5]; every value in [1, 32]."""
+    return [parse_adv_iters(tok.strip()) for tok in str(text).split(",") if tok.strip()]
+
+
 def grid_of(args):
-    """The grid dicts of the --grid_* flags (model.MFGrid.product order: eps slowest,
-    then reg_adv, lr, the seed fastest), or None when no --grid_* flag is given."""
+    """The grid dicts of the --grid_* flags (model.MFGrid.product order: adv_iters
+    slowest when given, then eps, reg_adv, lr, the seed fastest), or None when no
+    --grid_* flag is given."""
     axes = dict(eps=args.grid_eps or None, reg_adv=args.grid_reg_adv or None, lr=args.grid_lr or None,
                 seeds=args.grid_seeds or None)
+    iters = getattr(args, "grid_adv_iters", None) or None
+    if iters is not None:
+        axes.update(adv_iters=iters, adv_step=getattr(args, "adv_step", None))
     if all(v is None for v in axes.values()):
         return None
     from .model import MFGrid
     return MFGrid.product(**axes)
+
+
+def single_adv_iters(args):
+    """K of a plain apr run trained through a one-member grid (--adv_iters K > 1 without a
+    --grid_* flag), else 0."""
+    K = getattr(args, "adv_iters", 1)
+    return K if K > 1 and grid_of(args) is None else 0
 
 
 def apr_run_name(dataset, model, embed_size, eps, reg_adv, time_stamp):
@@ -518,6 +563,8 @@ def main(argv=None, flavor="ori"):
     elif args.model == "apr":
         runName = "%s_%s_d%d_e%f_l%f_%s" % (args.dataset, args.model, args.embed_size, args.eps,
                                              args.reg_adv, time_stamp)
+        if single_adv_iters(args):  # trained through a one-member grid, named as that member is
+            runName += "_k%d" % args.adv_iters
         write2file(out, runName + ".out", runName)
         args.adver = 0
         m = MF(dataset.num_users, dataset.num_items, args).build_graph()
@@ -537,10 +584,14 @@ def main(argv=None, flavor="ori"):
             training_grid(gm, dataset, args, runName, epoch_start=args.adv_epoch, epoch_end=args.epochs,
                           time_stamp=time_stamp)
             return 0
-        amf = MF(dataset.num_users, dataset.num_items, args).build_graph(device=m.device)
-        write2file(out, runName + ".out", "Initialize APR")
-        training(amf, dataset, args, runName, epoch_start=args.adv_epoch, epoch_end=args.epochs,
-                 time_stamp=time_stamp)
+        if single_adv_iters(args):  # the K-step attack lives in the grid trainer: a grid of one
+            from .train import training_single_pgd
+            amf = training_single_pgd(m, dataset, args, runName, time_stamp)
+        else:
+            amf = MF(dataset.num_users, dataset.num_items, args).build_graph(device=m.device)
+            write2file(out, runName + ".out", "Initialize APR")
+            training(amf, dataset, args, runName, epoch_start=args.adv_epoch, epoch_end=args.epochs,
+                     time_stamp=time_stamp)
     else:
         print("model %r is not on the APR path of this build (bpr, apr)" % args.model, file=sys.stderr)
         return 2

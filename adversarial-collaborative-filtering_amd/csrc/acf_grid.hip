@@ -1,5 +1,6 @@
 // acf_grid.hip — grid training of libacf_apr.so: M APR/BPR models ("members") over ONE triplet
-// stream in one call (acf_apr_grid_workspace, acf_apr_grid_train).  The members
+// stream in one call (acf_apr_grid_workspace, acf_apr_grid_train, and their _pgd siblings with a
+// K-step inner attack per member).  The members
 // share the plan, which depends on the triplets alone, and differ in their tables
 // ([M][rows][dim], member-major) and in their hyper-parameters.  Context-free: everything
 // lives in the caller's workspace.  Nothing here touches the step kernels, k_stream or the
@@ -18,17 +19,30 @@
 // Schedule: three launches per batch, a lane-group of LPR lanes per (member, slot), members of
 // a slot adjacent in the grid (unit = slot * M + member), so a slot's records are read by
 // neighbouring lane-groups of one workgroup.
-//   k_grid_sum<ADV = 0>  clean: reads the tables; per unit the clean gradient G0 of the row
-//                        (terms in plan order, 256 at a time) and delta = eps * l2norm(G0) go to
-//                        scratch; the user-row owner writes the triplets' clean loss.  A BPR
-//                        member's G (with its reg term) is final here.
-//   k_grid_sum<ADV = 1>  adversarial (APR members only): reads the tables and every delta of the
+//   k_grid_sum<GRID_CLEAN>  reads the tables; per unit the clean gradient G0 of the row (terms in
+//                        plan order, 256 at a time) and delta = eps * l2norm(G0) go to scratch;
+//                        the user-row owner writes the triplets' clean loss.  A BPR member's G
+//                        (with its reg term) is final here.
+//   k_grid_sum<GRID_ADV>  adversarial (APR members only): reads the tables and every delta of the
 //                        batch; G = G0 + reg term + reg_adv * G_adv over its own scratch row.
 //   k_grid_apply         Adagrad on the unit's own table row: the only writes to the tables.
+// K-step members (acf_apr_grid_train_pgd, K = adv_iters[m] > 1, alpha = adv_step[m]): the clean
+// launch leaves delta_1 = project(alpha * l2norm(G0)), and max(K) - 1 launches of
+//   k_grid_sum<GRID_INNER>  (launch k = 1 .. max(K) - 1) follow it: the batch gradient at
+//                        (P + delta_k, Q + delta_k), summed as above, normalised, and
+//                        delta_{k+1} = project(delta_k + alpha * n) onto the eps ball
+//                        (k_adv_pgd_step's arithmetic, restated for a lane-group).
+// Delta is double-buffered with a PER-MEMBER PARITY: delta_k of member m lives in buffer
+// (k - 1) & 1 of m's own scratch slice.  Inner launch k reads the member's buffer (k - 1) & 1 and
+// writes its buffer k & 1; a unit whose member has K < k + 1 returns at once and touches nothing,
+// and the adversarial launch reads buffer (K - 1) & 1 of each member, where its delta_K was left.
+// A unit reads deltas of its own member only, so members of different K never meet in a buffer.
+// K = 1 is today's member: one buffer, eps * l2norm(G0), alpha unread; acf_apr_grid_train launches
+// instances compiled without the K-step branches (PGD = false), the same arithmetic.
 // No launch reads a table row or a delta that a workgroup of the same launch writes; a unit
 // writes only its own scratch row and, in k_grid_apply, its own table row.  No float atomics:
 // every sum's order is the plan's.  A unit's arithmetic depends on LPR (that is, on dim) alone,
-// never on M or on the unit's place in the grid.
+// never on M, on the other members' K or on the unit's place in the grid.
 // Build: one hipcc line with acf_apr.hip and the library's other units, same flags.
 
 #include <hip/hip_runtime.h>
@@ -47,7 +61,8 @@ constexpr int GRID_WG = 256;
 
 struct GridHP {  // what a member's kernels read of its acf_apr_hparams
   float lr, eps, reg, reg_adv, lo, hi;
-  int32_t adver, pad;
+  int32_t iters;  // 0: a BPR member; else K, the steps of the attack (1: the one-step delta)
+  float alpha;    // the step size of a K > 1 member
 };
 
 struct GridHPs {  // by value to k_grid_hp: 2 KiB of kernel arguments
@@ -162,10 +177,11 @@ struct GridArgs {
   const int32_t* soff;
   const uint16_t* te;
   const uint16_t* ts;
-  float *delta, *G;                           // scratch [M][S][d]
+  float *delta[2], *G;                        // scratch [M][S][d]; delta[1]: K-step members only
   float *lc, *la;                             // member 0's losses of this batch, or NULL
   int64_t U1, I1, nloss;                      // nloss: a member's stride in lc / la
   int32_t M, B, d, S;
+  int32_t it;                                 // GRID_INNER: the launch k, which makes delta_{k+1}
 };
 
 // Unit (member m, slot s) of this lane-group; false: none.
@@ -180,18 +196,40 @@ __device__ __forceinline__ bool grid_unit(const GridArgs& a, int& m, int& s, int
   return true;
 }
 
-template <int LPR, bool ADV>
+enum { GRID_CLEAN = 0, GRID_ADV = 1, GRID_INNER = 2 };
+
+// delta' = project(delta + alpha * n) onto the L2 ball of radius eps, n = l2norm(g):
+// v = delta + alpha * n (the product rounded, then the sum), s = sqrt(dot_row(v, v)),
+// delta' = v when s <= eps (s = 0 included), else v * (eps / s).
+template <int LPR>
+__device__ __forceinline__ RowV<1> grid_pgd_step(const RowV<1>& delta, const RowV<1>& g, float alpha, float eps) {
+  RowV<1> v = add_row(delta, scale_row(l2_delta<LPR, 1>(g, 1.0f), alpha));
+  const float s = sqrtf(dot_row<LPR, 1>(v, v));
+  if (!(s <= eps)) v = scale_row(v, eps / s);
+  return v;
+}
+
+// PGD: an instance of acf_apr_grid_train_pgd, where a member may have K > 1.  The instances of
+// acf_apr_grid_train (every K = 1, one delta buffer) are compiled without any of it.
+template <int LPR, int MODE, bool PGD>
 __global__ void __launch_bounds__(GRID_WG) k_grid_sum(GridArgs a) {
+  static_assert(PGD || MODE != GRID_INNER, "the inner launch belongs to the K-step entry");
+  constexpr bool ADV = MODE != GRID_CLEAN;  // the triplets' rows are taken at the perturbed point
   int m, s, l;
   if (!grid_unit<LPR>(a, m, s, l)) return;
   const GridHP h = a.hp[m];
-  if (ADV && !h.adver) return;
+  const bool adver = h.iters != 0;
+  if (ADV && !adver) return;
+  if (MODE == GRID_INNER && h.iters < a.it + 1) return;  // this member's delta_K is already in place
   const int d = a.d, B = a.B;
   const float* Pm = a.P + (int64_t)m * a.U1 * d;
   const float* Qm = a.Q + (int64_t)m * a.I1 * d;
-  float* dl = a.delta + (int64_t)m * a.S * d;
+  // the member's delta_k is in buffer (k - 1) & 1: GRID_INNER k reads that and writes k & 1,
+  // GRID_ADV reads delta_K, GRID_CLEAN writes delta_1
+  const int src = MODE == GRID_INNER ? (a.it - 1) & 1 : (PGD && MODE == GRID_ADV ? (h.iters - 1) & 1 : 0);
+  float* dl = a.delta[src] + (int64_t)m * a.S * d;
   float* Gm = a.G + (int64_t)m * a.S * d;
-  float* loss = ADV ? a.la : a.lc;
+  float* loss = MODE == GRID_ADV ? a.la : (MODE == GRID_CLEAN ? a.lc : nullptr);
   const uint32_t key = a.srow[s];
   const bool is_user = (int64_t)key < a.U1;
   const int32_t o = a.soff[s], cnt = a.soff[s + 1] - o;
@@ -222,12 +260,19 @@ __global__ void __launch_bounds__(GRID_WG) k_grid_sum(GridArgs a) {
     tot = c0 == 0 ? acc : add_row(tot, acc);
   }
   // reg: 2 reg w / (B d) per occurrence, twice in the APR graph
-  const float coef = (2.0f * h.reg / ((float)B * (float)d)) * (h.adver ? 2.0f : 1.0f) *
+  const float coef = (2.0f * h.reg / ((float)B * (float)d)) * (adver ? 2.0f : 1.0f) *
                      (float)(is_user ? cnt / 2 : cnt);
+  if (MODE == GRID_INNER) {
+    float* dn = a.delta[src ^ 1] + (int64_t)m * a.S * d;
+    store_row<LPR, 1>(dn, s, d, l, grid_pgd_step<LPR>(load_row<LPR, 1>(dl, s, d, l), tot, h.alpha, h.eps));
+    return;
+  }
   const int64_t row = is_user ? (int64_t)key : (int64_t)key - a.U1;
-  if (!ADV) {
-    if (h.adver) {
-      store_row<LPR, 1>(dl, s, d, l, l2_delta<LPR, 1>(tot, h.eps));
+  if (MODE == GRID_CLEAN) {
+    if (adver) {
+      store_row<LPR, 1>(dl, s, d, l,
+                        PGD && h.iters > 1 ? grid_pgd_step<LPR>(zero_row<1>(), tot, h.alpha, h.eps)
+                                    : l2_delta<LPR, 1>(tot, h.eps));
     } else if (h.reg != 0.f) {
       axpy_row(tot, coef, load_row<LPR, 1>(is_user ? Pm : Qm, row, d, l));
     }
@@ -261,11 +306,23 @@ __global__ void __launch_bounds__(GRID_WG) k_grid_apply(GridArgs a) {
 
 template <int LPR>
 void launch_clean(const GridArgs& a, unsigned grid, hipStream_t s) {
-  hipLaunchKernelGGL((k_grid_sum<LPR, false>), dim3(grid), dim3(GRID_WG), 0, s, a);
+  hipLaunchKernelGGL((k_grid_sum<LPR, GRID_CLEAN, false>), dim3(grid), dim3(GRID_WG), 0, s, a);
+}
+template <int LPR>
+void launch_clean_pgd(const GridArgs& a, unsigned grid, hipStream_t s) {
+  hipLaunchKernelGGL((k_grid_sum<LPR, GRID_CLEAN, true>), dim3(grid), dim3(GRID_WG), 0, s, a);
 }
 template <int LPR>
 void launch_adv(const GridArgs& a, unsigned grid, hipStream_t s) {
-  hipLaunchKernelGGL((k_grid_sum<LPR, true>), dim3(grid), dim3(GRID_WG), 0, s, a);
+  hipLaunchKernelGGL((k_grid_sum<LPR, GRID_ADV, false>), dim3(grid), dim3(GRID_WG), 0, s, a);
+}
+template <int LPR>
+void launch_adv_pgd(const GridArgs& a, unsigned grid, hipStream_t s) {
+  hipLaunchKernelGGL((k_grid_sum<LPR, GRID_ADV, true>), dim3(grid), dim3(GRID_WG), 0, s, a);
+}
+template <int LPR>
+void launch_inner(const GridArgs& a, unsigned grid, hipStream_t s) {
+  hipLaunchKernelGGL((k_grid_sum<LPR, GRID_INNER, true>), dim3(grid), dim3(GRID_WG), 0, s, a);
 }
 template <int LPR>
 void launch_apply(const GridArgs& a, unsigned grid, hipStream_t s) {
@@ -274,12 +331,13 @@ void launch_apply(const GridArgs& a, unsigned grid, hipStream_t s) {
 
 // ---- host: workspace layout --------------------------------------------------
 struct GridLayout {
-  size_t err, hp, hdr, srow, soff, te, ts, delta, G, total;
+  size_t err, hp, hdr, srow, soff, te, ts, delta, G, delta2, total;
 };
 
 inline size_t grid_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
-GridLayout grid_layout(int32_t M, int32_t B, int32_t nb, int32_t d) {
+// pgd: the second delta buffer of K-step members, after everything else
+GridLayout grid_layout(int32_t M, int32_t B, int32_t nb, int32_t d, bool pgd) {
   GridLayout L;
   size_t at = 0;
   auto take = [&](size_t bytes) {
@@ -297,6 +355,7 @@ GridLayout grid_layout(int32_t M, int32_t B, int32_t nb, int32_t d) {
   L.ts = take(n * S * 2);
   L.delta = take((size_t)M * S * d * sizeof(float));
   L.G = take((size_t)M * S * d * sizeof(float));
+  L.delta2 = pgd ? take((size_t)M * S * d * sizeof(float)) : 0;
   L.total = at;
   return L;
 }
@@ -316,14 +375,32 @@ int grid_check_shape(int32_t M, int32_t B, int32_t nb, int64_t U1, int64_t I1, i
   return ACF_OK;
 }
 
+int grid_workspace(int32_t M, int32_t B, int32_t nb, int64_t U1, int64_t I1, int32_t d, bool pgd, size_t* bytes) {
+  ACF_CHECK(bytes, ACF_E_INVALID, "bytes is NULL");
+  ACF_RET(grid_check_shape(M, B, nb, U1, I1, d));
+  *bytes = grid_layout(M, B, nb, d, pgd).total;
+  return ACF_OK;
+}
+
+// Both entries.  pgd: acf_apr_grid_train_pgd (adv_iters, adv_step and the second delta buffer);
+// else every member has K = 1.
+int grid_train(float* P, float* Q, float* accP, float* accQ, int32_t M, int64_t U1, int64_t I1, int32_t d,
+               const acf_apr_hparams* hp, bool pgd, const int32_t* adv_iters, const float* adv_step,
+               const int32_t* user, const int32_t* item_pos, const int32_t* item_neg, int32_t B, int32_t nb,
+               float* loss_clean, float* loss_adv, void* workspace, size_t workspace_bytes, int32_t check,
+               void* stream);
+
 }  // namespace
 
 extern "C" int acf_apr_grid_workspace(int32_t n_models, int32_t batch_size, int32_t n_batches,
                                       int64_t num_user_rows, int64_t num_item_rows, int32_t dim, size_t* bytes) {
-  ACF_CHECK(bytes, ACF_E_INVALID, "bytes is NULL");
-  ACF_RET(grid_check_shape(n_models, batch_size, n_batches, num_user_rows, num_item_rows, dim));
-  *bytes = grid_layout(n_models, batch_size, n_batches, dim).total;
-  return ACF_OK;
+  return grid_workspace(n_models, batch_size, n_batches, num_user_rows, num_item_rows, dim, false, bytes);
+}
+
+extern "C" int acf_apr_grid_pgd_workspace(int32_t n_models, int32_t batch_size, int32_t n_batches,
+                                          int64_t num_user_rows, int64_t num_item_rows, int32_t dim,
+                                          size_t* bytes) {
+  return grid_workspace(n_models, batch_size, n_batches, num_user_rows, num_item_rows, dim, true, bytes);
 }
 
 extern "C" int acf_apr_grid_train(float* P, float* Q, float* accP, float* accQ, int32_t n_models,
@@ -332,24 +409,54 @@ extern "C" int acf_apr_grid_train(float* P, float* Q, float* accP, float* accQ, 
                                   const int32_t* item_neg, int32_t batch_size, int32_t n_batches,
                                   float* loss_clean, float* loss_adv, void* workspace, size_t workspace_bytes,
                                   int32_t check, void* stream) {
+  return grid_train(P, Q, accP, accQ, n_models, num_user_rows, num_item_rows, dim, hp, false, nullptr, nullptr, user,
+                    item_pos, item_neg, batch_size, n_batches, loss_clean, loss_adv, workspace, workspace_bytes,
+                    check, stream);
+}
+
+extern "C" int acf_apr_grid_train_pgd(float* P, float* Q, float* accP, float* accQ, int32_t n_models,
+                                      int64_t num_user_rows, int64_t num_item_rows, int32_t dim,
+                                      const acf_apr_hparams* hp, const int32_t* adv_iters, const float* adv_step,
+                                      const int32_t* user, const int32_t* item_pos, const int32_t* item_neg,
+                                      int32_t batch_size, int32_t n_batches, float* loss_clean, float* loss_adv,
+                                      void* workspace, size_t workspace_bytes, int32_t check, void* stream) {
+  return grid_train(P, Q, accP, accQ, n_models, num_user_rows, num_item_rows, dim, hp, true, adv_iters, adv_step,
+                    user, item_pos, item_neg, batch_size, n_batches, loss_clean, loss_adv, workspace,
+                    workspace_bytes, check, stream);
+}
+
+namespace {
+
+int grid_train(float* P, float* Q, float* accP, float* accQ, int32_t M, int64_t U1, int64_t I1, int32_t d,
+               const acf_apr_hparams* hp, bool pgd, const int32_t* adv_iters, const float* adv_step,
+               const int32_t* user, const int32_t* item_pos, const int32_t* item_neg, int32_t B, int32_t nb,
+               float* loss_clean, float* loss_adv, void* workspace, size_t workspace_bytes, int32_t check,
+               void* stream) {
   ACF_CHECK(P && Q && accP && accQ, ACF_E_INVALID, "a table pointer is NULL");
   ACF_CHECK(hp, ACF_E_INVALID, "hp is NULL");
-  const int32_t M = n_models, B = batch_size, nb = n_batches, d = dim;
-  const int64_t U1 = num_user_rows, I1 = num_item_rows;
+  ACF_CHECK(!pgd || (adv_iters && adv_step), ACF_E_INVALID, "adv_iters or adv_step is NULL");
   ACF_RET(grid_check_shape(M, B, nb, U1, I1, d));
   ACF_CHECK(nb == 0 || (user && item_pos && item_neg), ACF_E_INVALID, "a triplet pointer is NULL");
   bool any_adv = false;
+  int32_t max_iters = 1;  // over the APR members: a BPR member has no delta
   GridHPs hps;
-  for (int m = 0; m < ACF_GRID_MAX_MODELS; ++m) hps.h[m] = GridHP{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0, 0};
+  for (int m = 0; m < ACF_GRID_MAX_MODELS; ++m) hps.h[m] = GridHP{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0, 0.f};
   for (int m = 0; m < M; ++m) {
     ACF_CHECK(hp[m].adv_mode == 0, ACF_E_INVALID, "member %d: adv_mode %d (random delta) is not a grid mode", m,
               (int)hp[m].adv_mode);
     ACF_CHECK(hp[m].zero_delta == 0, ACF_E_INVALID, "member %d: zero_delta is not a grid mode", m);
+    const int32_t K = pgd ? adv_iters[m] : 1;
+    const float alpha = pgd ? adv_step[m] : 0.f;
+    ACF_CHECK(K >= 1 && K <= ACF_GRID_MAX_ADV_ITERS, ACF_E_INVALID, "member %d: adv_iters must be in [1, %d], got %d",
+              m, ACF_GRID_MAX_ADV_ITERS, (int)K);
+    ACF_CHECK(alpha >= 0.f && alpha <= 3.402823466e38f, ACF_E_INVALID,
+              "member %d: adv_step must be finite and >= 0, got %g", m, (double)alpha);
     hps.h[m] = GridHP{hp[m].lr, hp[m].eps, hp[m].reg, hp[m].reg_adv, hp[m].clip_lo, hp[m].clip_hi,
-                      hp[m].adver ? 1 : 0, 0};
+                      hp[m].adver ? K : 0, alpha};
     any_adv = any_adv || hp[m].adver;
+    if (hp[m].adver && K > max_iters) max_iters = K;
   }
-  const GridLayout L = grid_layout(M, B, nb, d);
+  const GridLayout L = grid_layout(M, B, nb, d, pgd);
   ACF_CHECK(workspace, ACF_E_INVALID, "workspace is NULL");
   ACF_CHECK(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, ACF_E_INVALID, "workspace must be 16-byte aligned");
   ACF_CHECK(workspace_bytes >= L.total, ACF_E_INVALID, "workspace of %zu bytes, %zu needed", workspace_bytes,
@@ -388,7 +495,9 @@ extern "C" int acf_apr_grid_train(float* P, float* Q, float* accP, float* accQ, 
   GridArgs a;
   a.P = P, a.Q = Q, a.accP = accP, a.accQ = accQ;
   a.hp = dhp;
-  a.delta = (float*)(ws + L.delta), a.G = (float*)(ws + L.G);
+  a.delta[0] = (float*)(ws + L.delta), a.delta[1] = pgd ? (float*)(ws + L.delta2) : nullptr;
+  a.G = (float*)(ws + L.G);
+  a.it = 0;
   a.U1 = U1, a.I1 = I1, a.nloss = (int64_t)nb * B;
   a.M = M, a.B = B, a.d = d, a.S = S;
   int lpr = 1;
@@ -400,10 +509,18 @@ extern "C" int acf_apr_grid_train(float* P, float* Q, float* accP, float* accQ, 
     a.te = pl.te + b * T, a.ts = pl.ts + b * S;
     a.lc = loss_clean ? loss_clean + b * B : nullptr;
     a.la = loss_adv ? loss_adv + b * B : nullptr;
-    ACF_RET(DISPATCH_LPR(d, launch_clean, a, grid, s));
-    if (any_adv) ACF_RET(DISPATCH_LPR(d, launch_adv, a, grid, s));
+    if (pgd) {
+      ACF_RET(DISPATCH_LPR(d, launch_clean_pgd, a, grid, s));
+      for (a.it = 1; a.it < max_iters; ++a.it) ACF_RET(DISPATCH_LPR(d, launch_inner, a, grid, s));
+      if (any_adv) ACF_RET(DISPATCH_LPR(d, launch_adv_pgd, a, grid, s));
+    } else {
+      ACF_RET(DISPATCH_LPR(d, launch_clean, a, grid, s));
+      if (any_adv) ACF_RET(DISPATCH_LPR(d, launch_adv, a, grid, s));
+    }
     ACF_RET(DISPATCH_LPR(d, launch_apply, a, grid, s));
   }
   HIP_TRY(hipGetLastError());
   return ACF_OK;
 }
+
+}  // namespace

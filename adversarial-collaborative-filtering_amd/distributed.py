@@ -795,6 +795,9 @@ class ShardedAPR:
         collectives, so they queue behind them (and the routing's host copy of
         the counts waits for most of chunk k); the split-step figures of DESIGN
         §7 are world-1 measurements."""
+        if getattr(hp, "adv_iters", 1) != 1:  # hp: anything with StepHParams' fields
+            raise ValueError(f"ShardedAPR trains against the one-step delta only: adv_iters = {hp.adv_iters!r} "
+                             "needs ops.grid_train")
         bs = self.b_max if self.routed else self.B
         n = len(u) // bs
         spans = [(c0, min(chunk, n - c0)) for c0 in range(0, n, chunk)]

@@ -61,6 +61,10 @@ class MF:
         self.epochs = args.epochs
         self.twin = twin
         self.seed = getattr(args, "seed", None)
+        # the K-step inner attack: trained by MFGrid only (ops.grid_train); an MF carries the
+        # fields so that a grid member reports them, and its own trainers refuse K > 1
+        self.adv_iters = getattr(args, "adv_iters", 1)
+        self.adv_step = getattr(args, "adv_step", None)
         self.built = False
 
     # -- graph ----------------------------------------------------------------
@@ -127,11 +131,14 @@ class MF:
         return (self.embedding_P, self.embedding_Q, self.accumulator_P, self.accumulator_Q)
 
     def hparams(self, adver=None) -> ops.StepHParams:
+        adver = int(self.adver if adver is None else adver)
         return ops.StepHParams(lr=self.learning_rate, eps=self.eps, reg=self.reg,
-                               reg_adv=self.reg_adv, adver=int(self.adver if adver is None else adver),
-                               adv=self.adv, seed=int(self.seed or 0))
+                               reg_adv=self.reg_adv, adver=adver, adv=self.adv, seed=int(self.seed or 0),
+                               adv_iters=self.adv_iters if adver else 1,  # a BPR step has no attack
+                               adv_step=self.adv_step if adver else None)
 
     def context(self, batch_size: int, n_batches: int) -> ops.APRContext:
+        self.hparams().require_one_step("MF.context")
         ctx = self._ctx
         if ctx is None or not ctx.fits(batch_size, n_batches):
             cap_b = max(batch_size, ctx.max_batch_size if ctx else 0)
@@ -142,6 +149,7 @@ class MF:
 
     def pipeline(self, batch_size: int, chunk: int = 512) -> ops.PlanPipeline:
         """Epoch trainer: chunks of `chunk` batches, next chunk planned while one trains."""
+        self.hparams().require_one_step("MF.pipeline")
         p = self._pipe
         if p is None or p.batch_size != batch_size or p.chunk != chunk:
             # concurrent planning for large batches only (device-wide sort plan); small
@@ -322,15 +330,17 @@ class MFGrid:
     """M MF models over one triplet stream: the sweep the reference runs as one
     job per (eps, reg_adv) point, trained by ops.grid_train in one call per epoch.
 
-    grid: a list of dicts over GRID_KEYS (eps, reg_adv, lr, reg, adver, seed);
-    a key a dict leaves out takes the value of `args`.  The tables are
+    grid: a list of dicts over GRID_KEYS (eps, reg_adv, lr, reg, adver, seed,
+    adv_iters, adv_step); a key a dict leaves out takes the value of `args`
+    (adv_iters 1, adv_step None where args has none).  adv_iters = K > 1 trains the
+    member against a K-step projected-gradient attack (ops.grid_train).  The tables are
     [M, rows, d], member-major: slice m is an ordinary dense table, and
     member(m) is an MF whose tables are views of it, so evaluation, top-K,
     robustness, certificates, neighbours and checkpoints work on a member as on
     any MF.  Members are initialised as MF._create_variables does with that
     member's seed (equal seeds: equal tables)."""
 
-    GRID_KEYS = ("eps", "reg_adv", "lr", "reg", "adver", "seed")
+    GRID_KEYS = ("eps", "reg_adv", "lr", "reg", "adver", "seed", "adv_iters", "adv_step")
 
     def __init__(self, num_users, num_items, args, grid, device=None, _init=True):
         import copy
@@ -353,6 +363,10 @@ class MFGrid:
             a = copy.copy(args)
             if not hasattr(a, "adver"):
                 a.adver = 1
+            if not hasattr(a, "adv_iters"):
+                a.adv_iters = 1
+            if not hasattr(a, "adv_step"):
+                a.adv_step = None
             for k, v in g.items():
                 setattr(a, k, v)
             self.member_args.append(a)
@@ -367,19 +381,24 @@ class MFGrid:
         return len(self.grid)
 
     @staticmethod
-    def product(eps=None, reg_adv=None, lr=None, seeds=None):
+    def product(eps=None, reg_adv=None, lr=None, seeds=None, adv_iters=None, adv_step=None):
         """The product of the given lists as grid dicts, in itertools.product order
-        over (eps, reg_adv, lr, seed): eps varies slowest, the seed fastest.  A list
-        left out (None) is not a key of the dicts.  seeds: a list of seeds, or an
-        int N for seeds 0..N-1."""
+        over (adv_iters, eps, reg_adv, lr, seed): adv_iters, when given, varies
+        slowest, then eps, the seed fastest.  A list left out (None) is not a key of
+        the dicts.  seeds: a list of seeds, or an int N for seeds 0..N-1.  adv_step:
+        one step size for every member (not an axis; None: each member's default)."""
         import itertools
         if isinstance(seeds, int):
             seeds = list(range(seeds))
-        axes = [(k, list(v)) for k, v in (("eps", eps), ("reg_adv", reg_adv), ("lr", lr), ("seed", seeds))
-                if v is not None]
+        axes = [(k, list(v)) for k, v in (("adv_iters", adv_iters), ("eps", eps), ("reg_adv", reg_adv), ("lr", lr),
+                                          ("seed", seeds)) if v is not None]
         if any(not v for _, v in axes):
             raise ValueError("a grid axis is empty")
-        return [dict(zip([k for k, _ in axes], vals)) for vals in itertools.product(*[v for _, v in axes])]
+        grid = [dict(zip([k for k, _ in axes], vals)) for vals in itertools.product(*[v for _, v in axes])]
+        if adv_step is not None:
+            for g in grid:
+                g["adv_step"] = adv_step
+        return grid
 
     def _allocate(self, device):
         self.device = torch.device(device) if device is not None else default_device()
@@ -429,7 +448,8 @@ class MFGrid:
 
     def hparams(self):
         """The members' StepHParams, in member order."""
-        return [ops.StepHParams(lr=a.lr, eps=a.eps, reg=a.reg, reg_adv=a.reg_adv, adver=int(bool(a.adver)))
+        return [ops.StepHParams(lr=a.lr, eps=a.eps, reg=a.reg, reg_adv=a.reg_adv, adver=int(bool(a.adver)),
+                                adv_iters=a.adv_iters, adv_step=a.adv_step)
                 for a in self.member_args]
 
     def member(self, m):
@@ -461,7 +481,8 @@ def argparse_like(mf):
     """The constructor arguments of an MF, read back from it (MFGrid.from_model)."""
     import argparse
     return argparse.Namespace(embed_size=mf.embedding_size, lr=mf.learning_rate, reg=mf.reg, dns=mf.dns, adv=mf.adv,
-                              eps=mf.eps, adver=mf.adver, reg_adv=mf.reg_adv, epochs=mf.epochs, seed=mf.seed)
+                              eps=mf.eps, adver=mf.adver, reg_adv=mf.reg_adv, epochs=mf.epochs, seed=mf.seed,
+                              adv_iters=mf.adv_iters, adv_step=mf.adv_step)
 
 
 class Session:

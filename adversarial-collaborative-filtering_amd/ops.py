@@ -103,8 +103,23 @@ class StepHParams:
     zero_delta: int = 0
     clip_lo: float = CLIP_LO
     clip_hi: float = CLIP_HI
+    # the K-step inner attack of grid_train (Python side only: not fields of the C struct);
+    # adv_step None is 2.5 * eps / adv_iters.  Every other trainer refuses adv_iters > 1.
+    adv_iters: int = 1
+    adv_step: float | None = None
+
+    def require_one_step(self, who: str = "this trainer") -> None:
+        """ValueError unless adv_iters is 1: only grid_train trains against a K-step attack,
+        and no other trainer may train one-step silently."""
+        if self.adv_iters != 1:
+            raise ValueError(f"{who} trains against the one-step delta only: adv_iters = {self.adv_iters!r} "
+                             "needs ops.grid_train (MFGrid, --adv_iters)")
 
     def to_c(self) -> HParams:
+        self.require_one_step()
+        return self._struct()
+
+    def _struct(self) -> HParams:
         key = (self.lr, self.eps, self.reg, self.reg_adv, self.adver, self.adv, self.seed, self.zero_delta,
                self.clip_lo, self.clip_hi)
         c = self.__dict__.get("_c")
@@ -1824,6 +1839,7 @@ def fold_in_items(P, Q, item_off, user_pos, item_neg, hp: StepHParams, epochs: i
 GRID_MAX_MODELS = 64    # ACF_GRID_MAX_MODELS
 GRID_MAX_BATCH = 1024   # ACF_GRID_MAX_BATCH
 GRID_MAX_DIM = 256
+GRID_MAX_ADV_ITERS = 32  # ACF_GRID_MAX_ADV_ITERS
 
 
 def grid_workspace(n_models: int, batch_size: int, n_batches: int, num_user_rows: int, num_item_rows: int,
@@ -1831,6 +1847,30 @@ def grid_workspace(n_models: int, batch_size: int, n_batches: int, num_user_rows
     """Bytes of workspace grid_train needs (acf_apr_grid_workspace; host only)."""
     return _workspace_bytes("acf_apr_grid_workspace", n_models, batch_size, n_batches, num_user_rows, num_item_rows,
                             dim)
+
+
+def grid_pgd_workspace(n_models: int, batch_size: int, n_batches: int, num_user_rows: int, num_item_rows: int,
+                       dim: int) -> int:
+    """Bytes of workspace grid_train needs when a member has adv_iters > 1
+    (acf_apr_grid_pgd_workspace; host only): grid_workspace plus the second delta buffer."""
+    return _workspace_bytes("acf_apr_grid_pgd_workspace", n_models, batch_size, n_batches, num_user_rows,
+                            num_item_rows, dim)
+
+
+def grid_pgd_arguments(h: StepHParams, m: int = 0):
+    """(adv_iters, adv_step) of grid member m after their checks (ValueError / TypeError);
+    adv_step None is 2.5 * eps / adv_iters (pgd_arguments' default)."""
+    K = h.adv_iters
+    if isinstance(K, bool) or not isinstance(K, int):
+        raise TypeError(f"hparams[{m}]: adv_iters must be an int, got {type(K).__name__}")
+    if not 1 <= K <= GRID_MAX_ADV_ITERS:
+        raise ValueError(f"hparams[{m}]: adv_iters must lie in [1, {GRID_MAX_ADV_ITERS}], got {K}")
+    alpha = 2.5 * float(h.eps) / K if h.adv_step is None else float(h.adv_step)
+    if not (math.isfinite(alpha) and alpha >= 0):
+        if h.adv_step is not None or K > 1:
+            raise ValueError(f"hparams[{m}]: adv_step must be finite and >= 0, got {alpha!r}")
+        alpha = 0.0  # a one-step member never reads it
+    return K, alpha
 
 
 def grid_train(P, Q, accP, accQ, hparams, user, item_pos, item_neg, batch_size: int, *, losses: bool = False,
@@ -1846,7 +1886,11 @@ def grid_train(P, Q, accP, accQ, hparams, user, item_pos, item_neg, batch_size: 
     bit for bit, whatever M and its position are; equal inputs give equal bits.
     losses: return (loss_clean, loss_adv) [M, n] float32, the per-triplet losses of
     each batch before its update (loss_adv rows of members with adver = 0 stay 0);
-    otherwise None.  Bad arguments raise ValueError / TypeError before any native
+    otherwise None.  A member with adv_iters = K > 1 trains against a K-step
+    projected-gradient attack of step adv_step (None: 2.5 * eps / K) inside the
+    eps ball instead of the one normalised gradient step; such a grid goes through
+    acf_apr_grid_train_pgd, a grid of one-step members through acf_apr_grid_train
+    as before, and a K = 1 member gives the same bits either way.  Bad arguments raise ValueError / TypeError before any native
     call; with check, an index outside its table raises NativeIndexError before
     any table is written."""
     hps = list(hparams)
@@ -1858,6 +1902,7 @@ def grid_train(P, Q, accP, accQ, hparams, user, item_pos, item_neg, batch_size: 
             raise TypeError(f"hparams[{m}] must be a StepHParams, got {type(h).__name__}")
         if h.adv != "grad" or h.zero_delta:
             raise ValueError(f"hparams[{m}]: adv='random' and zero_delta are not grid modes")
+    pgd = [grid_pgd_arguments(h, m) for m, h in enumerate(hps)]
     for t, n in ((P, "embedding_P"), (Q, "embedding_Q"), (accP, "accumulator_P"), (accQ, "accumulator_Q")):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{n} must be a torch.Tensor, got {type(t).__name__}")
@@ -1890,11 +1935,17 @@ def grid_train(P, Q, accP, accQ, hparams, user, item_pos, item_neg, batch_size: 
     U1, I1 = P.shape[1], Q.shape[1]
     lc = torch.zeros((M, n), dtype=torch.float32, device=dev) if losses else None
     la = torch.zeros((M, n), dtype=torch.float32, device=dev) if losses else None
-    chp = (HParams * M)(*[h.to_c() for h in hps])
-    nbytes = grid_workspace(M, B, nb, U1, I1, d)
+    chp = (HParams * M)(*[h._struct() for h in hps])
+    if all(K == 1 for K, _ in pgd):
+        entry, extra = "acf_apr_grid_train", ()
+        nbytes = grid_workspace(M, B, nb, U1, I1, d)
+    else:
+        entry = "acf_apr_grid_train_pgd"
+        extra = ((ctypes.c_int32 * M)(*[K for K, _ in pgd]), (ctypes.c_float * M)(*[a for _, a in pgd]))
+        nbytes = grid_pgd_workspace(M, B, nb, U1, I1, d)
     work = _workspace(nbytes, 8, dev)
     with _on(dev):
-        call("acf_apr_grid_train", P.data_ptr(), Q.data_ptr(), accP.data_ptr(), accQ.data_ptr(), M, U1, I1, d, chp,
+        call(entry, P.data_ptr(), Q.data_ptr(), accP.data_ptr(), accQ.data_ptr(), M, U1, I1, d, chp, *extra,
              u.data_ptr() if n else None, i.data_ptr() if n else None, j.data_ptr() if n else None, B, nb,
              _ptr(lc), _ptr(la), work.data_ptr(), nbytes, int(bool(check)), _stream_ptr(dev))
     return (lc, la) if losses else None

@@ -277,13 +277,17 @@ def training(model, dataset, args, runName, epoch_start, epoch_end, time_stamp, 
 def grid_run_names(grid_model, args, time_stamp):
     """The run name of every member: the name cli.main gives a single apr run at
     that member's (eps, reg_adv); a grid that also varies lr or the seed appends
-    _lr<lr> / _s<seed>, which no single-model name has."""
+    _lr<lr> / _s<seed>, which no single-model name has.  A member trained against a
+    K-step attack (adv_iters = K > 1) gets _k<K> right after the single-run name;
+    one-step members' names are unchanged."""
     from .cli import apr_run_name
     lrs = {a.lr for a in grid_model.member_args}
     seeds = {getattr(a, "seed", None) for a in grid_model.member_args}
     names = []
     for a in grid_model.member_args:
         name = apr_run_name(args.dataset, args.model, args.embed_size, a.eps, a.reg_adv, time_stamp)
+        if _adv_iters(a) > 1:
+            name += "_k%d" % _adv_iters(a)
         if len(lrs) > 1:
             name += "_lr%f" % a.lr
         if len(seeds) > 1:
@@ -294,33 +298,49 @@ def grid_run_names(grid_model, args, time_stamp):
     return names
 
 
+def _adv_iters(a):
+    return int(getattr(a, "adv_iters", 1) or 1)
+
+
 def write_grid_table(path, name, grid_model, best):
     """<runName>.grid: one line per member, "member<TAB>eps<TAB>reg_adv<TAB>lr<TAB>reg<TAB>adver<TAB>seed<TAB>
-    best_epoch<TAB>hr10<TAB>ndcg10" (floats by repr; best_epoch -1 and nan metrics: never evaluated)."""
+    best_epoch<TAB>hr10<TAB>ndcg10" (floats by repr; best_epoch -1 and nan metrics: never evaluated).  A grid
+    with a member of adv_iters > 1 appends "<TAB>adv_iters<TAB>adv_step" to every line (adv_step: the step
+    size trained with, ops.grid_pgd_arguments); a grid of one-step members writes the ten columns alone."""
+    from .ops import StepHParams, grid_pgd_arguments
     os.makedirs(path, exist_ok=True)
+    pgd = any(_adv_iters(a) > 1 for a in grid_model.member_args)
     with open(os.path.join(path, name), "w") as f:
         for m, a in enumerate(grid_model.member_args):
             b = best[m]
-            f.write("%d\t%r\t%r\t%r\t%r\t%d\t%d\t%d\t%r\t%r\n" % (
+            line = "%d\t%r\t%r\t%r\t%r\t%d\t%d\t%d\t%r\t%r" % (
                 m, float(a.eps), float(a.reg_adv), float(a.lr), float(a.reg), int(bool(a.adver)),
                 int(getattr(a, "seed", 0) or 0), b.get("epoch", -1), float(b.get("hr10", float("nan"))),
-                float(b.get("ndcg10", float("nan")))))
+                float(b.get("ndcg10", float("nan"))))
+            if pgd:
+                K, alpha = grid_pgd_arguments(StepHParams(eps=a.eps, adv_iters=_adv_iters(a),
+                                                          adv_step=getattr(a, "adv_step", None)), m)
+                line += "\t%d\t%r" % (K, float(alpha))
+            f.write(line + "\n")
 
 
 def read_grid_table(file):
-    """The rows [(member, eps, reg_adv, lr, reg, adver, seed, best_epoch, hr10, ndcg10)] write_grid_table wrote."""
+    """The rows [(member, eps, reg_adv, lr, reg, adver, seed, best_epoch, hr10, ndcg10)] write_grid_table wrote;
+    rows of a file with the two trailing columns end in (..., adv_iters, adv_step)."""
     rows = []
     with open(file) as f:
         for n, line in enumerate(f):
             p = line.rstrip("\n").split("\t")
-            if len(p) != 10:
-                raise ValueError(f"{file}: line {n} has {len(p)} fields, expected 10")
-            rows.append((int(p[0]), float(p[1]), float(p[2]), float(p[3]), float(p[4]), int(p[5]), int(p[6]),
-                         int(p[7]), float(p[8]), float(p[9])))
+            if len(p) not in (10, 12):
+                raise ValueError(f"{file}: line {n} has {len(p)} fields, expected 10 or 12")
+            row = (int(p[0]), float(p[1]), float(p[2]), float(p[3]), float(p[4]), int(p[5]), int(p[6]),
+                   int(p[7]), float(p[8]), float(p[9]))
+            rows.append(row + (int(p[10]), float(p[11])) if len(p) == 12 else row)
     return rows
 
 
-def training_grid(grid_model, dataset, args, runName, epoch_start, epoch_end, time_stamp, sampler=None):
+def training_grid(grid_model, dataset, args, runName, epoch_start, epoch_end, time_stamp, sampler=None,
+                  single=False):
     """`training` for an MFGrid: every epoch draws ONE sampled triplet stream and
     trains all members on it in one ops.grid_train call.  The members therefore
     see common negatives (common random numbers): a difference between two
@@ -331,9 +351,14 @@ def training_grid(grid_model, dataset, args, runName, epoch_start, epoch_end, ti
     own <name>.out / .hr / .ndcg in the reference's formats, under the name a
     single run at its (eps, reg_adv) gets (grid_run_names); the best epoch is
     tracked per member, and <runName>.grid holds one line per member
-    (write_grid_table).  Returns the per-member best results."""
+    (write_grid_table).  Returns the per-member best results.
+    single: a grid of one standing in for a plain run (training_single_pgd): the
+    member logs under runName itself and is checkpointed as `training` does, every
+    args.ckpt epochs and at the end, and no .grid table is written."""
     M = len(grid_model)
-    names = grid_run_names(grid_model, args, time_stamp)
+    if single and M != 1:
+        raise ValueError(f"single=True is a grid of one, got {M} members")
+    names = [runName] if single else grid_run_names(grid_model, args, time_stamp)
     out = args.path + "out/" + args.opath
     eval_feed_dicts = init_eval_model(dataset, args)
     if sampler is None:
@@ -375,8 +400,30 @@ def training_grid(grid_model, dataset, args, runName, epoch_start, epoch_end, ti
                 for idx, (hr_k, ndcg_k, auc_k) in enumerate(np.swapaxes(best[m]["result"], 0, 1)):
                     write2file(out, names[m] + ".out",
                                "K = %d: HR = %.4f, NDCG = %.4f AUC = %.4f" % (idx + 1, hr_k, ndcg_k, auc_k))
+        if single and args.ckpt > 0 and epoch_count % args.ckpt == 0:
+            save_checkpoint(members[0], ckpt_dirs(args, time_stamp)[0], epoch_count)
+    if single:
+        save_checkpoint(members[0], ckpt_dirs(args, time_stamp)[0], epoch_count)
+        return best
     write_grid_table(out, runName + ".grid", grid_model, best)
     if getattr(args, "ckpt", 0) > 0:
         for m, mf in enumerate(members):
             save_checkpoint(mf, ckpt_dirs(args, "%s_g%d" % (time_stamp, m))[0], epoch_count)
     return best
+
+
+def training_single_pgd(bpr_model, dataset, args, runName, time_stamp):
+    """The APR phase of a plain apr run trained against a K-step attack (args.adv_iters
+    > 1): only the grid trainer has that attack, so the run is a grid of one.  The member
+    branches from the BPR model (args.adv_epoch > 0) or starts from the seed's init, as the
+    members of a --grid_* run do, trains epochs adv_epoch .. epochs and evaluates,
+    logs and checkpoints under runName as `training` would.  Returns the member, an MF."""
+    from .model import MFGrid
+    if args.adv_epoch > 0:
+        gm = MFGrid.from_model(bpr_model, [{}], args)
+    else:
+        gm = MFGrid(dataset.num_users, dataset.num_items, args, [{}], device=bpr_model.device)
+    write2file(args.path + "out/" + args.opath, runName + ".out", "Initialize APR")
+    training_grid(gm, dataset, args, runName, epoch_start=args.adv_epoch, epoch_end=args.epochs,
+                  time_stamp=time_stamp, single=True)
+    return gm.member(0)

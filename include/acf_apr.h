@@ -903,6 +903,40 @@ int acf_apr_grid_train(float* P, float* Q, float* accP, float* accQ, int32_t n_m
                        float* loss_clean, float* loss_adv, void* workspace, size_t workspace_bytes, int32_t check,
                        void* stream);
 
+/* ---- grid training against a K-step inner attack ------------------------------
+ * acf_apr_grid_train with, per member, a projected-gradient attack of adv_iters[m]
+ * steps of size adv_step[m] in place of the one normalised gradient step (Madry-style
+ * adversarial training inside APR's per-row L2 ball).  Per
+ * member and batch, with K = adv_iters[m], alpha = adv_step[m], eps = hp[m].eps:
+ *   delta_0 = 0 on every unique row of the batch; for k = 1 .. K:
+ *     g_k = the batch's BPR-loss gradient of the row with the triplets' rows taken at
+ *           (P + delta_{k-1}, Q + delta_{k-1}), summed in the plan's order as above;
+ *     n_k = g_k * rsqrt(max(g_k . g_k, 1e-12));  v = delta_{k-1} + alpha * n_k (the
+ *     product rounded, then the sum);  s = sqrt(v . v);  delta_k = v when s <= eps,
+ *     else v * (eps / s)  (acf_adv_pgd's step).
+ *   The step's gradient is acf_apr_grid_train's with delta = delta_K: the clean
+ *   gradient at the unperturbed tables, the reg term, reg_adv times the gradient at
+ *   delta_K; loss_adv is the per-triplet loss at delta_K.
+ * A member with K = 1 is acf_apr_grid_train's member, the same bits (delta = eps *
+ * l2norm(g_1); its adv_step is not read).  A member with adver = 0 has no delta; its
+ * two fields are range-checked and otherwise ignored.  Both tables' deltas always
+ * move.  adv_iters, adv_step: HOST arrays of n_models; 1 <= adv_iters[m] <=
+ * ACF_GRID_MAX_ADV_ITERS, adv_step[m] finite and >= 0, else ACF_E_INVALID before any
+ * launch, as is a NULL array.  Schedule: per batch the clean launch, max(K) - 1 inner
+ * launches (a member whose K is reached does nothing in the later ones), the
+ * adversarial launch, Adagrad.  workspace: acf_apr_grid_pgd_workspace(...) bytes,
+ * acf_apr_grid_workspace's plus a second delta buffer of n_models * 3 * batch_size *
+ * dim floats.  Everything else, the guarantees included (a member's bits do not
+ * depend on n_models, its position or the other members' K), is acf_apr_grid_train's. */
+#define ACF_GRID_MAX_ADV_ITERS 32
+int acf_apr_grid_pgd_workspace(int32_t n_models, int32_t batch_size, int32_t n_batches, int64_t num_user_rows,
+                               int64_t num_item_rows, int32_t dim, size_t* bytes);
+int acf_apr_grid_train_pgd(float* P, float* Q, float* accP, float* accQ, int32_t n_models, int64_t num_user_rows,
+                           int64_t num_item_rows, int32_t dim, const acf_apr_hparams* hp, const int32_t* adv_iters,
+                           const float* adv_step, const int32_t* user, const int32_t* item_pos,
+                           const int32_t* item_neg, int32_t batch_size, int32_t n_batches, float* loss_clean,
+                           float* loss_adv, void* workspace, size_t workspace_bytes, int32_t check, void* stream);
+
 /* ---- sampler: shuffle/_get_train_batch (APR.py:39-81) --------------------
  * Shuffles the n_pos positive pairs with a counter-based permutation of
  * `seed`, keeps floor(n_pos / batch_size) * batch_size of them (drop-last,
